@@ -13,7 +13,10 @@ Workload
           nothing is exchanged while filtering, and every step ends with the one exchange the path has: an all-gather
           of the smoothed lon/lat.  Per-GPU work is fixed as N grows ("weak").
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ``--steps`` steps and prints the line; the figures
+below that take runs of their own (`serial`, `cpu_baseline`, `pcie_inclusive`, `extra`, and with N > 1 `all_gather_alone`
+and `filter_only`) are measured only with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step computed
+(see ``dump_outputs``).  Extra objects:
   roofline      SURVEY.md section 8(d)'s figure: `achieved` = 512 algorithmic HBM bytes per track-step (192 forward + 320
                 smoother) x the track-steps per second of the timed region, per GPU, against 8 TB/s (the forward and smoother
                 kernels of different steps share the chip, so the path's rate is the job's rate); `traffic` = HBM bytes of one
@@ -67,6 +70,31 @@ FLOPS_NOMINAL = 2.0e4  # SURVEY.md §8d estimate of the REFERENCE algorithm (fp6
 # rocprofv3 PMC summary of this command for the current kernel generation (see profiles/README.md for the passes)
 COUNTERS_CSV = os.path.join(ROOT, "profiles", "r05_counters_per_track_step.csv")
 EVENT_EVERY = 4  # steps between two steps whose kernels are bracketed by HIP events (see the timed loop)
+# --dump-outputs: tracks in the fixed sample of the histories (4 histories x 501 rows x 40 doubles per track: 41 MB)
+DUMP_TRACKS = 256
+DUMP_SEED = 20240601
+
+
+def dump_sample(ntracks: int) -> np.ndarray:
+    """Track indices of the --dump-outputs sample: every track of a batch of at most DUMP_TRACKS, otherwise a fixed seeded
+    choice of DUMP_TRACKS of them, ascending."""
+    if ntracks <= DUMP_TRACKS:
+        return np.arange(ntracks, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ntracks, DUMP_TRACKS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, db, ntracks: int):
+    """What a caller of the timed path receives from one step (DeviceBatch.download, track first): `means` / `means_smoothed`
+    (T, Nmax+1, 4) and `covs` / `covs_smoothed` (T, Nmax+1, 4, 4) of the tracks of ``dump_sample``, and `status` of every
+    track, each as DIR/<name>.npy in float64."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    idx = torch.as_tensor(dump_sample(ntracks), device=db.device)
+    got = db.download(("means", "covs", "means_smoothed", "covs_smoothed"), idx)
+    got["status"] = db.status_host()
+    for name, a in got.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def load_counters():
@@ -362,9 +390,9 @@ def _main(stack):
                     help="tracks of the whole job, cut into one contiguous shard per GPU (default: 10 000 at --gpus 1 = "
                          "BASELINE configs[1]; 12 500 x N otherwise = configs[2]'s shard size, 100 000 at --gpus 8)")
     ap.add_argument("--tracks", type=int, default=None, help="tracks per GPU (overrides --total-tracks; tests)")
-    ap.add_argument("--cpu-tracks", type=int, default=3072, help="tracks in the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-tracks", type=int, default=3072, help="--full: tracks in the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-ref-tracks", type=int, default=8,
-                    help="tracks of the batch timed through the oracle's per-track form, the reference's own call sequence "
+                    help="--full: tracks of the batch timed through the oracle's per-track form, the reference's own call sequence "
                          "(about 0.4 s per 500-step track; 0 = skip)")
     ap.add_argument("--lanes", type=int, default=0, help="forward-kernel lanes per track (0 = by batch size, 1, 4)")
     ap.add_argument("--no-gather", action="store_true", help="skip the all-gather of smoothed lon/lat when N>1")
@@ -378,7 +406,7 @@ def _main(stack):
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run the gather even with one rank (rehearsal of the N>1 path)")
     ap.add_argument("--cpu-pool-tracks", type=int, default=768,
-                    help="tracks per worker in the all-cores CPU-baseline leg (0 = skip)")
+                    help="--full: tracks per worker in the all-cores CPU-baseline leg (0 = skip)")
     # experiments (defaults are the measured best)
     ap.add_argument("--forward-cus", type=int, default=None)
     ap.add_argument("--forward-streams", type=int, default=None)
@@ -406,13 +434,22 @@ def _main(stack):
     ap.add_argument("--sequence-form", default="auto", choices=("auto", "per_step", "split", "single"),
                     help="with --sequence auto: run the untimed comparison of the three launch forms (auto), or pin one of them "
                          "without comparing (profiling passes)")
-    ap.add_argument("--no-fleet", action="store_true", help="skip the `extra.fleet_100k` entry (100 000 distinct tracks through batch.run_fleet)")
+    ap.add_argument("--no-fleet", action="store_true", help="--full: skip the `extra.fleet_100k` entry (100 000 distinct tracks through batch.run_fleet)")
     ap.add_argument("--fleet-tracks", type=int, default=100_000)
     ap.add_argument("--fleet-chunk", type=int, default=None, help="window size of the fleet entry (default: batch.FLEET_CHUNK)")
     ap.add_argument("--no-gp", action="store_true",
-                    help="skip the `extra.gp_config4` entry (BASELINE configs[4]: one batched GP objective at 1000 x 2000, "
+                    help="--full: skip the `extra.gp_config4` entry (BASELINE configs[4]: one batched GP objective at 1000 x 2000, "
                          "measured after the timed region at --gpus 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the serial leg, the CPU baselines and the GPU-vs-oracle "
+                         "cross-check (--cpu-*), the PCIe-inclusive rate, the `extra` entries (--no-gp, --no-fleet), and with N > 1 "
+                         "the exchange alone and the loop without it (default: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the histories the last timed step computed for a fixed sample of "
+                         f"{DUMP_TRACKS} tracks, and every track's status, as DIR/<name>.npy (float64; rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as a child job (one process per GPU) before anything in
@@ -422,7 +459,7 @@ def _main(stack):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     pool_result = None
-    if world == 1 and args.gpus == 1 and args.cpu_tracks > 0 and args.cpu_pool_tracks > 0:
+    if args.full and world == 1 and args.gpus == 1 and args.cpu_tracks > 0 and args.cpu_pool_tracks > 0:
         # all-cores leg of the CPU baseline: forked workers, so it runs before this process touches the GPU
         procs = host_core_share()
         pool_result = (procs,) + cpu_baseline_pool(procs, args.cpu_pool_tracks)
@@ -444,7 +481,7 @@ def _main(stack):
         # STE_BENCH_BACKEND=gloo lets several ranks share one GPU for a rehearsal of the N>1 control flow (RCCL refuses
         # two ranks on one device); the driver's multi-GPU runs use the default, nccl = RCCL over xGMI.
         backend = os.environ.get("STE_BENCH_BACKEND", "nccl")
-        if backend == "nccl" and os.environ.get("STE_BENCH_KEEP_NCCL_ENV") != "1":
+        if backend == "nccl" and args.full and os.environ.get("STE_BENCH_KEEP_NCCL_ENV") != "1":
             # which algorithm / protocol RCCL picks for the exchange: its TUNING log lines, into a file per rank (stdout
             # carries the one JSON line), read back after the untimed all_gather_alone leg.  A caller's own NCCL_DEBUG settings
             # are replaced for this process (STE_BENCH_KEEP_NCCL_ENV=1 keeps them and drops the `rccl` object)
@@ -592,7 +629,7 @@ def _main(stack):
 
     # one batch at a time (not the timed region): forward + smoother of one batch on one unrestricted stream
     serial_ms = serial_kernels = None
-    if pipe is not None and rank == 0:
+    if args.full and pipe is not None and rank == 0:
         saved, gathered = gathered, None
         serial_step(db)
         torch.cuda.synchronize(dev)
@@ -733,12 +770,14 @@ def _main(stack):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dbs[(args.steps - 1) % len(dbs)], B)  # the buffer set of the last timed step
 
     # The exchange on its own (not the timed region): the same all-gather with nothing beside it, so that a step time can be
     # read as max(filter, exchange) -- at the filter's speed the 16 B per track-step every rank sends to every other rank
     # is the larger term on xGMI.
     gather_alone = None
-    if gathered is not None:
+    if args.full and gathered is not None:
         torch.cuda.synchronize(dev)
         dist.barrier()
         t1 = time.perf_counter()
@@ -774,7 +813,7 @@ def _main(stack):
     # The same timed loop with the exchange switched off (not the timed region): one run then reads as filter against
     # exchange -- `value` has the gather in every step, `filter_only` does not, `all_gather_alone` is the gather by itself.
     filter_only = None
-    if gathered is not None:
+    if args.full and gathered is not None:
         saved, gathered = gathered, None
         torch.cuda.synchronize(dev)
         dist.barrier()
@@ -954,7 +993,7 @@ def _main(stack):
                     "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s"},
             },
         }
-        if world == 1:
+        if args.full and world == 1:
             # PCIe-inclusive rate of the host-buffer boundary (batch.run_batch: upload inputs, filter + smooth, download
             # the four history tensors).  Reported for DESIGN.md; it is never `value`.
             del dbs[1:]
@@ -967,7 +1006,7 @@ def _main(stack):
                                      "bytes_down": int(sum(res[k].nbytes for k in ("means", "covs", "means_smoothed",
                                                                                      "covs_smoothed")))}
             del res
-        if args.cpu_tracks > 0 and world == 1:  # the CPU baseline is a rank-0, N = 1 leg
+        if args.full and args.cpu_tracks > 0 and world == 1:  # the CPU baseline is a rank-0, N = 1 leg
             v, secs, ref, chb = cpu_baseline(args.cpu_tracks)
             # the CPU sample is the first cpu_tracks tracks of rank 0's shard: cross-check the GPU result on it -- filtered
             # and smoothed, means and covariances (north_star: means 1e-6 relative, covariances 1e-5)
@@ -1014,8 +1053,8 @@ def _main(stack):
                     "value": pool_result[1], "unit": "track-steps/s", "cores": pool_result[0],
                     "sample": f"{pool_result[0]} forked workers x {args.cpu_pool_tracks} tracks x {chb.Nmax} steps "
                               f"({pool_result[2]:.1f} s, slowest worker)"}
-        if world == 1 and args.cpu_tracks > 0:
-            # The other BASELINE configs, reported beside the headline so that the driver's default run measures them too.
+        if args.full and world == 1 and args.cpu_tracks > 0:
+            # The other BASELINE configs, reported beside the headline in a --full run.
             if pipe is not None:
                 pipe.close()  # its streams own hardware queues, and the fleet entry below builds a pipeline of its own
             dbs, db, pipe = [], None, None
@@ -1033,7 +1072,7 @@ def _main(stack):
                 out["extra"]["config3_modern_ships_robust"] = measure_config3(dev)
             except Exception as exc:
                 out["extra"]["config3_modern_ships_robust"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_fleet and args.cpu_tracks > 0:
+        if args.full and world == 1 and not args.no_fleet and args.cpu_tracks > 0:
             dbs, db, pipe = [], None, None
             torch.cuda.empty_cache()
             try:

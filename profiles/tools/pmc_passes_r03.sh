@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${PMC_OUT:-r3_pmc}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 2 --cpu-tracks 0 --no-gp"
+ARGS="--steps 10 --warmup 2 --cpu-tracks 0 --no-gp --full"
 : > $O/exits.txt
 pass() { name=$1; shift; timeout -k 10 300 rocprofv3 "$@" --kernel-trace --output-format csv -d $O/$name -- python3 $R/bench.py $ARGS > $O/$name.log 2>&1; rc=$?; echo "$name exit $rc" >> $O/exits.txt; return $rc; }
 pass stats --stats && pass fetch --pmc FETCH_SIZE && pass write --pmc WRITE_SIZE \
@@ -16,5 +16,5 @@ pass stats --stats && pass fetch --pmc FETCH_SIZE && pass write --pmc WRITE_SIZE
 cat $O/exits.txt
 # the same command without a profiler, and at the driver's flags
 cd $R
-python3 bench.py --steps 100 --warmup 10 --no-gp > $O/bench_k100.json 2> $O/bench_k100.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err
+python3 bench.py --steps 100 --warmup 10 --no-gp --full > $O/bench_k100.json 2> $O/bench_k100.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_form.json 2> $O/bench_driver_form.err

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${PMC_OUT:-r5_pmc}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 2 --cpu-tracks 0 --no-gp --sequence 0"
+ARGS="--steps 10 --warmup 2 --cpu-tracks 0 --no-gp --full --sequence 0"
 : > $O/exits.txt
 pass() { name=$1; shift; timeout -k 10 300 rocprofv3 "$@" --kernel-trace --output-format csv -d $O/$name -- python3 $R/bench.py $ARGS > $O/$name.log 2>&1; rc=$?; echo "$name exit $rc" >> $O/exits.txt; return $rc; }
 pass stats --stats && pass fetch --pmc FETCH_SIZE && pass write --pmc WRITE_SIZE \
@@ -16,11 +16,11 @@ pass stats --stats && pass fetch --pmc FETCH_SIZE && pass write --pmc WRITE_SIZE
 cat $O/exits.txt
 # the same command without a profiler, and at the driver's flags
 cd $R
-python3 bench.py --steps 100 --warmup 10 --no-gp > $O/bench_k100.json 2> $O/bench_k100.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err
+python3 bench.py --steps 100 --warmup 10 --no-gp --full > $O/bench_k100.json 2> $O/bench_k100.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_form.json 2> $O/bench_driver_form.err
 # the driver's form runs its forward passes as scheduled launches (7 + 13 steps) (bench.py --sequence auto): its own kernel stats
 cd /tmp
 # (--sequence-form single: the form the untimed comparison of --sequence auto usually ends on, pinned so that the stats show one form)
 rm -rf $O/stats_driver_form
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_driver_form -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --cpu-tracks 0 --no-gp --no-fleet --sequence-form single > $O/stats_driver_form.log 2>&1; echo "stats_driver_form exit $?" >> $O/exits.txt
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_driver_form -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --cpu-tracks 0 --no-gp --no-fleet --sequence-form single --full > $O/stats_driver_form.log 2>&1; echo "stats_driver_form exit $?" >> $O/exits.txt
 cd $R

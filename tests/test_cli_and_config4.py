@@ -366,7 +366,7 @@ def test_bench_two_rank_control_flow():
     env = dict(os.environ, STE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--tracks", "256", "--cpu-tracks", "0"]
+           "--tracks", "256", "--cpu-tracks", "0", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -412,7 +412,7 @@ def test_bench_one_rank_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "STE_BENCH_BACKEND")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29537", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--tracks", "640", "--steps", "3", "--warmup", "1",
-           "--cpu-tracks", "0"]
+           "--cpu-tracks", "0", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -443,7 +443,7 @@ def test_bench_line_carries_the_contract():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "2", "--tracks", "640",
            "--cpu-tracks", "64", "--cpu-ref-tracks", "2", "--cpu-pool-tracks", "0", "--no-gp", "--fleet-tracks", "1500",
-           "--fleet-chunk", "500"]
+           "--fleet-chunk", "500", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -515,6 +515,66 @@ def test_bench_gpus_flag_launches_its_own_ranks():
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["total_tracks"] == 512 and out["value"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain N = 1 run (no --full): the headline line without the figures that take runs of their own, and
+    --dump-outputs writes the histories of the last timed step for the fixed track sample -- checked against the oracle."""
+    import subprocess
+    import sys
+
+    import bench
+    from conftest import ROOT
+    from track_estimators import batch, synthetic
+
+    from oracle import ukf_oracle as orc
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tracks", "640",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert (out["steps"], out["warmup"], out["dtype"], out["higher_is_better"]) == (3, 1, "f64", True)
+    assert abs(out["value"] - 640 * 500 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["serial"] is None and not {"cpu_baseline", "pcie_inclusive", "extra"} & set(out)
+    idx = bench.dump_sample(640)
+    files = {f[:-len(".npy")]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(files) == ["covs", "covs_smoothed", "means", "means_smoothed", "status"]
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["means"].shape == (len(idx), 501, 4) and files["covs_smoothed"].shape == (len(idx), 501, 4, 4)
+    assert files["status"].shape == (640,) and not files["status"].any()
+    H, Q, R, P0 = synthetic.example_matrices()
+    sb = synthetic.make_batch(640, nobs=126, gap_h=1.0, seed0=0)  # bench.py's batch: seed = global track index
+    hb = batch.pack_uniform(sb, 4, H, Q, R, P0)
+    fires = hb.upd_idx.T[idx] >= 0
+    zidx = np.where(fires, hb.upd_idx.T[idx], 0)
+    ridx = np.cumsum(fires, axis=1) - fires
+    rr = np.broadcast_to(batch.rts_rate_index(hb.Nmax + 1, 125, 126), (len(idx), hb.Nmax))
+    m, P = orc.forward_batch(hb.x0.T[idx], P0, H, Q, R, hb.dt.T[idx], fires, zidx, ridx, sb.z[idx], sb.sog_rate[idx],
+                             sb.cog_rate[idx])
+    sm, sP = orc.backward_batch(m, P, Q, hb.dt.T[idx], rr, sb.sog_rate[idx], sb.cog_rate[idx])
+    par = bench.compare_histories(files, {"means": m, "covs": P, "means_smoothed": sm, "covs_smoothed": sP})
+    for name in ("means", "means_smoothed"):
+        assert par[name]["max_rel_err"] < 1e-6, (name, par[name])
+    for name in ("covs", "covs_smoothed"):
+        assert par[name]["max_rel_err_per_matrix"] < 1e-5, (name, par[name])
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """The --dump-outputs sample: the same tracks in every run, every track of a small batch, and within 64 MB at the
+    default 10 000-track batch (four histories of 501 rows, 4 + 16 + 4 + 16 doubles per row, plus the status words)."""
+    import bench
+
+    a, b = bench.dump_sample(10_000), bench.dump_sample(10_000)
+    assert np.array_equal(a, b) and len(np.unique(a)) == bench.DUMP_TRACKS and np.all(np.diff(a) > 0)
+    assert a[0] >= 0 and a[-1] < 10_000
+    assert np.array_equal(bench.dump_sample(100), np.arange(100))
+    assert bench.DUMP_TRACKS * 501 * 40 * 8 + 10_000 * 8 <= 64 << 20
 
 
 def test_bench_self_launch_command(monkeypatch):
