@@ -43,7 +43,8 @@
 extern "C" {
 #endif
 
-#define STE_VERSION 321 /* 0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
+#define STE_VERSION 330 /* 0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
+                           0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
                            time slices (step_begin / step_end).  0.3.0: rts_work rows of 30 doubles (+ B at the end); sigma
                            weights sum to one */
@@ -333,7 +334,8 @@ int ste_sigma_points_generic_f64(int32_t n, int64_t count, const double* x, cons
  * gaussian_process.py:28-89, a wrapper over scikit-learn's GaussianProcessRegressor).  One batch = B independent tracks;
  * track b has n[b] observations at 1-D inputs x (cumulative time, gaussian_process.py:53-58) with nout outputs
  * (lon, lat: :66) and its own kernel hyper-parameters theta = log(constant, length_scale, noise) of
- * ConstantKernel * RBF + WhiteKernel (examples/example_gaussian_process_batch.py:41).
+ * ConstantKernel * K + WhiteKernel, K = RBF (examples/example_gaussian_process_batch.py:41) or a Matern kernel with
+ * nu = 1/2, 3/2, 5/2 (scikit-learn's Matern), the same K for the whole batch (ste_gp_batch_f64.kernel).
  * Matrices are row-major [B][ld][ld] with ld = 64 * ceil(nmax / 64) + STE_GP_LD_PAD (the pad keeps consecutive rows off
  * the same HBM channel when 64 * ceil(nmax / 64) is a power of two); all buffers are caller-owned device memory.
  * ------------------------------------------------------------------------------------------------------------- */
@@ -341,6 +343,15 @@ int ste_sigma_points_generic_f64(int32_t n, int64_t count, const double* x, cons
 #define STE_GP_INVERSE_AUTO 0 /* column order (one workgroup per matrix) when B >= 128, else row order (nb workgroups per matrix) */
 #define STE_GP_INVERSE_ROWS 1
 #define STE_GP_INVERSE_COLS 2
+/* ste_gp_batch_f64.kernel, with d = |xi - xj| / length_scale:                                     d k / d log(length_scale):
+ *   RBF       exp(-d^2/2)                                                                          d^2 exp(-d^2/2)
+ *   MATERN12  exp(-d)                                                                              d exp(-d)
+ *   MATERN32  (1 + sqrt(3) d) exp(-sqrt(3) d)                                                      3 d^2 exp(-sqrt(3) d)
+ *   MATERN52  (1 + sqrt(5) d + 5 d^2/3) exp(-sqrt(5) d)                                            (5/3) d^2 (1 + sqrt(5) d) exp(-sqrt(5) d) */
+#define STE_GP_KERNEL_RBF 0
+#define STE_GP_KERNEL_MATERN12 1
+#define STE_GP_KERNEL_MATERN32 2
+#define STE_GP_KERNEL_MATERN52 3
 
 typedef struct ste_gp_batch_f64 {
     int32_t B;     /* number of tracks */
@@ -366,11 +377,13 @@ typedef struct ste_gp_batch_f64 {
     double* grad;   /* [B][3] out: d lml / d theta, or NULL to skip the gradient */
     double* tr;     /* [B][3][nt] workspace, nt = nb(nb + 1)/2 with nb = ceil(nmax/64): per-tile partial traces (summed in tile order) */
     int32_t* status; /* [B] out: 0 ok, 1 = K not positive definite */
+    int32_t kernel;  /* 0.3.3: STE_GP_KERNEL_* (0, RBF, in a zero-initialised struct); any other value is refused with STE_EINVAL */
 } ste_gp_batch_f64;
 
 const char* ste_gp_last_error(void);
 
-/* K(X,X) build only (lower 64x64 tiles + identity padding) -- sklearn kernel __call__ (RBF: exp(-pdist^2/2)). */
+/* K(X,X) build only (lower 64x64 tiles + identity padding) -- sklearn kernel __call__.  Despite the name it builds whichever
+ * kernel `kernel` names (RBF: exp(-pdist^2/2)). */
 int ste_gp_rbf_kmatrix_f64(const ste_gp_batch_f64* b, void* stream);
 
 /* In-place blocked Cholesky of the K that ste_gp_rbf_kmatrix_f64 left in the buffer (scipy.linalg.cholesky(K, lower=True) in

@@ -2,16 +2,17 @@
 //
 // The reference's GPRegression (src/track_estimators/gaussian_processes/gaussian_process.py:28-89) hands X = cumulative
 // time (n x 1) and y = (lon, lat) (n x 2) to scikit-learn's GaussianProcessRegressor with the kernel
-// ConstantKernel * RBF + WhiteKernel (examples/example_gaussian_process_batch.py:41).  Every objective evaluation of its
+// ConstantKernel * RBF + WhiteKernel (examples/example_gaussian_process_batch.py:41); here RBF may also be a Matern
+// kernel with nu = 1/2, 3/2 or 5/2 (STE_GP_KERNEL_*, one kind per batch).  Every objective evaluation of its
 // L-BFGS-B fit is: build K(X,X), Cholesky, alpha = K^-1 y, log-marginal likelihood, K^-1, gradient (GPML Alg. 2.1,
 // eq. 5.9).  This file evaluates that objective for a batch of tracks with hand-written kernels:
 //
-//   gp_kbuild      K = c exp(-(xi-xj)^2 / 2 l^2) + (s + jitter) I, lower 64x64 tiles, identity padding
+//   gp_kbuild      K = c k((xi-xj) / l) + (s + jitter) I, lower 64x64 tiles, identity padding (k: RBF or Matern, below)
 //   gp_potrf_cols  blocked left-looking Cholesky in column order, one workgroup per matrix, four tiles per pass
 //   gp_trtri_cols  U = L^-T (upper, row-major) in column order (large batches); gp_trtri_rows: one workgroup per
 //                  (matrix, block row) for small batches
 //   gp_kinv_trace  K^-1 = U U^T tile by tile, reduced on the fly against dK/dtheta (never materialised), and
-//                  alpha^T (dK/dtheta) alpha with the same Krbf values -> gradient
+//                  alpha^T (dK/dtheta) alpha with the same kernel values -> gradient
 //   alpha = U (U^T y): in the column-ordered kernels the right-hand sides ride along (w = L^-1 y by forward substitution
 //                  in gp_potrf_cols, alpha = U w tile by tile in gp_trtri_cols); gp_w / gp_alpha for the row-ordered inverse
 //   gp_alpha / gp_finish   per-block shares of y.alpha, log det, alpha.alpha -> log-marginal likelihood, gradient assembly
@@ -53,7 +54,7 @@ struct GpParams {
     double* alpha;  // [B][nout][nmax]
     double* lml;    // [B]
     double* grad;   // [B][3] or null
-    double* tr;     // [B][3][ntiles_max] per-tile partial sums of tr(K^-1 Krbf), tr(K^-1 (Krbf o D2)), tr(K^-1)
+    double* tr;     // [B][3][ntiles_max] per-tile partial sums of tr(K^-1 Kc), tr(K^-1 dK/dlog l), tr(K^-1)
     int32_t* status;
     int store_kinv;
     int inverse_cols;  // U = L^-T by gp_trtri_cols (else gp_trtri_rows)
@@ -61,7 +62,53 @@ struct GpParams {
     // without a list, slot s is matrix s and nslots == B.
     int nslots;
     const int32_t* active;
+    int kernel;  // STE_GP_KERNEL_*: which functor below the launches are instantiated with (one kind per batch)
 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// Kernel functions of ConstantKernel * K + WhiteKernel, d = (xi - xj) / l (signed; the 1-D inputs need no square root):
+//   k(d) = value(env(c, d), d),   dk/dlog l = env(c, d) * dlogl(d),   env = c times the exponential
+// The exponential is shared by the value and the derivative, so gp_kinv_trace evaluates it once per pair, and the RBF
+// instantiation is exactly the arithmetic of the RBF-only kernels (kr = c exp(-d^2/2), dK/dlog l = kr * d^2, d*d not fabs).
+// Each functor is scikit-learn's Matern / RBF __call__(eval_gradient=True) times the constant.  Every site that forms an
+// element of K (gp_kbuild, gp_potrf_cols<F>, gp_kstar) calls value(env(c, d), d), so the in-place build and the
+// stand-alone build are one expression.
+// ---------------------------------------------------------------------------------------------------------------
+struct KernRbf {  // c exp(-d^2/2);  dk/dlog l = c d^2 exp(-d^2/2)
+    static constexpr int kind = STE_GP_KERNEL_RBF;
+    __device__ static __forceinline__ double env(double c, double d) { return c * exp(-0.5 * (d * d)); }
+    __device__ static __forceinline__ double value(double e, double) { return e; }
+    __device__ static __forceinline__ double dlogl(double d) { return d * d; }
+};
+struct KernMatern12 {  // c exp(-|d|);  dk/dlog l = c |d| exp(-|d|)
+    static constexpr int kind = STE_GP_KERNEL_MATERN12;
+    __device__ static __forceinline__ double env(double c, double d) { return c * exp(-fabs(d)); }
+    __device__ static __forceinline__ double value(double e, double) { return e; }
+    __device__ static __forceinline__ double dlogl(double d) { return fabs(d); }
+};
+// (the polynomials are written as explicit fma: nothing is left for -ffp-contract to fuse one way in one kernel and another
+//  way in the next, so every call site gets the same bits)
+constexpr double kSqrt3 = 1.7320508075688772, kSqrt5 = 2.23606797749979;
+struct KernMatern32 {  // c (1 + sqrt3 |d|) exp(-sqrt3 |d|);  dk/dlog l = c 3 d^2 exp(-sqrt3 |d|)
+    static constexpr int kind = STE_GP_KERNEL_MATERN32;
+    __device__ static __forceinline__ double env(double c, double d) { return c * exp(-kSqrt3 * fabs(d)); }
+    __device__ static __forceinline__ double value(double e, double d) { return e * fma(kSqrt3, fabs(d), 1.0); }
+    __device__ static __forceinline__ double dlogl(double d) { return 3.0 * (d * d); }
+};
+struct KernMatern52 {  // c (1 + sqrt5 |d| + 5 d^2/3) exp(-sqrt5 |d|);  dk/dlog l = c (5/3) d^2 (1 + sqrt5 |d|) exp(-sqrt5 |d|)
+    static constexpr int kind = STE_GP_KERNEL_MATERN52;
+    __device__ static __forceinline__ double env(double c, double d) { return c * exp(-kSqrt5 * fabs(d)); }
+    __device__ static __forceinline__ double value(double e, double d) {
+        const double a = kSqrt5 * fabs(d);
+        return e * fma(fma(a, 1.0 / 3.0, 1.0), a, 1.0);  // 1 + a (1 + a/3)
+    }
+    __device__ static __forceinline__ double dlogl(double d) { return (5.0 / 3.0) * (d * d) * fma(kSqrt5, fabs(d), 1.0); }
+};
+// one element of c k(d): what gp_kbuild stores, gp_potrf_cols<F> evaluates in place and gp_kstar uses
+template <typename F>
+__device__ __forceinline__ double kernel_value(double c, double d) {
+    return F::value(F::env(c, d), d);
+}
 
 __device__ __forceinline__ int matrix_of(const GpParams& p, int slot) { return p.active ? p.active[slot] : slot; }
 
@@ -127,6 +174,7 @@ __device__ __forceinline__ void for_each_acc(v4d (&acc)[2][2], int wave, int lan
 // ---------------------------------------------------------------------------------------------------------------
 // K build: lower tiles of K (including the diagonal tiles in full), identity on the padding.
 // ---------------------------------------------------------------------------------------------------------------
+template <typename F>
 __global__ __launch_bounds__(256) void gp_kbuild(const GpParams p) {
     const int b = matrix_of(p, blockIdx.y);
     const int n = p.n[b];
@@ -146,7 +194,7 @@ __global__ __launch_bounds__(256) void gp_kbuild(const GpParams p) {
         double v;
         if (r < n && cidx < n) {
             const double d = (x[r] - x[cidx]) * inv_l;
-            v = c * exp(-0.5 * d * d);
+            v = kernel_value<F>(c, d);
             if (r == cidx) v += s + p.jitter;
         } else {
             v = (r == cidx) ? 1.0 : 0.0;
@@ -754,10 +802,21 @@ __device__ __noinline__ void chol_trinv_wave(double* S, double* X, double* work,
     for (int c = 0; c < T; ++c) X[c * LD + lane] = x[c];  // x[c] of lane `lane` = X[row c][column lane]
 }
 
-// kBuild: K is not read but evaluated where gp_kbuild would have put it (same expression, same bits), so that an
-// objective evaluation neither writes nor re-reads the 16 MB of K; the stand-alone ste_gp_potrf_f64 factors what is there.
-template <bool kBuild>
+// the chol_trinv_wave copy of each gp_potrf_cols instantiation: 0 for the stand-alone factorisation, 1 + kind for the others
+template <typename F>
+constexpr int chol_copy() {
+    if constexpr (std::is_void<F>::value)
+        return 0;
+    else
+        return 1 + F::kind;
+}
+
+// F (a kernel functor): K is not read but evaluated where gp_kbuild<F> would have put it (same expression, same bits), so
+// that an objective evaluation neither writes nor re-reads the 16 MB of K; F = void, the stand-alone ste_gp_potrf_f64,
+// factors what is there.
+template <typename F>
 __global__ __launch_bounds__(256) void gp_potrf_cols(const GpParams p) {
+    constexpr bool kBuild = !std::is_void<F>::value;
     __shared__ double S[T * LD];
     __shared__ double X[T * LD];
     __shared__ __attribute__((aligned(16))) double stage[2 * T * LDB];
@@ -799,7 +858,7 @@ __global__ __launch_bounds__(256) void gp_potrf_cols(const GpParams p) {
             // acc[m][n][e] is element (jj = 16 m + 4 e + g, row r of strip n) of the transposed tiles; it starts as K[i][j]^T
             // (loads in flight behind the first panel blocks) and the negated panel products are accumulated onto it
             v4d acc[4][4];
-            if (kBuild) {
+            if constexpr (kBuild) {
                 // (theta and x are re-read per pass: nothing of this is live across the panel loop)
                 const double* xb = p.x + (size_t)b * p.nmax;
                 const double kc = exp(p.theta[b * 3 + 0]), kinv_l = exp(-p.theta[b * 3 + 1]), ks = exp(p.theta[b * 3 + 2]);
@@ -824,7 +883,7 @@ __global__ __launch_bounds__(256) void gp_potrf_cols(const GpParams p) {
                                 double v;
                                 if (row < nrows && col < nrows) {
                                     const double d = (xr - xc[m][e]) * kinv_l;
-                                    v = kc * exp(-0.5 * d * d);
+                                    v = kernel_value<F>(kc, d);
                                     if (row == col) v += ks + p.jitter;
                                 } else {
                                     v = (row == col) ? 1.0 : 0.0;
@@ -856,7 +915,7 @@ __global__ __launch_bounds__(256) void gp_potrf_cols(const GpParams p) {
                     for (int e = 0; e < 4; ++e) S[(16 * wave + r) * LD + 16 * m + 4 * e + g] = acc[m][0][e];
                 __syncthreads();
                 if (wave == 0) {
-                    chol_trinv_wave<kBuild ? 1 : 0>(S, X, stage, lane, &ok);
+                    chol_trinv_wave<chol_copy<F>()>(S, X, stage, lane, &ok);
                     for (int o = 0; o < nout; ++o) {
                         const int row = j * T + lane;
                         const double sj = row < nrows ? ld_l2(rhs + (size_t)o * p.nmax + row) : 0.0;
@@ -967,7 +1026,8 @@ __global__ __launch_bounds__(256) void gp_trtri_cols(const GpParams p) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // K^-1 tile (ta >= tb) = sum_{k >= ta} U[ta][k] U[tb][k]^T, reduced against the kernel derivatives:
-//   tr[0] += sum Kinv * Krbf,  tr[1] += sum Kinv * Krbf * d^2,  tr[2] += trace(Kinv)      (off-diagonal tiles count twice)
+//   tr[0] += sum Kinv * Kc,  tr[1] += sum Kinv * dKc/dlog l,  tr[2] += trace(Kinv)      (off-diagonal tiles count twice)
+// with Kc = c k(d), the kernel without the noise (RBF: dKc/dlog l = Kc d^2)
 // and optionally stored (both triangles) into `kinv_out` for the predictive variance.
 // One workgroup per strip = block row ta x four block columns tb (one 64 x 64 tile per wave): all four contractions run
 // over the same k-range [ta, nb) and share the rows of U[ta], which is exactly the shape of panel_gemm_t -- shared rows
@@ -981,9 +1041,10 @@ __host__ __device__ inline int kinv_strips(int nb) {  // strips of a matrix with
 
 __device__ __forceinline__ double* gp_wbuf(const GpParams& p, int b) { return p.Dinv + (size_t)b * p.nb_max * T * T; }
 __device__ __forceinline__ double* gp_share(const GpParams& p, int b) { return gp_wbuf(p, b) + (size_t)p.nout * p.ld; }
-// per-strip partial sums of alpha^T Krbf alpha and alpha^T (Krbf o d^2) alpha, behind the per-block shares
+// per-strip partial sums of alpha^T Kc alpha and alpha^T (dKc/dlog l) alpha, behind the per-block shares
 __device__ __forceinline__ double* gp_quad_share(const GpParams& p, int b) { return gp_share(p, b) + 5 * (size_t)p.nb_max; }
 
+template <typename F>
 __global__ __launch_bounds__(256, 2) void gp_kinv_trace(const GpParams p, double* kinv_out) {
     __shared__ double red[5][4];
     __shared__ __attribute__((aligned(16))) double stage[2 * T * LDB];
@@ -1030,7 +1091,7 @@ __global__ __launch_bounds__(256, 2) void gp_kinv_trace(const GpParams p, double
     const double* x = p.x + (size_t)b * p.nmax;
     double t0 = 0.0, t1 = 0.0, t2 = 0.0, q0 = 0.0, q1 = 0.0;
     {
-        // The quadratic forms alpha^T (dK/dtheta) alpha ride along: every pair (gr, gc) meets its Krbf and d^2 here anyway
+        // The quadratic forms alpha^T (dK/dtheta) alpha ride along: every pair (gr, gc) meets its Kc and dKc/dlog l here anyway
         // (alpha is complete before this kernel is launched; summed over the outputs, like the traces).
         const double* al = p.alpha + (size_t)b * p.nout * p.nmax;
         const bool quad = p.grad != nullptr;
@@ -1059,17 +1120,16 @@ __global__ __launch_bounds__(256, 2) void gp_kinv_trace(const GpParams p, double
                     const double v = -acc[m][nn][e];
                     if (gr < n && gc < n) {
                         const double d = (xr - x[gc]) * inv_l;
-                        const double d2 = d * d;
-                        const double kr = c * exp(-0.5 * d2);
+                        const double ke = F::env(c, d), dl = F::dlogl(d);  // dK/dlog l = ke * dl
+                        const double kr = F::value(ke, d);
                         t0 += wgt * v * kr;
-                        t1 += wgt * v * kr * d2;
+                        t1 += wgt * v * ke * dl;
                         if (gr == gc) t2 += v;
                         double aa = ar[0] * ac[0][nn];
 #pragma unroll
                         for (int o = 1; o < kMaxOut; ++o) aa = fma(ar[o], ac[o][nn], aa);
-                        const double qk = wgt * kr * aa;
-                        q0 += qk;
-                        q1 += qk * d2;
+                        q0 += wgt * kr * aa;
+                        q1 += wgt * ke * aa * dl;  // (RBF: ke is kr, and this is q0's term times d^2)
                     }
                     if (kinv_out && gr < nrows && gc < nrows) {
                         kinv_out[(size_t)b * ld * ld + (size_t)gr * ld + gc] = v;
@@ -1259,8 +1319,8 @@ __global__ __launch_bounds__(64) void gp_finish(const GpParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Prediction: Kstar[m][i] = c exp(-(xs_m - x_i)^2 / 2 l^2) (padded to tiles with zeros), mean = Kstar alpha,
-// var_m = c + s - kstar_m^T K^-1 kstar_m as tile products W = Kstar K^-1 reduced against Kstar on the fly.
+// Prediction: Kstar[m][i] = c k((xs_m - x_i) / l) (padded to tiles with zeros), mean = Kstar alpha,
+// var_m = c + s - kstar_m^T K^-1 kstar_m (c k(0) + s for every kind) as tile products W = Kstar K^-1 reduced against Kstar on the fly.
 // ---------------------------------------------------------------------------------------------------------------
 struct GpPredict {
     int B, mmax, mb_max, ldk;  // ldk = leading dim of Kstar rows (= ld of the n x n buffers)
@@ -1272,6 +1332,7 @@ struct GpPredict {
     double* var;   // [B][mmax]
 };
 
+template <typename F>
 __global__ __launch_bounds__(256) void gp_kstar(const GpParams p, const GpPredict q) {
     const int b = blockIdx.y, mt = blockIdx.x;
     const int n = p.n[b], m = q.m[b];
@@ -1287,7 +1348,7 @@ __global__ __launch_bounds__(256) void gp_kstar(const GpParams p, const GpPredic
             double v = 0.0;
             if (gm < m && i < n) {
                 const double d = (xs[gm] - x[i]) * inv_l;
-                v = c * exp(-0.5 * d * d);
+                v = kernel_value<F>(c, d);
             }
             Ks[(size_t)gm * q.ldk + i] = v;
         }
@@ -1402,7 +1463,20 @@ int gp_params(const ste_gp_batch_f64* b, stegp::GpParams* p) {
     p->inverse_cols = b->inverse_order == STE_GP_INVERSE_AUTO ? (b->B >= 128) : (b->inverse_order == STE_GP_INVERSE_COLS);
     p->nslots = b->B;
     p->active = nullptr;
+    if (b->kernel < STE_GP_KERNEL_RBF || b->kernel > STE_GP_KERNEL_MATERN52)
+        return gp_fail("kernel must be STE_GP_KERNEL_RBF, _MATERN12, _MATERN32 or _MATERN52");
+    p->kernel = b->kernel;
     return STE_OK;
+}
+// fn(F{}) with the functor of the batch's kernel kind: each launch is one instantiation, no per-element branch on the kind
+template <typename Fn>
+void with_kernel(int kind, Fn&& fn) {
+    switch (kind) {
+        case STE_GP_KERNEL_RBF: fn(stegp::KernRbf{}); break;
+        case STE_GP_KERNEL_MATERN12: fn(stegp::KernMatern12{}); break;
+        case STE_GP_KERNEL_MATERN32: fn(stegp::KernMatern32{}); break;
+        default: fn(stegp::KernMatern52{}); break;  // (gp_params has refused any other value)
+    }
 }
 }  // namespace
 
@@ -1415,7 +1489,9 @@ int ste_gp_rbf_kmatrix_f64(const ste_gp_batch_f64* b, void* stream) {
     int rc = gp_params(b, &p);
     if (rc) return rc;
     const int tiles = p.nb_max * (p.nb_max + 1) / 2;
-    hipLaunchKernelGGL(stegp::gp_kbuild, dim3(tiles, p.B), dim3(256), 0, (hipStream_t)stream, p);
+    with_kernel(p.kernel, [&](auto f) {
+        hipLaunchKernelGGL(stegp::gp_kbuild<decltype(f)>, dim3(tiles, p.B), dim3(256), 0, (hipStream_t)stream, p);
+    });
     return gp_hip(hipGetLastError(), "gp_kbuild launch");
 }
 
@@ -1423,7 +1499,7 @@ int ste_gp_potrf_f64(const ste_gp_batch_f64* b, void* stream) {
     stegp::GpParams p;
     int rc = gp_params(b, &p);
     if (rc) return rc;
-    hipLaunchKernelGGL(stegp::gp_potrf_cols<false>, dim3(p.B), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(stegp::gp_potrf_cols<void>, dim3(p.B), dim3(256), 0, (hipStream_t)stream, p);
     return gp_hip(hipGetLastError(), "gp_potrf launch");
 }
 
@@ -1440,7 +1516,7 @@ static int gp_lml_launch(const ste_gp_batch_f64* b, int32_t count, const int32_t
     const unsigned ns = (unsigned)p.nslots;
     hipStream_t s = (hipStream_t)stream;
     // (no gp_kbuild: the factorisation evaluates the kernel function where it would read K)
-    hipLaunchKernelGGL(stegp::gp_potrf_cols<true>, dim3(ns), dim3(256), 0, s, p);
+    with_kernel(p.kernel, [&](auto f) { hipLaunchKernelGGL(stegp::gp_potrf_cols<decltype(f)>, dim3(ns), dim3(256), 0, s, p); });
     // which of the two inverse kernels runs is a property of the batch (gp_params), never of this launch: a subset launch
     // must leave the bits a full launch leaves (include/ste.h: "per-matrix results do not depend on which other matrices are
     // listed"), and the two kernels sum in different orders
@@ -1454,7 +1530,9 @@ static int gp_lml_launch(const ste_gp_batch_f64* b, int32_t count, const int32_t
     hipLaunchKernelGGL(stegp::gp_alpha, dim3(p.nb_max, ns), dim3(256), 0, s, p);
     if (p.grad || b->Kinv) {
         const unsigned groups = (ns + 7) / 8, strips = (unsigned)stegp::kinv_strips(p.nb_max);
-        hipLaunchKernelGGL(stegp::gp_kinv_trace, dim3(groups * 8u * strips), dim3(256), 0, s, p, b->Kinv);
+        with_kernel(p.kernel, [&](auto f) {
+            hipLaunchKernelGGL(stegp::gp_kinv_trace<decltype(f)>, dim3(groups * 8u * strips), dim3(256), 0, s, p, b->Kinv);
+        });
     }
     hipLaunchKernelGGL(stegp::gp_finish, dim3((ns + 63) / 64), dim3(64), 0, s, p);
     return gp_hip(hipGetLastError(), "gp_lml launch");
@@ -1486,7 +1564,7 @@ int ste_gp_predict_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m
     q.mean = mean;
     q.var = var;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(stegp::gp_kstar, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
+    with_kernel(p.kernel, [&](auto f) { hipLaunchKernelGGL(stegp::gp_kstar<decltype(f)>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q); });
     hipLaunchKernelGGL(stegp::gp_predict, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
     return gp_hip(hipGetLastError(), "gp_predict launch");
 }

@@ -139,6 +139,7 @@ class SteGpBatchF64(C.Structure):
         ("grad", _dp),
         ("tr", _dp),
         ("status", _dp),
+        ("kernel", C.c_int32),  # 0.3.3: STE_GP_KERNEL_*
     ]
 
 
@@ -164,6 +165,7 @@ class StePrepBatchF64(C.Structure):
 
 
 STE_GP_INVERSE_AUTO, STE_GP_INVERSE_ROWS, STE_GP_INVERSE_COLS = 0, 1, 2
+STE_GP_KERNEL_RBF, STE_GP_KERNEL_MATERN12, STE_GP_KERNEL_MATERN32, STE_GP_KERNEL_MATERN52 = 0, 1, 2, 3
 STE_PREP_SPHERE = 0
 STE_PREP_WGS84 = 1
 STE_PREP_STATUS_NOCONV = 0x1

@@ -15,10 +15,13 @@ JITTER = 1e-10  # GaussianProcessRegressor(alpha=1e-10), the value the reference
 
 
 class GpDeviceBatch:
-    """B tracks (1-D inputs x_b, outputs y_b (n_b, nout)) resident on the GPU; evaluates the GP objective for all."""
+    """B tracks (1-D inputs x_b, outputs y_b (n_b, nout)) resident on the GPU; evaluates the GP objective for all.
+
+    ``kernel``: the kernel function of ConstantKernel * K + WhiteKernel for every track of the batch,
+    ``binding.STE_GP_KERNEL_RBF`` (default) or ``STE_GP_KERNEL_MATERN12 / 32 / 52`` (Matern, nu = 1/2, 3/2, 5/2)."""
 
     def __init__(self, xs: Sequence[np.ndarray], ys: Sequence[np.ndarray], device="cuda:0", jitter: float = JITTER,
-                 inverse_order: int = binding.STE_GP_INVERSE_AUTO):
+                 inverse_order: int = binding.STE_GP_INVERSE_AUTO, kernel: int = binding.STE_GP_KERNEL_RBF):
         import torch
 
         self.torch = torch
@@ -64,6 +67,7 @@ class GpDeviceBatch:
         s.alpha, s.lml, s.grad, s.tr = (self.t_alpha.data_ptr(), self.t_lml.data_ptr(), self.t_grad.data_ptr(),
                                         self.t_tr.data_ptr())
         s.status = self.t_status.data_ptr()
+        self.kernel = s.kernel = int(kernel)  # (the library refuses an unknown kind at the first call)
         # The kernel that forms L^-T is named explicitly once resolved, so that a replicated copy of this batch (whose B is
         # a multiple of this one's and may cross the library's size threshold) sums in the same order: a track's first
         # optimiser start and its restarts then see bit-identical objectives for identical theta.
@@ -84,7 +88,7 @@ class GpDeviceBatch:
         """A batch holding ``copies`` consecutive copies of this one's tracks (entry c * B + b is track b): the optimiser
         restarts of a fit run as extra batch entries that share their track's data."""
         return GpDeviceBatch(self._xs * copies, self._ys * copies, device=self.device, jitter=self._jitter,
-                             inverse_order=self.inverse_order)
+                             inverse_order=self.inverse_order, kernel=self.kernel)
 
     def _set_theta(self, thetas):
         th = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64).reshape(self.B, 3))

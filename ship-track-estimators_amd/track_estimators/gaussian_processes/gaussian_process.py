@@ -9,8 +9,9 @@ The reference delegates every number to scikit-learn's ``GaussianProcessRegresso
 plus ``n_restarts_optimizer`` log-uniform restarts drawn from the same random stream, best optimum kept) but evaluates
 the objective -- K build, Cholesky, alpha, log-marginal likelihood, K^-1, gradient -- and the predictions with the HIP
 kernels of csrc/ste_gp.hip.  scikit-learn kernel objects are accepted as the description of the kernel (they carry the
-initial hyper-parameters and bounds); only ``ConstantKernel * RBF + WhiteKernel`` (what the reference's examples use,
-examples/example_gaussian_process_batch.py:41) has a device implementation.  No CPU fallback.
+initial hyper-parameters and bounds); ``ConstantKernel * K + WhiteKernel`` has a device implementation, with K an
+isotropic ``RBF`` (what the reference's examples use, examples/example_gaussian_process_batch.py:41) or ``Matern`` with
+nu = 0.5, 1.5, 2.5 (or inf, which is RBF).  Any other kernel raises ``NotImplementedError``: there is no CPU fallback.
 
 Additive extra: ``fit_batch`` / ``predict_batch`` fit many tracks at once, advancing all their optimisers in lock-step so
 that each objective evaluation is one batched launch (the reference loops over ships in Python,
@@ -25,23 +26,48 @@ import numpy as np
 import scipy.optimize
 
 from ..ship_track import ShipTrack
+from .._hip import binding
 from .device import GpDeviceBatch
+
+_SUPPORTED = ("ConstantKernel * K + WhiteKernel with K = RBF or Matern(nu = 0.5, 1.5, 2.5 or inf), isotropic length scale, "
+              "all three hyper-parameters free")
+_MATERN_KINDS = {0.5: binding.STE_GP_KERNEL_MATERN12, 1.5: binding.STE_GP_KERNEL_MATERN32,
+                 2.5: binding.STE_GP_KERNEL_MATERN52, np.inf: binding.STE_GP_KERNEL_RBF}  # nu = inf: scikit-learn's RBF
+
+
+def _kernel_kind(kernel):
+    """binding.STE_GP_KERNEL_* of ConstantKernel * K + WhiteKernel given as scikit-learn objects; NotImplementedError for
+    any kernel the device path does not implement."""
+    from sklearn.gaussian_process import kernels as sk
+
+    def refuse(why):
+        raise NotImplementedError(f"the HIP GP path implements {_SUPPORTED} only ({why}; got {kernel!r}); no CPU fallback")
+
+    if not (isinstance(kernel, sk.Sum) and isinstance(kernel.k1, sk.Product) and isinstance(kernel.k1.k1, sk.ConstantKernel)
+            and isinstance(kernel.k2, sk.WhiteKernel)):
+        refuse("structure")
+    k = kernel.k1.k2
+    if isinstance(k, sk.Matern):  # (a subclass of RBF)
+        kind = _MATERN_KINDS.get(float(k.nu))
+        if kind is None:
+            refuse(f"nu = {k.nu}")
+    elif type(k) is sk.RBF:
+        kind = binding.STE_GP_KERNEL_RBF
+    else:
+        refuse(f"{type(k).__name__}")
+    if np.ndim(k.length_scale) != 0:
+        refuse("anisotropic length scale")
+    if np.shape(kernel.theta) != (3,):
+        refuse("fixed hyper-parameters")
+    return kind
 
 
 def _kernel_spec(kernel):
-    """theta0 (3,), bounds (3,2) in log space for ConstantKernel * RBF + WhiteKernel given as scikit-learn objects."""
-    from sklearn.gaussian_process import kernels as sk
-
-    ok = (isinstance(kernel, sk.Sum) and isinstance(kernel.k1, sk.Product) and isinstance(kernel.k1.k1, sk.ConstantKernel)
-          and isinstance(kernel.k1.k2, sk.RBF) and isinstance(kernel.k2, sk.WhiteKernel)
-          and np.ndim(kernel.k1.k2.length_scale) == 0)
-    if not ok:
-        raise NotImplementedError("the HIP GP path implements ConstantKernel * RBF(isotropic) + WhiteKernel only "
-                                  f"(got {kernel!r}); no CPU fallback")
+    """theta0 (3,), bounds (3,2) in log space for ConstantKernel * K + WhiteKernel given as scikit-learn objects (K: see
+    ``_kernel_kind``, which names the kernel function)."""
+    _kernel_kind(kernel)
     theta = np.asarray(kernel.theta, dtype=np.float64)
     bounds = np.asarray(kernel.bounds, dtype=np.float64)
-    if theta.shape != (3,):
-        raise NotImplementedError("fixed hyper-parameters are not supported on the HIP GP path")
     return theta, bounds
 
 
@@ -210,7 +236,7 @@ class DeviceGaussianProcessRegressor:
         theta0, bounds = _kernel_spec(self.kernel)
         self._rng = _check_random_state(self.random_state)
         self.X_train_, self.y_train_ = X.copy(), y.copy()
-        self._batch = GpDeviceBatch([X[:, 0]], [y], jitter=float(self.alpha))
+        self._batch = GpDeviceBatch([X[:, 0]], [y], jitter=float(self.alpha), kernel=_kernel_kind(self.kernel))
         thetas, lml = fit_thetas(self._batch, theta0, bounds, self.n_restarts_optimizer, self._rng, self.optimizer)
         self.kernel_ = _clone_with_theta(self.kernel, thetas[0])
         self.log_marginal_likelihood_value_ = float(self._batch.objective(thetas, eval_gradient=False)[0][0])
@@ -242,7 +268,8 @@ class GPRegression:
     Parameters
     ----------
     kernel
-        scikit-learn kernel object, e.g. ``1.0 * RBF() + WhiteKernel(noise_level=0.5)``.
+        scikit-learn kernel object, e.g. ``1.0 * RBF() + WhiteKernel(noise_level=0.5)`` or
+        ``1.0 * Matern(nu=1.5) + WhiteKernel()``.
     gpr
         Regressor class; defaults to the GPU implementation (the reference's default is scikit-learn's class).
     """
@@ -278,16 +305,17 @@ class GPRegression:
         gpr_kwargs = dict(gpr_kwargs or {"n_restarts_optimizer": 50})
         data = [self._training_data(st) for st in ship_tracks]
         theta0, bounds = _kernel_spec(self._kernel)
+        kind = _kernel_kind(self._kernel)
         seed = gpr_kwargs.get("random_state")
         # an integer seed means what it means for a loop of single fits (the reference's batch example builds one
         # regressor per ship): every track gets its own stream from that seed
         rng = [np.random.RandomState(seed) for _ in data] if isinstance(seed, (int, np.integer)) else _check_random_state(seed)
         self._batch = GpDeviceBatch([X[:, 0] for X, _ in data], [y for _, y in data],
-                                    jitter=float(gpr_kwargs.get("alpha", 1e-10)))
+                                    jitter=float(gpr_kwargs.get("alpha", 1e-10)), kernel=kind)
         self._thetas, self._lml = fit_thetas(self._batch, theta0, bounds, int(gpr_kwargs.get("n_restarts_optimizer", 0)),
                                              rng, gpr_kwargs.get("optimizer", "fmin_l_bfgs_b"))
         return self._thetas, self._lml
 
     def predict_batch(self, times: Sequence[np.ndarray]):
-        """[(mean (m_b, 2), std (m_b, 2)) for every track] after ``fit_batch``."""
+        """[(mean (m_b, 2), std (m_b, 2)) for every track] after ``fit_batch`` (with its kernel function)."""
         return self._batch.predict(self._thetas, [np.asarray(t).reshape(-1) for t in times])
