@@ -43,7 +43,8 @@
 extern "C" {
 #endif
 
-#define STE_VERSION 330 /* 0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
+#define STE_VERSION 340 /* 0.3.4: posterior covariance on the GP path (ste_gp_predict_cov_f64).
+                           0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
                            time slices (step_begin / step_end).  0.3.0: rts_work rows of 30 doubles (+ B at the end); sigma
@@ -370,7 +371,7 @@ typedef struct ste_gp_batch_f64 {
                        function inside the factorisation and leaves L here without K ever being stored */
     double* U;      /* [B][ld][ld]  workspace: L^-T (upper triangle) */
     double* Dinv;   /* [B][(ld-16)/64][64][64] workspace: inverses of the diagonal blocks of L */
-    double* Kinv;   /* [B][ld][ld] K^-1 (both triangles) when non-NULL; needed by ste_gp_predict_f64 */
+    double* Kinv;   /* [B][ld][ld] K^-1 (both triangles) when non-NULL; needed by ste_gp_predict_f64 and ste_gp_predict_cov_f64 */
     double* alpha;  /* [B][nout][nmax] out: K^-1 y (after ste_gp_potrf_f64 alone: the forward substitution L^-1 y, which rides along
                        with the factorisation) */
     double* lml;    /* [B] out: log marginal likelihood summed over outputs */
@@ -410,6 +411,18 @@ int ste_gp_lml_subset_f64(const ste_gp_batch_f64* b, int32_t count, const int32_
  */
 int ste_gp_predict_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
                        double* mean, double* var, void* stream);
+
+/*
+ * Posterior mean [B][nout][mmax] and covariance [B][mmax][mmax] at m[b] new inputs xs [B][mmax]
+ * (GaussianProcessRegressor.predict(return_cov=True)):
+ *   cov = c k(xs_i - xs_j) + s [i == j] - Kstar K^-1 Kstar^T      (the WhiteKernel adds s on the diagonal only)
+ * Needs alpha and Kinv from a preceding ste_gp_lml_f64 on the same batch.  Kstar, W: workspaces [B][64*ceil(mmax/64)][ld].
+ * The mean is ste_gp_predict_f64's, bit for bit; mean rows >= m[b] are not written.  Every element of a track's
+ * [mmax][mmax] block of cov is written: both triangles (the upper one mirrors the lower one bit for bit), 0 in rows and
+ * columns >= m[b].  Per-track results do not depend on the other tracks of the batch.
+ */
+int ste_gp_predict_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
+                           double* W, double* mean, double* cov, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Observation preparation: speed / course over ground and their rates for a batch of tracks, the

@@ -17,6 +17,7 @@
 //                  in gp_potrf_cols, alpha = U w tile by tile in gp_trtri_cols); gp_w / gp_alpha for the row-ordered inverse
 //   gp_alpha / gp_finish   per-block shares of y.alpha, log det, alpha.alpha -> log-marginal likelihood, gradient assembly
 //   gp_kstar / gp_predict   posterior mean and variance at new times (variance as a tile GEMM against K^-1)
+//   gp_pcov_w / gp_pcov     posterior covariance: W = Kstar K^-1, then Kss + s I - W Kstar^T on the lower tiles, mirrored
 //
 // All dense work is 64x64-tile "NT" products C += A_rows * B_rows^T with both operands row-major and contiguous along
 // the contraction index, issued as v_mfma_f64_16x16x4_f64: lane l feeds A[row l&15][k = l>>4] and B[col l&15][k = l>>4]
@@ -1330,7 +1331,28 @@ struct GpPredict {
     const double* Kinv;
     double* mean;  // [B][nout][mmax]
     double* var;   // [B][mmax]
+    double* W;     // [B][mb_max*64][ldk]  Kstar K^-1 (ste_gp_predict_cov_f64 only)
+    double* cov;   // [B][mmax][mmax]      (ste_gp_predict_cov_f64 only)
 };
+
+// mean = Kstar alpha for the 64 query rows of tile mt: wave per row, lanes over i (one code path for both predict calls, so
+// that their means agree bit for bit)
+__device__ __forceinline__ void predict_mean(const GpParams& p, const GpPredict& q, int b, int mt, int wave, int lane) {
+    const int n = p.n[b], m = q.m[b];
+    const double* Ks = q.Kstar + (size_t)b * q.mb_max * T * q.ldk;
+    for (int o = 0; o < p.nout; ++o) {
+        const double* al = p.alpha + ((size_t)b * p.nout + o) * p.nmax;
+        for (int r = wave; r < T; r += 4) {
+            const int gm = mt * T + r;
+            if (gm >= m) continue;
+            double acc = 0.0;
+            for (int i = lane; i < n; i += 64) acc = fma(Ks[(size_t)gm * q.ldk + i], al[i], acc);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+            if (lane == 0) q.mean[((size_t)b * p.nout + o) * q.mmax + gm] = acc;
+        }
+    }
+}
 
 template <typename F>
 __global__ __launch_bounds__(256) void gp_kstar(const GpParams p, const GpPredict q) {
@@ -1401,18 +1423,79 @@ __global__ __launch_bounds__(256) void gp_predict(const GpParams p, const GpPred
         const int gm = mt * T + tid;
         if (gm < m) q.var[(size_t)b * q.mmax + gm] = (c + s) - (rowsum[tid][0] + rowsum[tid][1]);
     }
-    // mean: wave per row, lanes over i
-    for (int o = 0; o < p.nout; ++o) {
-        const double* al = p.alpha + ((size_t)b * p.nout + o) * p.nmax;
-        for (int r = wave; r < T; r += 4) {
-            const int gm = mt * T + r;
-            if (gm >= m) continue;
-            double acc = 0.0;
-            for (int i = lane; i < n; i += 64) acc = fma(Ks[(size_t)gm * q.ldk + i], al[i], acc);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-            if (lane == 0) q.mean[((size_t)b * p.nout + o) * q.mmax + gm] = acc;
-        }
+    predict_mean(p, q, b, mt, wave, lane);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Posterior covariance (GaussianProcessRegressor.predict(return_cov=True)): two tile GEMMs in NT form on gp_kstar's Kstar,
+//   gp_pcov_w   W = Kstar K^-1            one workgroup per 64 x 64 tile (mt, it) of W; K^-1 is symmetric, so its rows are
+//                                         the k-contiguous operand; the it = 0 workgroups also write the mean
+//   gp_pcov     cov = Kss + s I - W Kstar^T   lower tiles (ti >= tj) only, Kss = c k(xs_i - xs_j) evaluated in the epilogue;
+//                                         each tile is staged in LDS and stored twice (as itself and mirrored), the diagonal
+//                                         tile's upper half from its lower half: the result is symmetric bit for bit
+// Contractions run over this track's padded n only (Kstar is zero in columns [n, npad)); every output element of the
+// track's [mmax][mmax] block is written, zeros outside [0, m)^2.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gp_pcov_w(const GpParams p, const GpPredict q) {
+    const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = p.n[b], m = q.m[b], nb = nblocks(n);
+    const int mt = blockIdx.x / p.nb_max, it = blockIdx.x % p.nb_max;
+    if (mt * T >= m || it >= nb) return;
+    const size_t ld = p.ld;
+    const double* Ks = q.Kstar + (size_t)b * q.mb_max * T * q.ldk;
+    const double* Kinv = q.Kinv + (size_t)b * ld * ld;
+    double* W = q.W + (size_t)b * q.mb_max * T * q.ldk;
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+    v4d acc[2][2];
+    zero_acc(acc);
+    wave_gemm_nt(acc, Ks + (size_t)(mt * T + wr) * q.ldk, q.ldk, Kinv + (size_t)(it * T + wc) * ld, ld, 0, nb * T, lane);
+    for_each_acc(acc, wave, lane, [&](int r, int c, double v) { W[(size_t)(mt * T + r) * q.ldk + it * T + c] = v; });
+    if (it == 0) predict_mean(p, q, b, mt, wave, lane);
+}
+
+template <typename F>
+__global__ __launch_bounds__(256) void gp_pcov(const GpParams p, const GpPredict q) {
+    __shared__ double S[T * LD];
+    const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // tile index -> (ti >= tj), as in gp_kbuild
+    const int tile = blockIdx.x;
+    int ti = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+    while (ti * (ti + 1) / 2 > tile) --ti;
+    const int tj = tile - ti * (ti + 1) / 2;
+    const int n = p.n[b], m = q.m[b], nb = nblocks(n);
+    const bool live = ti * T < m;  // (then tj * T < m too)
+    if (live) {
+        const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+        const double* Ks = q.Kstar + (size_t)b * q.mb_max * T * q.ldk;
+        const double* W = q.W + (size_t)b * q.mb_max * T * q.ldk;
+        v4d acc[2][2];
+        zero_acc(acc);
+        wave_gemm_nt(acc, W + (size_t)(ti * T + wr) * q.ldk, q.ldk, Ks + (size_t)(tj * T + wc) * q.ldk, q.ldk, 0, nb * T, lane);
+        const double c = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]), s = exp(p.theta[b * 3 + 2]);
+        const double* xs = q.xs + (size_t)b * q.mmax;
+        for_each_acc(acc, wave, lane, [&](int r, int cc, double v) {
+            const int gi = ti * T + r, gj = tj * T + cc;
+            double out = 0.0;
+            if (gi < m && gj < m) {
+                double kss = kernel_value<F>(c, (xs[gi] - xs[gj]) * inv_l);
+                if (gi == gj) kss += s;  // WhiteKernel: on the diagonal only
+                out = kss - v;
+            }
+            S[r * LD + cc] = out;
+        });
+        __syncthreads();
+    }
+    double* cov = q.cov + (size_t)b * q.mmax * q.mmax;
+    const size_t mm = q.mmax;
+    // tile (ti, tj) as it is, then mirrored to (tj, ti); row-major walks, so both stores are coalesced
+    for (int e = tid; e < T * T; e += 256) {
+        const int r = e / T, cc = e % T, gi = ti * T + r, gj = tj * T + cc;
+        if (gi < q.mmax && gj < q.mmax && (ti > tj || r >= cc)) cov[(size_t)gi * mm + gj] = live ? S[r * LD + cc] : 0.0;
+    }
+    for (int e = tid; e < T * T; e += 256) {
+        const int r = e / T, cc = e % T, gi = tj * T + r, gj = ti * T + cc;
+        if (gi < q.mmax && gj < q.mmax && (ti > tj || cc >= r)) cov[(size_t)gi * mm + gj] = live ? S[cc * LD + r] : 0.0;
     }
 }
 
@@ -1563,10 +1646,43 @@ int ste_gp_predict_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m
     q.Kinv = b->Kinv;
     q.mean = mean;
     q.var = var;
+    q.W = nullptr;
+    q.cov = nullptr;
     hipStream_t s = (hipStream_t)stream;
     with_kernel(p.kernel, [&](auto f) { hipLaunchKernelGGL(stegp::gp_kstar<decltype(f)>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q); });
     hipLaunchKernelGGL(stegp::gp_predict, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
     return gp_hip(hipGetLastError(), "gp_predict launch");
+}
+
+int ste_gp_predict_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
+                           double* W, double* mean, double* cov, void* stream) {
+    stegp::GpParams p;
+    int rc = gp_params(b, &p);
+    if (rc) return rc;
+    if (mmax <= 0) return gp_fail("mmax must be > 0");
+    if (!m || !xs || !Kstar || !W || !mean || !cov || !b->Kinv)
+        return gp_fail("m, xs, Kstar, W, mean, cov and batch.Kinv are required (run ste_gp_lml_f64 with Kinv set first)");
+    stegp::GpPredict q;
+    q.B = p.B;
+    q.mmax = mmax;
+    q.mb_max = (mmax + 63) / 64;
+    q.ldk = p.ld;
+    q.m = m;
+    q.xs = xs;
+    q.Kstar = Kstar;
+    q.Kinv = b->Kinv;
+    q.mean = mean;
+    q.var = nullptr;
+    q.W = W;
+    q.cov = cov;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned wtiles = (unsigned)(q.mb_max * p.nb_max), ctiles = (unsigned)(q.mb_max * (q.mb_max + 1) / 2);
+    with_kernel(p.kernel, [&](auto f) {
+        hipLaunchKernelGGL(stegp::gp_kstar<decltype(f)>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
+        hipLaunchKernelGGL(stegp::gp_pcov_w, dim3(wtiles, p.B), dim3(256), 0, s, p, q);
+        hipLaunchKernelGGL(stegp::gp_pcov<decltype(f)>, dim3(ctiles, p.B), dim3(256), 0, s, p, q);
+    });
+    return gp_hip(hipGetLastError(), "gp_pcov launch");
 }
 
 }  // extern "C"

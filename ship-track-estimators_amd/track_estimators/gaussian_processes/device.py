@@ -139,19 +139,35 @@ class GpDeviceBatch:
     def alpha(self):
         return [self.t_alpha[b, :, : self.n[b]].cpu().numpy().T for b in range(self.B)]
 
-    def predict(self, thetas, xq: Sequence[np.ndarray]):
-        """Posterior (mean (m_b, nout), std (m_b, nout)) per track at query inputs xq[b]."""
+    def predict_cov_bytes_per_track(self, mmax: int) -> int:
+        """HBM that ``predict(..., return_cov=True)`` allocates per track for ``mmax`` query inputs, on top of
+        ``bytes_per_track`` and K^-1 (8 * ld * ld): the Kstar and W workspaces, the covariance and the mean."""
+        return 8 * (2 * 64 * ((mmax + 63) // 64) * self.ld + mmax * mmax + (self.nout + 1) * mmax)
+
+    def predict(self, thetas, xq: Sequence[np.ndarray], return_cov: bool = False):
+        """Posterior (mean (m_b, nout), std (m_b, nout)) per track at query inputs xq[b]; with ``return_cov``
+        (mean (m_b, nout), cov (m_b, m_b)) per track instead (``ste_gp_predict_cov_f64``; cost:
+        ``predict_cov_bytes_per_track``, a MemoryError names it when the device cannot hold it)."""
         torch = self.torch
-        self.objective(thetas, eval_gradient=False, keep_kinv=True)
         m = np.array([len(q) for q in xq], dtype=np.int32)
         mmax = int(m.max())
         mb = (mmax + 63) // 64
+        if return_cov:
+            need = self.B * self.predict_cov_bytes_per_track(mmax)
+            free = torch.cuda.mem_get_info(self.device)[0]
+            if need > free:
+                raise MemoryError(f"posterior covariance of {self.B} tracks x {mmax} queries needs {need / 2**30:.1f} GiB of "
+                                  f"device memory (Kstar, W and cov: {self.predict_cov_bytes_per_track(mmax)} B per track), "
+                                  f"{free / 2**30:.1f} GiB are free; predict fewer tracks or query points per call")
+        self.objective(thetas, eval_gradient=False, keep_kinv=True)
         xs = np.zeros((self.B, mmax))
         for b in range(self.B):
             xs[b, : m[b]] = np.asarray(xq[b], dtype=np.float64).reshape(-1)
         t_m = torch.from_numpy(m).to(self.device)
         t_xs = torch.from_numpy(xs).to(self.device)
         t_ks = torch.empty((self.B, mb * 64, self.ld), dtype=torch.float64, device=self.device)
+        if return_cov:
+            return self._predict_cov(m, mmax, t_m, t_xs, t_ks)
         t_mean = torch.zeros((self.B, self.nout, mmax), dtype=torch.float64, device=self.device)
         t_var = torch.zeros((self.B, mmax), dtype=torch.float64, device=self.device)
         binding.check(self.lib.ste_gp_predict_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
@@ -166,3 +182,16 @@ class GpDeviceBatch:
             std = np.sqrt(v)
             out.append((mean[b, :, : m[b]].T.copy(), np.repeat(std[:, None], self.nout, axis=1)))
         return out
+
+    def _predict_cov(self, m, mmax, t_m, t_xs, t_ks):
+        torch = self.torch
+        t_w = torch.empty_like(t_ks)
+        t_mean = torch.zeros((self.B, self.nout, mmax), dtype=torch.float64, device=self.device)
+        t_cov = torch.empty((self.B, mmax, mmax), dtype=torch.float64, device=self.device)  # (every element is written)
+        binding.check(self.lib.ste_gp_predict_cov_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
+                                                      t_ks.data_ptr(), t_w.data_ptr(), t_mean.data_ptr(), t_cov.data_ptr(),
+                                                      self._stream()),
+                      "ste_gp_predict_cov_f64")
+        del t_w, t_ks
+        mean = t_mean.cpu().numpy()
+        return [(mean[b, :, : m[b]].T.copy(), t_cov[b, : m[b], : m[b]].cpu().numpy()) for b in range(self.B)]

@@ -12,6 +12,8 @@ kernels of csrc/ste_gp.hip.  scikit-learn kernel objects are accepted as the des
 initial hyper-parameters and bounds); ``ConstantKernel * K + WhiteKernel`` has a device implementation, with K an
 isotropic ``RBF`` (what the reference's examples use, examples/example_gaussian_process_batch.py:41) or ``Matern`` with
 nu = 0.5, 1.5, 2.5 (or inf, which is RBF).  Any other kernel raises ``NotImplementedError``: there is no CPU fallback.
+``normalize_y``, ``predict(return_std / return_cov)`` and ``sample_y`` follow scikit-learn 1.7; the posterior covariance is
+computed on the device (``ste_gp_predict_cov_f64``), the draws of ``sample_y`` on the host, as in scikit-learn.
 
 Additive extra: ``fit_batch`` / ``predict_batch`` fit many tracks at once, advancing all their optimisers in lock-step so
 that each objective evaluation is one batched launch (the reference loops over ships in Python,
@@ -202,6 +204,25 @@ def fit_thetas(batch: GpDeviceBatch, theta0: np.ndarray, bounds: np.ndarray, n_r
     return best_theta, -best_fun
 
 
+def _normalization(y):
+    """scikit-learn's ``normalize_y`` statistics of y (n, nout): the per-output mean and ``_handle_zeros_in_scale`` of the
+    per-output std (a constant output gets 1)."""
+    y = np.asarray(y, dtype=np.float64)
+    mean = np.mean(y, axis=0)
+    std = np.std(y, axis=0)
+    std[std < 10 * np.finfo(std.dtype).eps] = 1.0
+    return mean, std
+
+
+def _undo_normalization(mean, std_or_cov, y_mean, y_std, cov):
+    """(mean (m, nout), std (m, nout) or cov (m, m)) in normalised units -> the units of y, per output as in scikit-learn's
+    predict: mean * y_std + y_mean, std * y_std, cov (m, m, nout) = cov * y_std**2 (np.outer)."""
+    mean = y_std * mean + y_mean
+    if cov:
+        return mean, np.outer(std_or_cov, y_std**2).reshape(*std_or_cov.shape, -1)
+    return mean, std_or_cov * y_std
+
+
 def _check_random_state(seed):
     if seed is None or seed is np.random:
         return np.random.mtrand._rand
@@ -217,8 +238,6 @@ class DeviceGaussianProcessRegressor:
 
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None):
-        if normalize_y:
-            raise NotImplementedError("normalize_y=True is not supported on the HIP GP path")
         self.kernel = kernel
         self.alpha = alpha
         self.optimizer = optimizer
@@ -235,6 +254,12 @@ class DeviceGaussianProcessRegressor:
         y = np.asarray(y, dtype=np.float64).reshape(len(X), -1)
         theta0, bounds = _kernel_spec(self.kernel)
         self._rng = _check_random_state(self.random_state)
+        if self.normalize_y:
+            self._y_train_mean, self._y_train_std = _normalization(y)
+            y = (y - self._y_train_mean) / self._y_train_std
+        else:
+            self._y_train_mean, self._y_train_std = np.zeros(y.shape[1]), np.ones(y.shape[1])
+        # (y_train_ holds what the GP is fitted to: the normalised targets with normalize_y, as in scikit-learn)
         self.X_train_, self.y_train_ = X.copy(), y.copy()
         self._batch = GpDeviceBatch([X[:, 0]], [y], jitter=float(self.alpha), kernel=_kernel_kind(self.kernel))
         thetas, lml = fit_thetas(self._batch, theta0, bounds, self.n_restarts_optimizer, self._rng, self.optimizer)
@@ -252,13 +277,32 @@ class DeviceGaussianProcessRegressor:
         return (float(lml[0]), grad[0]) if eval_gradient else float(lml[0])
 
     def predict(self, X, return_std=False, return_cov=False):
-        if return_cov:
-            raise NotImplementedError("return_cov is not supported on the HIP GP path")
+        """Posterior mean (m,) or (m, nout); with ``return_std`` also the std of the same shape, with ``return_cov`` also
+        the covariance (m, m) or (m, m, nout) (``ste_gp_predict_cov_f64``).  Normalisation is undone per output."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
         X = np.asarray(X, dtype=np.float64).reshape(-1)
-        mean, std = self._batch.predict(self.kernel_.theta[None], [X])[0]
+        mean, spread = self._batch.predict(self.kernel_.theta[None], [X], return_cov=return_cov)[0]
+        if self.normalize_y:
+            mean, spread = _undo_normalization(mean, spread, self._y_train_mean, self._y_train_std, return_cov)
+        elif return_cov:
+            spread = np.repeat(spread[:, :, None], self.y_train_.shape[1], axis=2)
         if self.y_train_.shape[1] == 1:
-            mean, std = mean[:, 0], std[:, 0]
-        return (mean, std) if return_std else mean
+            mean, spread = mean[:, 0], spread[..., 0]
+        return (mean, spread) if (return_std or return_cov) else mean
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        """Draws from the posterior at X: (m, n_samples) for one output, (m, nout, n_samples) for several.  scikit-learn's
+        procedure: ``RandomState.multivariate_normal`` per output on the mean and covariance of
+        ``predict(X, return_cov=True)``.  The mean and covariance come from the device; the draw -- an O(m^3) SVD of the
+        covariance inside ``multivariate_normal`` -- runs on the host, as it does in scikit-learn."""
+        rng = _check_random_state(random_state)
+        y_mean, y_cov = self.predict(X, return_cov=True)
+        if y_mean.ndim == 1:
+            return rng.multivariate_normal(y_mean, y_cov, n_samples).T
+        y_samples = [rng.multivariate_normal(y_mean[:, t], y_cov[..., t], n_samples).T[:, np.newaxis]
+                     for t in range(y_mean.shape[1])]
+        return np.hstack(y_samples)
 
 
 class GPRegression:
@@ -278,6 +322,7 @@ class GPRegression:
         self._kernel = kernel
         self._gpr = gpr
         self._model = None
+        self._norm = None  # fit_batch with normalize_y: per-track (mean, std) of the targets
 
     @staticmethod
     def _training_data(ship_track: ShipTrack):
@@ -310,12 +355,24 @@ class GPRegression:
         # an integer seed means what it means for a loop of single fits (the reference's batch example builds one
         # regressor per ship): every track gets its own stream from that seed
         rng = [np.random.RandomState(seed) for _ in data] if isinstance(seed, (int, np.integer)) else _check_random_state(seed)
-        self._batch = GpDeviceBatch([X[:, 0] for X, _ in data], [y for _, y in data],
-                                    jitter=float(gpr_kwargs.get("alpha", 1e-10)), kernel=kind)
+        ys = [y for _, y in data]
+        # normalize_y: each track's own statistics, as a fit of its own would use
+        self._norm = [_normalization(y) for y in ys] if gpr_kwargs.get("normalize_y", False) else None
+        if self._norm is not None:
+            ys = [(y - mu) / sd for y, (mu, sd) in zip(ys, self._norm)]
+        self._batch = GpDeviceBatch([X[:, 0] for X, _ in data], ys, jitter=float(gpr_kwargs.get("alpha", 1e-10)),
+                                    kernel=kind)
         self._thetas, self._lml = fit_thetas(self._batch, theta0, bounds, int(gpr_kwargs.get("n_restarts_optimizer", 0)),
                                              rng, gpr_kwargs.get("optimizer", "fmin_l_bfgs_b"))
         return self._thetas, self._lml
 
-    def predict_batch(self, times: Sequence[np.ndarray]):
-        """[(mean (m_b, 2), std (m_b, 2)) for every track] after ``fit_batch`` (with its kernel function)."""
-        return self._batch.predict(self._thetas, [np.asarray(t).reshape(-1) for t in times])
+    def predict_batch(self, times: Sequence[np.ndarray], return_cov: bool = False):
+        """[(mean (m_b, 2), std (m_b, 2)) for every track] after ``fit_batch`` (with its kernel function); with
+        ``return_cov`` [(mean (m_b, 2), cov (m_b, m_b, 2))], the covariance per output as
+        ``DeviceGaussianProcessRegressor.predict(return_cov=True)`` gives it.  ``normalize_y`` is undone per track."""
+        out = self._batch.predict(self._thetas, [np.asarray(t).reshape(-1) for t in times], return_cov=return_cov)
+        if self._norm is not None:
+            return [_undo_normalization(mean, spread, mu, sd, return_cov) for (mean, spread), (mu, sd) in zip(out, self._norm)]
+        if return_cov:
+            return [(mean, np.repeat(cov[:, :, None], self._batch.nout, axis=2)) for mean, cov in out]
+        return out
