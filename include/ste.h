@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-#define STE_VERSION 340 /* 0.3.4: posterior covariance on the GP path (ste_gp_predict_cov_f64).
+#define STE_VERSION 340 /* 0.3.4: posterior covariance on the GP path (ste_gp_predict_cov_f64).  Unnumbered addition:
+                           the innovation log-likelihood of the forward pass (ste_ukf_loglik_f64,
+                           ste_ukf_forward_loglik_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -197,6 +199,40 @@ int ste_device_count(void);
 
 /* Forward UKF over all steps of every track: writes fwd_mean, fwd_cov, status. */
 int ste_ukf_forward_f64(const ste_ukf_batch_f64* b, void* stream);
+
+/*
+ * Innovation log-likelihood of the forward pass (the prediction-error decomposition), per track.  For every measurement
+ * update the pass performs -- the initial one at z[:, 0] unless STE_FLAG_NO_INITIAL_UPDATE, then one per upd_idx[k] >= 0 --
+ * with x-, P- the state it starts from (the predicted one, recorded noise_pred included; the prior for the initial update),
+ * z its observation column (+ noise_upd), R_u its R (rescaled under STE_FLAG_ROBUST):
+ *      S = H P- H^T + R_u,   y = z - H x-  with y[3] wrapped to [-180, 180) as the update wraps it,
+ *      S^+ the update's own pseudo-inverse, keeping the r eigenvalues lambda_i with |lambda| > 1e-15 max |lambda|,
+ *      nis_u = y^T S^+ y,    l_u = -1/2 (nis_u + sum_i log lambda_i + r log 2 pi)
+ * l_u is the Gaussian log density of the part of y in the range of S (the part in its null space enters neither the gain
+ * nor l_u; for H = diag(1, 1, 0, 0) that is y[2], y[3] and r = 2).  A kept eigenvalue <= 0 makes l_u NaN; a non-finite
+ * observation that makes the update's state NaN makes the track's loglik NaN too.  r is the pseudo-inverse's own count: a NaN
+ * eigenvalue (an S that is not finite, e.g. every update after such an observation) is not inverted, so it adds nothing to
+ * dof, while the update still counts in nupd and its l_u is NaN.
+ * Output arrays are indexed like status and nsteps: a window's pointers name its first track, rows hold track_stride.
+ */
+typedef struct ste_ukf_loglik_f64 {
+    double*  loglik; /* [B] out, required: sum of l_u over the track's updates */
+    int32_t* dof;    /* [B] out or NULL: sum of the ranks r (NaN eigenvalues not counted, see above) */
+    int32_t* nupd;   /* [B] out or NULL: updates summed */
+    double*  nis;    /* [Nmax+1][track_stride] out or NULL: nis_u of the update that produced history row k; NaN in rows
+                        0..nsteps[t] without an update; rows past nsteps[t] are not written */
+} ste_ukf_loglik_f64;
+
+/* The forward pass of ste_ukf_forward_f64 with the lane-per-track mapping, plus the innovation log-likelihood above.
+ *   - fwd_mean and fwd_cov both non-NULL: everything else the call writes (histories, rts_work, status) is bit-identical to
+ *     ste_ukf_forward_f64 with flags | STE_FLAG_LANES_1, and ste_urtss_backward_f64 may follow it unchanged.
+ *   - both NULL: the likelihood alone (no history is written; rts_work must be NULL).  One such call per candidate (Q, R)
+ *     scores the candidates over a whole fleet (track_estimators.batch.log_likelihood_grid).
+ * Recorded noise, STE_FLAG_ROBUST, STE_FLAG_NO_INITIAL_UPDATE, STE_FLAG_SHARED_P0, STE_FLAG_PACKED_COV, ragged nsteps and
+ * windows are accepted.  Refused with STE_EINVAL before any launch: STE_FLAG_LANES_4, time slices (step_begin != 0 or
+ * step_end not in {0, Nmax}), l or l->loglik NULL, exactly one of fwd_mean / fwd_cov NULL, rts_work without histories,
+ * and whatever ste_ukf_forward_f64 refuses. */
+int ste_ukf_forward_loglik_f64(const ste_ukf_batch_f64* b, const ste_ukf_loglik_f64* l, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

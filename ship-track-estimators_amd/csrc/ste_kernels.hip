@@ -485,8 +485,11 @@ __device__ __forceinline__ int robust_terms(const double (&H)[4][4], const doubl
 }
 
 // Linear Kalman update with pseudo-inverse gain and Joseph-form covariance (unscented.py:219-265).
+// kLik: also the update's log-likelihood terms into *lik (UpdLik, ste_math.h), from the eigenvalues the pseudo-inverse
+// already has and the innovation it already forms.
+template <bool kLik = false>
 __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double (&P)[4][4], const double (&zin)[4],
-                                          const double* noise, size_t nrow, size_t B, size_t t) {
+                                          const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr) {
     double H[4][4], R[4][4];
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
@@ -541,10 +544,22 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
             }
         }
         blk = blk || !(fin * 0.0 == 0.0);  // a non-finite S is NaN on either route: no veto against the fast one
-        if (__all(blk))
-            sym_pinv4_block2(S, Si);
-        else
-            st |= sym_pinv4(S, Si);
+        if constexpr (kLik) {
+            if (__all(blk)) {
+                double w[2];
+                sym_pinv4_block2(S, Si, w);
+                pinv_loglik_terms(w, *lik);
+            } else {
+                double w[4];
+                st |= sym_pinv4(S, Si, w);
+                pinv_loglik_terms(w, *lik);
+            }
+        } else {
+            if (__all(blk))
+                sym_pinv4_block2(S, Si);
+            else
+                st |= sym_pinv4(S, Si);
+        }
     }
     mmt(P, H, PHt);
     mm(PHt, Si, K);
@@ -557,6 +572,17 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
         y[r] = z[r] - hx;
     }
     y[3] = wrap180(y[3]);
+    if constexpr (kLik) {
+        double nis = 0.0;
+        STE_UNROLL
+        for (int r = 0; r < 4; ++r) {
+            double acc = 0.0;
+            STE_UNROLL
+            for (int c = 0; c < 4; ++c) acc = fma(Si[r][c], y[c], acc);
+            nis = fma(y[r], acc, nis);  // y^T S^+ y
+        }
+        lik->nis = nis;
+    }
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
         double acc = x[r];
@@ -742,9 +768,10 @@ __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], doubl
 
 // Measurement update on packed (x, P): the closed form for H = diag(1, 1, 0, 0) (kFastUpd, chosen by launch_forward from
 // the matrices), otherwise the general 4x4 route (any H, R; the opt-in robust rescaling).
-template <bool kFastUpd, bool kRobust = false>
+// kLik: also the update's log-likelihood terms into *lik (either route).
+template <bool kFastUpd, bool kRobust = false, bool kLik = false>
 __device__ __forceinline__ int lane_update(const Mats& p, double (&x)[4], double (&P)[10], const double (&zin)[4],
-                                           const double* noise, size_t nrow, size_t B, size_t t) {
+                                           const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr) {
     if (kFastUpd) {
         double z[4];
         STE_UNROLL
@@ -756,7 +783,7 @@ __device__ __forceinline__ int lane_update(const Mats& p, double (&x)[4], double
             STE_UNROLL
             for (int c = 0; c < 4; ++c) z[c] += noise[(nrow * 4 + c) * B + t];
         }
-        lane_update_sel2(r00, r01, r11, x, P, z);
+        lane_update_sel2<kLik>(r00, r01, r11, x, P, z, lik);
         return st;
     } else {
         double Pf[4][4];
@@ -765,7 +792,7 @@ __device__ __forceinline__ int lane_update(const Mats& p, double (&x)[4], double
             STE_UNROLL
             for (int c = 0; c < 4; ++c) Pf[r][c] = P[tix(r, c)];
         }
-        const int st = ukf_update(p, x, Pf, zin, noise, nrow, B, t);
+        const int st = ukf_update<kLik>(p, x, Pf, zin, noise, nrow, B, t, lik);
         STE_UNROLL
         for (int r = 0; r < 4; ++r) {
             STE_UNROLL
@@ -790,8 +817,21 @@ __device__ __forceinline__ void store_hist(const KParams& p, size_t row, size_t 
 // kRobust: the closed-form update with the closed-form robust rescaling in front of it (a template parameter, so that the
 // default instantiation's step loop is exactly the one measured without it); with kFastUpd false the general route reads
 // robust_iters itself.
-template <bool kGains, bool kFastUpd, bool kRobust, bool kSched>
-__device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t) {
+// kLik: the innovation log-likelihood (ste_ukf_forward_loglik_f64): kLikOff (every existing kernel), kLikHist (the pass
+// as it is, plus the likelihood) or kLikOnly (no histories: store_hist skipped, kGains false, rts_work NULL).  l_u, the
+// ranks and the update count add up in registers and are written once per track; `lk->nis`, if given, gets one row per
+// history row (NaN where no update fired).
+enum { kLikOff = 0, kLikHist = 1, kLikOnly = 2 };
+struct LikParams {
+    double* loglik;  // [ld] (indexed like status)
+    int32_t* dof;    // [ld] or nullptr
+    int32_t* nupd;   // [ld] or nullptr
+    double* nis;     // [Nmax+1][ld] or nullptr
+};
+
+template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff>
+__device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t, const LikParams* lk = nullptr) {
+    static_assert(kLik != kLikOnly || (!kGains && !kSched), "the likelihood-only pass writes no histories and no work rows");
     const size_t B = (size_t)p.ld;  // row pitch of every per-track array (= the batch's own width unless it is a window)
     if (t >= (size_t)p.B) return;
     // A later time slice of a forward pass (slice_params): x0 / P0 name history row k0 -- the state the previous launch
@@ -824,7 +864,7 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
             for (int c = r; c < 4; ++c) P[tix(r, c)] = 0.5 * (Pf[r][c] + Pf[c][r]);
         }
     }
-    store_hist(p, 0, B, t, x, P);  // slot 0 = prior (kalman_filter.py:76-77); a later slice rewrites row k0 with its own bits
+    if (kLik != kLikOnly) store_hist(p, 0, B, t, x, P);  // slot 0 = prior (kalman_filter.py:76-77); a later slice rewrites row k0 with its own bits
 
     // (a later slice may run in the same launch, on the same wave, as the one that wrote these two words -- the scheduled
     //  kernel -- without a cache invalidate in between: read them past the CU's L1)
@@ -860,10 +900,23 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
         st |= lane_predict<true, kSched>(p.m, xc, Pc, V, false, p.dt[t], p.sog_rate[t], p.cog_rate[t], nullptr, p.noise_rts, 0, B, t,
                                          p.rts_work, true, noise_mode, flagged, first_bad, tk, Qv);
     }
+    double lik_sum = 0.0;  // kLik: sum of l_u, of the ranks, and the number of updates
+    int lik_dof = 0, lik_nupd = 0;
     if (initial_update) {
         double z0[4];
         load_vec(p.z, 0, B, t, z0);
-        st |= lane_update<kFastUpd, kRobust>(p.m, x, P, z0, p.noise_upd, 0, B, t);  // kalman_filter.py:81
+        if constexpr (kLik != kLikOff) {
+            UpdLik u;
+            st |= lane_update<kFastUpd, kRobust, true>(p.m, x, P, z0, p.noise_upd, 0, B, t, &u);
+            lik_sum += update_loglik(u);
+            lik_dof += u.rank;
+            lik_nupd += 1;
+            if (lk->nis) st_stream(&lk->nis[t], u.nis);
+        } else {
+            st |= lane_update<kFastUpd, kRobust>(p.m, x, P, z0, p.noise_upd, 0, B, t);  // kalman_filter.py:81
+        }
+    } else if (kLik != kLikOff && lk->nis) {
+        st_stream(&lk->nis[t], __builtin_nan(""));
     }
 
     // The eigenvectors of the fan matrix carry over from step to step (warm start); restarted from the identity every
@@ -901,9 +954,21 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
             const bool warm = (k & (kColdEvery - 1)) != 0;
             st |= lane_predict<kGains, kSched>(p.m, x, P, V, warm, dt, sr, cr, p.noise_pred, p.noise_rts, (size_t)k, B, t, work,
                                                upd || noise_mode, noise_mode, flagged, first_bad, tk, Qv);
-            if (upd) st |= lane_update<kFastUpd, kRobust>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t);
+            if constexpr (kLik != kLikOff) {
+                UpdLik u;
+                u.nis = __builtin_nan("");
+                if (upd) {
+                    st |= lane_update<kFastUpd, kRobust, true>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t, &u);
+                    lik_sum += update_loglik(u);
+                    lik_dof += u.rank;
+                    lik_nupd += 1;
+                }
+                if (lk->nis) st_stream(&lk->nis[((size_t)k + 1) * B + t], u.nis);
+            } else {
+                if (upd) st |= lane_update<kFastUpd, kRobust>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t);
+            }
             if (!ui_ok) st |= STE_STATUS_BAD_INDEX;
-            store_hist(p, (size_t)k + 1, B, t, x, P);
+            if (kLik != kLikOnly) store_hist(p, (size_t)k + 1, B, t, x, P);
         }
     }
     double chk = 0.0;
@@ -913,11 +978,23 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
     for (int e = 0; e < 10; ++e) chk += P[e] * 0.0;
     if (!(chk == 0.0)) st |= STE_STATUS_NAN;  // inf*0 and nan*0 are NaN
     p.status[t] = st;
+    if constexpr (kLik != kLikOff) {
+        lk->loglik[t] = lik_sum;
+        if (lk->dof) lk->dof[t] = lik_dof;
+        if (lk->nupd) lk->nupd[t] = lik_nupd;
+    }
 }
 
 template <bool kGains, bool kFastUpd, bool kRobust = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_l1(const KParams p) {
     forward_tile_l1<kGains, kFastUpd, kRobust, false>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
+}
+
+// ukf_forward_l1 with the innovation log-likelihood (ste_ukf_forward_loglik_f64).  KParams stays the first argument (late_k0
+// reads it at its own offset); the likelihood's outputs follow it.
+template <bool kGains, bool kFastUpd, bool kRobust, int kLik>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_lik(const KParams p, const LikParams l) {
+    forward_tile_l1<kGains, kFastUpd, kRobust, false, kLik>(p, (size_t)blockIdx.x * 64 + threadIdx.x, &l);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2364,7 +2441,7 @@ int ste::abi_check_hip(hipError_t e, const char* what) { return check_hip(e, wha
 
 namespace {
 
-int make_params(const ste_ukf_batch_f64* b, bool need_fwd_in, bool need_sm_out, ste::KParams* kp) {
+int make_params(const ste_ukf_batch_f64* b, bool need_fwd_in, bool need_sm_out, ste::KParams* kp, bool need_hist = true) {
     if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
     if (b->n != 4) return fail(STE_EINVAL, "state dimension n must be 4 (heading index 3 is hard-wired, unscented.py:250)");
     if (b->B <= 0) return fail(STE_EINVAL, "B must be > 0");
@@ -2375,7 +2452,8 @@ int make_params(const ste_ukf_batch_f64* b, bool need_fwd_in, bool need_sm_out, 
     if (b->Nmax > 0 && (!b->dt || !b->sog_rate || !b->cog_rate || !b->upd_idx))
         return fail(STE_EINVAL, "dt, sog_rate, cog_rate and upd_idx are required when Nmax > 0");
     if (!b->z) return fail(STE_EINVAL, "z is required");
-    if (!b->fwd_mean || !b->fwd_cov || !b->status) return fail(STE_EINVAL, "fwd_mean, fwd_cov and status are required");
+    if (need_hist && (!b->fwd_mean || !b->fwd_cov)) return fail(STE_EINVAL, "fwd_mean, fwd_cov and status are required");
+    if (!b->status) return fail(STE_EINVAL, "fwd_mean, fwd_cov and status are required");
     if (need_sm_out && (!b->sm_mean || !b->sm_cov)) return fail(STE_EINVAL, "sm_mean and sm_cov are required");
     (void)need_fwd_in;
     kp->B = b->B;
@@ -2514,6 +2592,26 @@ int launch_forward(const ste::KParams& kp, hipStream_t s) {
     return check_hip(hipGetLastError(), "ukf_forward launch");
 }
 
+// The forward pass with the innovation log-likelihood: lane per track, whole passes (ste_ukf_forward_loglik_f64 checks).
+// With histories the kernel is the one launch_forward takes (same kGains / kFastUpd / kRobust choice), plus the likelihood.
+int launch_forward_lik(const ste::KParams& kp, const ste::LikParams& lp, hipStream_t s) {
+    const bool robust = kp.m.robust_iters > 0;
+    const unsigned grid = (unsigned)((kp.B + 63) / 64);
+    const int which = (kp.fwd_mean ? 0 : 8) | (kp.rts_work ? 4 : 0) | (kp.fast_upd ? (robust ? 2 : 1) : 0);
+    switch (which) {
+#define STE_LK(n, g, f, r, m) \
+    case n: hipLaunchKernelGGL((ste::ukf_forward_lik<g, f, r, m>), dim3(grid), dim3(64), 0, s, kp, lp); break;
+        STE_LK(0, false, false, false, ste::kLikHist) STE_LK(1, false, true, false, ste::kLikHist)
+        STE_LK(2, false, true, true, ste::kLikHist) STE_LK(4, true, false, false, ste::kLikHist)
+        STE_LK(5, true, true, false, ste::kLikHist) STE_LK(6, true, true, true, ste::kLikHist)
+        STE_LK(8, false, false, false, ste::kLikOnly) STE_LK(9, false, true, false, ste::kLikOnly)
+        STE_LK(10, false, true, true, ste::kLikOnly)
+#undef STE_LK
+        default: return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: rts_work needs the histories");
+    }
+    return check_hip(hipGetLastError(), "ukf_forward_lik launch");
+}
+
 // Batches of at most this many tracks smooth with the two-kernel form (urtss_gains_all + urtss_recur_lean): up to there the
 // one-kernel smoother is a few waves running a latency chain of ~1.5-4.7 us per step, and the extra 440 B per track-step of
 // the gains pass cost less than the chain they remove; a batch that fills the chip is bound by bytes and issue instead.
@@ -2650,6 +2748,30 @@ int ste_ukf_forward_f64(const ste_ukf_batch_f64* b, void* stream) {
     rc = slice_params(b, &kp);
     if (rc) return rc;
     return launch_forward(kp, (hipStream_t)stream);
+}
+
+int ste_ukf_forward_loglik_f64(const ste_ukf_batch_f64* b, const ste_ukf_loglik_f64* l, void* stream) {
+    if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
+    if (!l) return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: the likelihood outputs (l) are NULL");
+    if (!l->loglik) return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: l->loglik is required");
+    const bool hist = b->fwd_mean != nullptr;
+    if (hist != (b->fwd_cov != nullptr))
+        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: fwd_mean and fwd_cov go together: both (histories) or neither "
+                                "(the likelihood alone)");
+    if (!hist && b->rts_work)
+        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: rts_work needs the histories (the smoother reads both); pass "
+                                "fwd_mean and fwd_cov, or no rts_work");
+    if (b->flags & STE_FLAG_LANES_4)
+        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64 runs the lane-per-track mapping only: STE_FLAG_LANES_4 is refused");
+    if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
+        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64 runs whole passes: the likelihood sums over every update, so time "
+                                "slices (step_begin / step_end) are refused");
+    ste::KParams kp;
+    int rc = make_params(b, false, false, &kp, hist);
+    if (rc) return rc;
+    kp.flags |= STE_FLAG_LANES_1;
+    const ste::LikParams lp = {l->loglik, l->dof, l->nupd, l->nis};
+    return launch_forward_lik(kp, lp, (hipStream_t)stream);
 }
 
 size_t ste_ukf_forward_sched_workspace(int32_t nwindows, int32_t max_slices, int64_t ntiles_total, int32_t nrounds,

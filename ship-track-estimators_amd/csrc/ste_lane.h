@@ -477,8 +477,10 @@ __device__ __forceinline__ int robust_rescale_sel2(const Mats& p, const double (
 // (I - K H) P (I - K H)^T + K R K^T needs the products with those two columns only.  r00, r01, r11: the block of R.
 // The unobserved components of the innovation still reach the state through exact zeros of K (0 * NaN = NaN in the
 // reference when an observation carries a non-finite speed or course): kept as a poison term.
+// kLik: also the update's log-likelihood terms into *lik (UpdLik, ste_math.h); the poison term reaches nis as well.
+template <bool kLik = false>
 __device__ __forceinline__ void lane_update_sel2(double r00, double r01, double r11, double (&x)[4], double (&P)[10],
-                                                 const double (&z)[4]) {
+                                                 const double (&z)[4], UpdLik* lik = nullptr) {
 #pragma clang fp contract(off)  // explicit fma() only: the same bits in every kernel this is inlined into
     double Sm[4][4], Si[4][4];
     STE_UNROLL
@@ -490,8 +492,15 @@ __device__ __forceinline__ void lane_update_sel2(double r00, double r01, double 
     Sm[0][1] = P[tix(0, 1)] + r01;
     Sm[1][0] = Sm[0][1];
     Sm[1][1] = P[tix(1, 1)] + r11;
-    sym_pinv4_block2(Sm, Si);
+    double w[2];
+    sym_pinv4_block2(Sm, Si, w);
     const double i00 = Si[0][0], i01 = Si[0][1], i11 = Si[1][1];
+    if constexpr (kLik) {
+        const double y0 = z[0] - x[0], y1 = z[1] - x[1];
+        const double u0 = fma(i01, y1, i00 * y0), u1 = fma(i11, y1, i01 * y0);  // S^+ y
+        lik->nis = fma(y1, u1, y0 * u0) + fma(0.0, z[2], 0.0 * z[3]);
+        pinv_loglik_terms(w, *lik);
+    }
     double K[4][2];
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {

@@ -628,9 +628,10 @@ __device__ __forceinline__ int sym_sqrt4(const double (&P)[4][4], double scale, 
 
 // Moore–Penrose pseudo-inverse of a symmetric 4x4 with NumPy's cutoff: singular values (= |eigenvalues|) not larger
 // than rcond * max are dropped (np.linalg.pinv as called at unscented.py:243 and :333).
+// `w` receives the eigenvalues (the innovation log-likelihood takes the kept ones, pinv_loglik_terms).
 template <bool kWarm>
-__device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4][4], EigBasis& basis) {
-    double A[4][4], w[4], f[4];
+__device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4][4], EigBasis& basis, double (&w)[4]) {
+    double A[4][4], f[4];
     double (&V)[4][4] = basis.V;
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
@@ -659,6 +660,17 @@ __device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4
     return st;
 }
 
+template <bool kWarm>
+__device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4][4], EigBasis& basis) {
+    double w[4];
+    return sym_pinv4<kWarm>(S, Si, basis, w);
+}
+
+__device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4][4], double (&w)[4]) {
+    EigBasis none;
+    return sym_pinv4<false>(S, Si, none, w);
+}
+
 __device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4][4]) {
     EigBasis none;
     return sym_pinv4<false>(S, Si, none);
@@ -667,7 +679,8 @@ __device__ __forceinline__ int sym_pinv4(const double (&S)[4][4], double (&Si)[4
 // The same for an S that is zero outside its leading 2 x 2 block -- S = H P H^T + R with an H that observes two components
 // (the reference's H = diag(1, 1, 0, 0)): its eigen-decomposition is ONE exact rotation, with the formulas of jacobi_rot,
 // instead of sweeps over a matrix that is three quarters zeros.  The caller checks the structure (wave-uniformly).
-__device__ __forceinline__ void sym_pinv4_block2(const double (&S)[4][4], double (&Si)[4][4]) {
+// `w` receives the block's two eigenvalues (the other two are exact zeros, never kept).
+__device__ __forceinline__ void sym_pinv4_block2(const double (&S)[4][4], double (&Si)[4][4], double (&w)[2]) {
     const double a = S[0][0], d = S[1][1], b = 0.5 * (S[0][1] + S[1][0]);
     const bool go = b * b > kRotTol2 * fabs(a * d);
     const double delta = d - a, two_b = b + b;
@@ -690,7 +703,43 @@ __device__ __forceinline__ void sym_pinv4_block2(const double (&S)[4][4], double
     Si[1][1] = fma(ss, f0, cc * f1);
     Si[0][1] = cs * (f1 - f0);
     Si[1][0] = Si[0][1];
+    w[0] = w0;
+    w[1] = w1;
 }
+
+__device__ __forceinline__ void sym_pinv4_block2(const double (&S)[4][4], double (&Si)[4][4]) {
+    double w[2];
+    sym_pinv4_block2(S, Si, w);
+}
+
+// What one measurement update contributes to the innovation log-likelihood ("Innovation log-likelihood"):
+//   l_u = -1/2 (nis + logdet + rank log 2 pi),  nis = y^T S^+ y,  logdet = sum of log(lambda) over S's kept eigenvalues,
+// rank = their number.  The kept eigenvalues are those the pseudo-inverse inverts (|lambda| > kPinvRcond max |lambda|);
+// a kept eigenvalue <= 0 makes logdet NaN.
+struct UpdLik {
+    double nis, logdet;
+    int rank;
+};
+constexpr double kLog2Pi = 1.8378770664093453;  // log(2 pi)
+
+template <int N>
+__device__ __forceinline__ void pinv_loglik_terms(const double (&w)[N], UpdLik& u) {
+    double smax = 0.0;
+    STE_UNROLL
+    for (int i = 0; i < N; ++i) smax = fmax(smax, fabs(w[i]));
+    const double cutoff = kPinvRcond * smax;
+    double ld = 0.0;
+    int r = 0;
+    STE_UNROLL
+    for (int i = 0; i < N; ++i) {
+        const bool keep = fabs(w[i]) > cutoff;
+        ld += keep ? log(w[i]) : 0.0;
+        r += keep ? 1 : 0;
+    }
+    u.logdet = ld;
+    u.rank = r;
+}
+__device__ __forceinline__ double update_loglik(const UpdLik& u) { return -0.5 * (u.nis + u.logdet + u.rank * kLog2Pi); }
 
 // 1/d for normal d of either sign: v_rcp_f64 (~2^-24) and two Newton steps (below 2^-80 before the final rounding).
 __device__ __forceinline__ double rcp_refined(double d) {

@@ -79,6 +79,17 @@ class SteUkfBatchF64(C.Structure):
     ]
 
 
+class SteUkfLoglikF64(C.Structure):
+    """Mirror of ``struct ste_ukf_loglik_f64`` (include/ste.h)."""
+
+    _fields_ = [
+        ("loglik", _dp),
+        ("dof", _dp),
+        ("nupd", _dp),
+        ("nis", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -176,6 +187,7 @@ SYMBOLS = {
     "ste_last_error": (C.c_char_p, []),
     "ste_device_count": (C.c_int, []),
     "ste_ukf_forward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
+    "ste_ukf_forward_loglik_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfLoglikF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -336,10 +336,13 @@ class DeviceBatch:
     _PACKED_INDEX = [min(r, c) * 4 - (min(r, c) * (min(r, c) - 1)) // 2 + abs(r - c) for r in range(4) for c in range(4)]
 
     def __init__(self, hb: HostBatch, device="cuda:0", alloc_smoothed: bool = True, fuse_gains: bool = True,
-                 tuning: int = 0, packed_cov: bool = True, sm_pos: bool = False, upload: bool = True):
+                 tuning: int = 0, packed_cov: bool = True, sm_pos: bool = False, upload: bool = True,
+                 histories: bool = True):
         """``sm_pos``: also allocate the smoother's optional [N+1][2][B] output of smoothed lon / lat (what a multi-GPU
         run exchanges).  ``upload=False``: allocate the input tensors without filling them -- ``upload_tracks(lo, hi)``
-        then brings the host batch up window by window (``run_fleet``)."""
+        then brings the host batch up window by window (``run_fleet``).  ``histories=False``: no history, smoother or
+        work buffers at all -- a batch for ``log_likelihood`` alone (``log_likelihood_grid``); ``forward`` / ``run``
+        refuse it."""
         import torch
 
         self.lib = binding.require_gpu()
@@ -358,12 +361,14 @@ class DeviceBatch:
         B, N = hb.B, hb.Nmax
         self.ntracks, self.lo, self.parent = B, 0, None
         f64 = dict(dtype=torch.float64, device=self.device)
-        self.fwd_mean = torch.empty((N + 1, 4, B), **f64)
+        if not histories:
+            alloc_smoothed = False
+        self.fwd_mean = torch.empty((N + 1, 4, B), **f64) if histories else None
         # covariance histories as upper triangles on the device (they are symmetric by construction); download()
         # expands them to the reference's (.., 4, 4).  packed_cov=False keeps full matrices in HBM.
         self.packed_cov = bool(packed_cov)
         cov_rows = 10 if self.packed_cov else 16
-        self.fwd_cov = torch.empty((N + 1, cov_rows, B), **f64)
+        self.fwd_cov = torch.empty((N + 1, cov_rows, B), **f64) if histories else None
         self.sm_mean = torch.empty((N + 1, 4, B), **f64) if alloc_smoothed else None
         self.sm_cov = torch.empty((N + 1, cov_rows, B), **f64) if alloc_smoothed else None
         # rows past a short track's end are never written: zeros, so that a gathered tensor is defined everywhere
@@ -391,7 +396,8 @@ class DeviceBatch:
         for name in self._IN:
             ten = self.t[name]
             setattr(s, name, None if ten is None else ten.data_ptr())
-        s.fwd_mean, s.fwd_cov = self.fwd_mean.data_ptr(), self.fwd_cov.data_ptr()
+        s.fwd_mean = None if self.fwd_mean is None else self.fwd_mean.data_ptr()
+        s.fwd_cov = None if self.fwd_cov is None else self.fwd_cov.data_ptr()
         s.sm_mean = None if self.sm_mean is None else self.sm_mean.data_ptr()
         s.sm_cov = None if self.sm_cov is None else self.sm_cov.data_ptr()
         s.status = self.status.data_ptr()
@@ -501,9 +507,15 @@ class DeviceBatch:
         cuts = list(range(0, nsteps, step)) + [nsteps]
         return list(zip(cuts[:-1], cuts[1:]))
 
+    def _require_histories(self, what):
+        if self.fwd_mean is None:
+            raise ValueError(f"{what} needs the filtered histories, and this batch was built with histories=False (a batch "
+                             "for log_likelihood alone)")
+
     def forward(self, stream=None, slices: int = 1, mark: bool = True):
         """The forward pass; ``slices`` > 1 issues it as that many launches over consecutive step ranges (include/ste.h:
         step_begin / step_end), bit-identical to the single launch."""
+        self._require_histories("forward()")
         s = self.struct
         try:
             for k0, k1 in self.slice_bounds(int(s.Nmax), int(slices)):
@@ -515,14 +527,53 @@ class DeviceBatch:
             self._mark_use(stream)
 
     def backward(self, stream=None, mark: bool = True):
+        self._require_histories("backward()")
         binding.check(self.lib.ste_urtss_backward_f64(C.byref(self.struct), self._stream(stream)),
                       "ste_urtss_backward_f64")
         if mark:
             self._mark_use(stream)
 
     def run(self, stream=None):
+        self._require_histories("run()")
         binding.check(self.lib.ste_ukf_urtss_f64(C.byref(self.struct), self._stream(stream)), "ste_ukf_urtss_f64")
         self._mark_use(stream)
+
+    def log_likelihood(self, stream=None, nis: bool = False) -> "LogLikelihood":
+        """The forward pass with the innovation log-likelihood (include/ste.h: ste_ukf_forward_loglik_f64), on this batch's
+        own histories: with histories allocated it writes the same bits as ``forward`` with the lane-per-track mapping
+        (rts_work and status included, so ``backward`` may follow).  It always uses the lane-per-track mapping, whatever
+        ``lanes`` the batch was built with: the quad mapping has no likelihood.  Returns a ``LogLikelihood`` of NumPy
+        arrays in this batch's track order (HostBatch slots, ``hb.order`` maps them to the caller's tracks).
+        ``nis``: also the normalised innovation squared per history row, (B, Nmax+1), NaN where no update fired and past
+        a track's last step.  ``stream``: the stream the pass runs on (default: the current one); it is ordered after the
+        current stream's work and the batch's upload, and the results are read back on it once the pass is done."""
+        torch = self.torch
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)  # whatever the caller queued on the current stream (inputs, histories) comes first
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        B, N = self.ntracks, int(self.struct.Nmax)
+        ld = int(self.struct.track_stride or self.struct.B)
+        col = self.lo  # a window's first column in rows of `ld` (0 for a batch of its own)
+        dev = dict(device=self.device)
+        with torch.cuda.stream(st):  # outputs allocated, filled, written and read back on `st`, in that order
+            ll = torch.empty((B,), dtype=torch.float64, **dev)
+            dof = torch.empty((B,), dtype=torch.int32, **dev)
+            nupd = torch.empty((B,), dtype=torch.int32, **dev)
+            nis_t = torch.full((N + 1, ld), float("nan"), dtype=torch.float64, **dev) if nis else None
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            s.flags = (s.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
+            lk = binding.SteUkfLoglikF64(ll.data_ptr(), dof.data_ptr(), nupd.data_ptr(),
+                                         None if nis_t is None else nis_t.data_ptr() + 8 * col)
+            binding.check(self.lib.ste_ukf_forward_loglik_f64(C.byref(s), C.byref(lk), self._stream(st)),
+                          "ste_ukf_forward_loglik_f64")
+            self._mark_use(st)
+            return LogLikelihood(loglik=ll.cpu().numpy(), dof=dof.cpu().numpy(), nupd=nupd.cpu().numpy(),
+                                 status=self.status.cpu().numpy(),
+                                 nis=None if nis_t is None else nis_t[:, col:col + B].T.cpu().numpy())
 
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
@@ -536,6 +587,7 @@ class DeviceBatch:
         host allocator recycles it once they are dropped, so only a process's first large download pays for pinning).
         10 000 x 500 with all four histories: 1.6 GB, ~35 ms over PCIe gen 5 instead of ~170 ms through pageable memory."""
         torch = self.torch
+        self._require_histories("download()")
         if self._pipeline_done is not None:  # results of a SmootherPipeline.submit still in flight on another stream
             torch.cuda.current_stream(self.device).wait_event(self._pipeline_done)
         out, pending = {}, []
@@ -1372,6 +1424,110 @@ def _run_batch(hb, device, smooth, fuse_gains, outputs, sm_pos):
     nsteps = hb.nsteps.copy()
     out["status"], out["nsteps"] = (status, nsteps) if inv is None else (status[inv], nsteps[inv])
     return out, db
+
+
+@dataclasses.dataclass
+class LogLikelihood:
+    """Innovation log-likelihood of a forward pass per track (include/ste.h: ste_ukf_loglik_f64).  ``loglik``: sum over the
+    track's updates of l_u = -1/2 (y^T S^+ y + sum log lambda_i + r log 2 pi) (DESIGN.md, "Innovation log-likelihood");
+    ``dof``: sum of the ranks r; ``nupd``: updates summed; ``status``: the pass's STE_STATUS_* bits; ``nis``: y^T S^+ y per
+    history row, or None.  From ``log_likelihood_grid`` every array has a leading candidate axis."""
+
+    loglik: np.ndarray
+    dof: np.ndarray
+    nupd: np.ndarray
+    status: np.ndarray
+    nis: Optional[np.ndarray] = None
+
+
+def log_likelihood_grid(hb: HostBatch, candidates: Sequence, device="cuda:0", nis: bool = False) -> LogLikelihood:
+    """
+    Score candidate noise models on the device: one forward pass that writes no histories per (Q, R) pair of
+    ``candidates``, over every track of ``hb`` (uploaded once).  Each pair is checked like ``pack_tracks`` checks its
+    matrices (4 x 4, symmetric); the rest of the filter (H, P0, flags, recorded noise) is the HostBatch's.  A candidate
+    whose R leaves the closed-form structure (H = diag(1, 1, 0, 0), R confined to the leading 2 x 2 block) takes the
+    general update route.  Returns a ``LogLikelihood`` whose arrays are [K, B] (``nis``: [K, B, Nmax+1]), tracks in the
+    HostBatch's slot order.  ``best_noise`` picks from it.
+    """
+    import torch
+
+    cands = [(_as44(Q, "Q", True), _as44(R, "R", True)) for Q, R in candidates]
+    if not cands:
+        raise ValueError("no candidates")
+    db = DeviceBatch(hb, device=device, alloc_smoothed=False, fuse_gains=False, histories=False)
+    K, B, N = len(cands), hb.B, hb.Nmax
+    dev = dict(device=db.device)
+    ll = torch.empty((K, B), dtype=torch.float64, **dev)
+    dof = torch.empty((K, B), dtype=torch.int32, **dev)
+    nupd = torch.empty((K, B), dtype=torch.int32, **dev)
+    status = torch.empty((K, B), dtype=torch.int32, **dev)
+    nis_t = torch.full((K, N + 1, B), float("nan"), dtype=torch.float64, **dev) if nis else None
+    _launch_loglik_grid(db, cands, ll, dof, nupd, status, nis_t)
+    return LogLikelihood(loglik=ll.cpu().numpy(), dof=dof.cpu().numpy(), nupd=nupd.cpu().numpy(),
+                         status=status.cpu().numpy(),
+                         nis=None if nis_t is None else nis_t.permute(0, 2, 1).cpu().numpy())
+
+
+# Streams the candidates of a grid are spread over.  A likelihood-only pass is one wave per 64 tracks for the whole pass, so
+# a 10 000-track batch is 157 waves on 1 024 SIMDs: candidates on separate streams run side by side.  Four: the hardware
+# queues a process opens by default.
+GRID_STREAMS = 4
+
+
+def _launch_loglik_grid(db: DeviceBatch, cands, ll, dof, nupd, status, nis_t=None, streams=None):
+    """One likelihood-only launch per candidate (Q, R) of ``cands`` on ``db`` (a ``histories=False`` batch), candidate k
+    writing row k of the [K, B] tensors (``nis_t``: [K, Nmax+1, B]); launches go round-robin over ``streams`` (default:
+    ``GRID_STREAMS`` new ones), which wait for the batch's upload, and the current stream waits for all of them."""
+    torch = db.torch
+    cur = torch.cuda.current_stream(db.device)
+    if streams is None:
+        streams = [torch.cuda.Stream(db.device) for _ in range(min(len(cands), GRID_STREAMS))]
+    for st in streams:
+        st.wait_event(db._uploaded)
+        st.wait_stream(cur)  # the output tensors were allocated / filled on the current stream
+    s = binding.SteUkfBatchF64.from_buffer_copy(db.struct)
+    s.flags = (s.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
+    for k, (Q, R) in enumerate(cands):  # Q and R are host pointers, read at call time: `cands` holds them
+        s.Q, s.R = Q.ctypes.data, R.ctypes.data
+        s.status = status[k].data_ptr()
+        lk = binding.SteUkfLoglikF64(ll[k].data_ptr(), dof[k].data_ptr(), nupd[k].data_ptr(),
+                                     None if nis_t is None else nis_t[k].data_ptr())
+        binding.check(db.lib.ste_ukf_forward_loglik_f64(C.byref(s), C.byref(lk), db._stream(streams[k % len(streams)])),
+                      "ste_ukf_forward_loglik_f64")
+    for st in streams:
+        cur.wait_stream(st)
+
+
+@dataclasses.dataclass
+class NoiseChoice:
+    """``best_noise``'s answer.  Fleet: ``index`` is the candidate with the largest fleet-summed loglik (-1, with NaN sums,
+    when every track was left out), ``loglik`` the [K] sums, ``excluded`` the number of tracks left out of every sum.  Per track: ``index`` [B] (-1 where no candidate gave a
+    usable value), ``loglik`` [B] the chosen values, ``excluded`` the number of tracks without any."""
+
+    index: object
+    loglik: np.ndarray
+    excluded: int
+
+
+def best_noise(grid: LogLikelihood, per_track: bool = False) -> NoiseChoice:
+    """The candidate of ``log_likelihood_grid`` with the largest log-likelihood, summed over the fleet or per track.  A
+    (candidate, track) value is unusable when the track's status carries STE_STATUS_NAN or its loglik is not finite.  For
+    the fleet sum a track is left out of every candidate's sum if any candidate's value for it is unusable -- otherwise a
+    candidate would gain by losing tracks --; ``excluded`` says how many were left out."""
+    ll = np.asarray(grid.loglik, dtype=np.float64)
+    ok = np.isfinite(ll) & ((np.asarray(grid.status) & binding.STE_STATUS_NAN) == 0)
+    if per_track:
+        masked = np.where(ok, ll, -np.inf)
+        idx = np.argmax(masked, axis=0)
+        none = ~ok.any(axis=0)
+        idx = np.where(none, -1, idx)
+        return NoiseChoice(index=idx, loglik=np.where(none, np.nan, masked[np.maximum(idx, 0), np.arange(ll.shape[1])]),
+                           excluded=int(none.sum()))
+    keep = ok.all(axis=0)
+    if not keep.any():  # nothing to compare: no candidate wins
+        return NoiseChoice(index=-1, loglik=np.full(ll.shape[0], np.nan), excluded=int(keep.size))
+    sums = np.where(keep[None, :], ll, 0.0).sum(axis=1)
+    return NoiseChoice(index=int(np.argmax(sums)), loglik=sums, excluded=int((~keep).sum()))
 
 
 def fleet_windows(ntracks: int, chunk: int):
