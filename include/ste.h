@@ -45,7 +45,8 @@ extern "C" {
 
 #define STE_VERSION 340 /* 0.3.4: posterior covariance on the GP path (ste_gp_predict_cov_f64).  Unnumbered addition:
                            the innovation log-likelihood of the forward pass (ste_ukf_loglik_f64,
-                           ste_ukf_forward_loglik_f64).
+                           ste_ukf_forward_loglik_f64).  Unnumbered addition: the posterior of the time derivative on the
+                           GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -459,6 +460,32 @@ int ste_gp_predict_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m
  */
 int ste_gp_predict_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
                            double* W, double* mean, double* cov, void* stream);
+
+/*
+ * Posterior of the time derivative f'(t) of the latent function (the velocity of a track: deg/h for lon / lat against
+ * hours) at m[b] new inputs xs [B][mmax].  The derivative of a GP is a GP; with c, l, s = exp(theta), d = (t - x) / l and
+ * k(t, x) = c kappa(d) for the batch's kernel function:
+ *   kind        kappa'(d)                                         q = -kappa''(0)   -kappa''(d)
+ *   RBF         -d exp(-d^2/2)                                    1                 (1 - d^2) exp(-d^2/2)
+ *   MATERN32    -3 d exp(-sqrt(3) |d|)                            3                 3 (1 - sqrt(3) |d|) exp(-sqrt(3) |d|)
+ *   MATERN52    -(5/3) d (1 + sqrt(5) |d|) exp(-sqrt(5) |d|)      5/3               (5/3) (1 + sqrt(5) |d| - 5 d^2) exp(-sqrt(5) |d|)
+ *   MATERN12    not differentiable: refused with STE_EINVAL
+ *   K'*[j][i] = (c / l) kappa'((xs_j - x_i) / l)      (0 in padding columns i >= n[b] and rows j >= m[b], as Kstar)
+ *   dmean     = K'* alpha                              [B][nout][mmax], per output
+ *   dvar_j    = c q / l^2 - (K'* K^-1 K'*^T)_jj       [B][mmax]
+ *   dcov_ij   = (c / l^2) (-kappa''((xs_i - xs_j) / l)) - (K'* K^-1 K'*^T)_ij
+ * This is the latent derivative: the WhiteKernel adds nothing (no + s, unlike the position variance).
+ * Layouts, workspaces and preconditions are those of ste_gp_predict_f64 / ste_gp_predict_cov_f64 (Kinv and alpha from a
+ * preceding ste_gp_lml_f64; Kstar and W are the same workspaces and hold K'* and K'* K^-1 afterwards).  Rows >= m[b] of
+ * dmean and dvar are not written; every element of a track's [mmax][mmax] block of dcov is written, both triangles
+ * mirrored bit for bit, 0 outside [0, m[b])^2.  The two calls' dmean agree bit for bit, and per-track results do not
+ * depend on the other tracks of the batch.  Every argument the position calls refuse, and kernel == MATERN12, is refused
+ * with STE_EINVAL before any launch.
+ */
+int ste_gp_predict_deriv_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
+                             double* dmean, double* dvar, void* stream);
+int ste_gp_predict_deriv_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs,
+                                 double* Kstar, double* W, double* dmean, double* dcov, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Observation preparation: speed / course over ground and their rates for a batch of tracks, the

@@ -18,6 +18,8 @@
 //   gp_alpha / gp_finish   per-block shares of y.alpha, log det, alpha.alpha -> log-marginal likelihood, gradient assembly
 //   gp_kstar / gp_predict   posterior mean and variance at new times (variance as a tile GEMM against K^-1)
 //   gp_pcov_w / gp_pcov     posterior covariance: W = Kstar K^-1, then Kss + s I - W Kstar^T on the lower tiles, mirrored
+//   gp_predict_deriv        posterior of the time derivative (velocity): gp_kstar / gp_pcov_w / gp_pcov again, with the
+//                  derivative element functors (KernD1, KernD2) in place of the kernel function
 //
 // All dense work is 64x64-tile "NT" products C += A_rows * B_rows^T with both operands row-major and contiguous along
 // the contraction index, issued as v_mfma_f64_16x16x4_f64: lane l feeds A[row l&15][k = l>>4] and B[col l&15][k = l>>4]
@@ -75,13 +77,19 @@ struct GpParams {
 // element of K (gp_kbuild, gp_potrf_cols<F>, gp_kstar) calls value(env(c, d), d), so the in-place build and the
 // stand-alone build are one expression.
 // ---------------------------------------------------------------------------------------------------------------
-struct KernRbf {  // c exp(-d^2/2);  dk/dlog l = c d^2 exp(-d^2/2)
+// What the element sites (gp_kstar, gp_pcov) scale the function by, given c and 1/l, and whether the WhiteKernel's s belongs
+// on the diagonal: c and yes for the kernel functions; the derivative functors (KernD1, KernD2, after gp_pcov) override both.
+struct KernScale {
+    __device__ static __forceinline__ double amp(double c, double) { return c; }
+    static constexpr bool kWhite = true;
+};
+struct KernRbf : KernScale {  // c exp(-d^2/2);  dk/dlog l = c d^2 exp(-d^2/2)
     static constexpr int kind = STE_GP_KERNEL_RBF;
     __device__ static __forceinline__ double env(double c, double d) { return c * exp(-0.5 * (d * d)); }
     __device__ static __forceinline__ double value(double e, double) { return e; }
     __device__ static __forceinline__ double dlogl(double d) { return d * d; }
 };
-struct KernMatern12 {  // c exp(-|d|);  dk/dlog l = c |d| exp(-|d|)
+struct KernMatern12 : KernScale {  // c exp(-|d|);  dk/dlog l = c |d| exp(-|d|)
     static constexpr int kind = STE_GP_KERNEL_MATERN12;
     __device__ static __forceinline__ double env(double c, double d) { return c * exp(-fabs(d)); }
     __device__ static __forceinline__ double value(double e, double) { return e; }
@@ -90,13 +98,13 @@ struct KernMatern12 {  // c exp(-|d|);  dk/dlog l = c |d| exp(-|d|)
 // (the polynomials are written as explicit fma: nothing is left for -ffp-contract to fuse one way in one kernel and another
 //  way in the next, so every call site gets the same bits)
 constexpr double kSqrt3 = 1.7320508075688772, kSqrt5 = 2.23606797749979;
-struct KernMatern32 {  // c (1 + sqrt3 |d|) exp(-sqrt3 |d|);  dk/dlog l = c 3 d^2 exp(-sqrt3 |d|)
+struct KernMatern32 : KernScale {  // c (1 + sqrt3 |d|) exp(-sqrt3 |d|);  dk/dlog l = c 3 d^2 exp(-sqrt3 |d|)
     static constexpr int kind = STE_GP_KERNEL_MATERN32;
     __device__ static __forceinline__ double env(double c, double d) { return c * exp(-kSqrt3 * fabs(d)); }
     __device__ static __forceinline__ double value(double e, double d) { return e * fma(kSqrt3, fabs(d), 1.0); }
     __device__ static __forceinline__ double dlogl(double d) { return 3.0 * (d * d); }
 };
-struct KernMatern52 {  // c (1 + sqrt5 |d| + 5 d^2/3) exp(-sqrt5 |d|);  dk/dlog l = c (5/3) d^2 (1 + sqrt5 |d|) exp(-sqrt5 |d|)
+struct KernMatern52 : KernScale {  // c (1 + sqrt5 |d| + 5 d^2/3) exp(-sqrt5 |d|);  dk/dlog l = c (5/3) d^2 (1 + sqrt5 |d|) exp(-sqrt5 |d|)
     static constexpr int kind = STE_GP_KERNEL_MATERN52;
     __device__ static __forceinline__ double env(double c, double d) { return c * exp(-kSqrt5 * fabs(d)); }
     __device__ static __forceinline__ double value(double e, double d) {
@@ -1359,7 +1367,8 @@ __global__ __launch_bounds__(256) void gp_kstar(const GpParams p, const GpPredic
     const int b = blockIdx.y, mt = blockIdx.x;
     const int n = p.n[b], m = q.m[b];
     if (mt * T >= ((m + T - 1) / T) * T) return;
-    const double c = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]);
+    const double c0 = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]);
+    const double c = F::amp(c0, inv_l);  // c, or c / l for the derivative (KernD1)
     const double* x = p.x + (size_t)b * p.nmax;
     const double* xs = q.xs + (size_t)b * q.mmax;
     double* Ks = q.Kstar + (size_t)b * q.mb_max * T * q.ldk;
@@ -1472,14 +1481,15 @@ __global__ __launch_bounds__(256) void gp_pcov(const GpParams p, const GpPredict
         v4d acc[2][2];
         zero_acc(acc);
         wave_gemm_nt(acc, W + (size_t)(ti * T + wr) * q.ldk, q.ldk, Ks + (size_t)(tj * T + wc) * q.ldk, q.ldk, 0, nb * T, lane);
-        const double c = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]), s = exp(p.theta[b * 3 + 2]);
+        const double c0 = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]), s = exp(p.theta[b * 3 + 2]);
+        const double c = F::amp(c0, inv_l);  // c, or c / l^2 for the derivative (KernD2)
         const double* xs = q.xs + (size_t)b * q.mmax;
         for_each_acc(acc, wave, lane, [&](int r, int cc, double v) {
             const int gi = ti * T + r, gj = tj * T + cc;
             double out = 0.0;
             if (gi < m && gj < m) {
                 double kss = kernel_value<F>(c, (xs[gi] - xs[gj]) * inv_l);
-                if (gi == gj) kss += s;  // WhiteKernel: on the diagonal only
+                if (F::kWhite && gi == gj) kss += s;  // WhiteKernel: on the diagonal only (not on the latent derivative)
                 out = kss - v;
             }
             S[r * LD + cc] = out;
@@ -1497,6 +1507,117 @@ __global__ __launch_bounds__(256) void gp_pcov(const GpParams p, const GpPredict
         const int r = e / T, cc = e % T, gi = tj * T + r, gj = ti * T + cc;
         if (gi < q.mmax && gj < q.mmax && (ti > tj || cc >= r)) cov[(size_t)gi * mm + gj] = live ? S[cc * LD + r] : 0.0;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Posterior of the time derivative f'(t) (the latent velocity; include/ste.h, ste_gp_predict_deriv_f64).  With
+// k(t, x) = c kappa(d), d = (t - x) / l:
+//   cov(f'(t), y_i)    = d k / dt         = (c / l)   kappa'(d)          KernD1: the elements of K'* (gp_kstar<KernD1<K>>)
+//   cov(f'(t), f'(t')) = d^2 k / dt dt'   = (c / l^2) (-kappa''(d))      KernD2: the prior of gp_pcov<KernD2<K>> and of
+//                                                                                gp_predict_deriv, no WhiteKernel term
+// dmean = K'* alpha (predict_mean), dvar = c q / l^2 - (K'* K^-1 K'*^T)_jj with q = -kappa''(0), dcov likewise with the
+// whole KernD2 matrix.  Each functor shares its exponential with the kernel function's env; Matern 1/2 is not
+// differentiable at d = 0 and has none (the C ABI refuses it).
+// ---------------------------------------------------------------------------------------------------------------
+template <typename K>
+struct KernD1;
+template <typename K>
+struct KernD2;
+template <typename K>
+struct KernDeriv {
+    static constexpr int kind = K::kind;
+    static constexpr bool kWhite = false;
+    __device__ static __forceinline__ double env(double c, double d) { return K::env(c, d); }
+};
+template <>
+struct KernD1<KernRbf> : KernDeriv<KernRbf> {  // kappa' = -d exp(-d^2/2)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) { return -d * e; }
+};
+template <>
+struct KernD2<KernRbf> : KernDeriv<KernRbf> {  // -kappa'' = (1 - d^2) exp(-d^2/2)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) { return e * fma(-d, d, 1.0); }
+};
+template <>
+struct KernD1<KernMatern32> : KernDeriv<KernMatern32> {  // kappa' = -3 d exp(-sqrt3 |d|)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) { return (-3.0 * d) * e; }
+};
+template <>
+struct KernD2<KernMatern32> : KernDeriv<KernMatern32> {  // -kappa'' = 3 (1 - sqrt3 |d|) exp(-sqrt3 |d|)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) { return e * (3.0 * fma(-kSqrt3, fabs(d), 1.0)); }
+};
+template <>
+struct KernD1<KernMatern52> : KernDeriv<KernMatern52> {  // kappa' = -(5/3) d (1 + sqrt5 |d|) exp(-sqrt5 |d|)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) {
+        return ((-5.0 / 3.0) * d) * fma(kSqrt5, fabs(d), 1.0) * e;
+    }
+};
+template <>
+struct KernD2<KernMatern52> : KernDeriv<KernMatern52> {  // -kappa'' = (5/3) (1 + sqrt5 |d| - 5 d^2) exp(-sqrt5 |d|)
+    __device__ static __forceinline__ double amp(double c, double inv_l) { return c * inv_l * inv_l; }
+    __device__ static __forceinline__ double value(double e, double d) {
+        const double a = kSqrt5 * fabs(d);
+        return e * ((5.0 / 3.0) * fma(a, 1.0 - a, 1.0));  // 1 + a (1 - a), a^2 = 5 d^2
+    }
+};
+
+// gp_predict with the derivative's prior: dvar = c q / l^2 - rowsum, the value gp_pcov<F> puts on dcov's diagonal before
+// its GEMM term (kernel_value<F> at d = 0); the mean rows are K'* alpha.  This is gp_predict's text with only the prior
+// changed, not a body the two kernels share: moved into a function that both inline, gp_predict compiles to different code
+// (hipcc hoists its kernel-argument loads differently), and the position path's code is to stay as it is.
+template <typename F>
+__global__ __launch_bounds__(256) void gp_predict_deriv(const GpParams p, const GpPredict q) {
+    __shared__ double rowsum[T][2];
+    const int b = blockIdx.y, mt = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = p.n[b], m = q.m[b], nb = nblocks(n);
+    if (mt * T >= m) return;
+    const size_t ld = p.ld;
+    const double* Ks = q.Kstar + (size_t)b * q.mb_max * T * q.ldk;
+    const double* Kinv = q.Kinv + (size_t)b * ld * ld;
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+    double part[8];  // per-lane partial of sum_i W[m][i] Kstar[m][i] for the 8 rows this lane touches (2 m-blocks x 4 regs)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[e] = 0.0;
+    for (int it = 0; it < nb; ++it) {
+        v4d acc[2][2];
+        zero_acc(acc);
+        wave_gemm_nt(acc, Ks + (size_t)(mt * T + wr) * q.ldk, q.ldk, Kinv + (size_t)(it * T + wc) * ld, ld, 0, nb * T, lane);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = wr + 16 * mi + (lane >> 4) + 4 * e, c = wc + 16 * ni + (lane & 15);
+                    part[mi * 4 + e] += acc[mi][ni][e] * Ks[(size_t)(mt * T + r) * q.ldk + it * T + c];
+                }
+    }
+    // reduce over the 16 lanes that share a row (lane & 15), then over the two waves that share the row block
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        double t = part[e];
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        part[e] = t;
+    }
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rowsum[wr + 16 * mi + (lane >> 4) + 4 * e][wave & 1] = part[mi * 4 + e];
+    }
+    __syncthreads();
+    const double c0 = exp(p.theta[b * 3 + 0]), inv_l = exp(-p.theta[b * 3 + 1]);
+    const double prior = kernel_value<F>(F::amp(c0, inv_l), 0.0);  // c q / l^2
+    if (tid < T) {
+        const int gm = mt * T + tid;
+        if (gm < m) q.var[(size_t)b * q.mmax + gm] = prior - (rowsum[tid][0] + rowsum[tid][1]);
+    }
+    predict_mean(p, q, b, mt, wave, lane);
 }
 
 }  // namespace stegp
@@ -1560,6 +1681,39 @@ void with_kernel(int kind, Fn&& fn) {
         case STE_GP_KERNEL_MATERN32: fn(stegp::KernMatern32{}); break;
         default: fn(stegp::KernMatern52{}); break;  // (gp_params has refused any other value)
     }
+}
+// Matern 1/2 has no derivative at d = 0: the derivative calls refuse it with the other argument errors, before any launch
+int gp_deriv_kernel(const stegp::GpParams& p) {
+    if (p.kernel == STE_GP_KERNEL_MATERN12)
+        return gp_fail("kernel STE_GP_KERNEL_MATERN12 (Matern nu = 1/2) is not differentiable: no derivative prediction");
+    return STE_OK;
+}
+// the same for the kernels that have a derivative (gp_deriv_kernel has refused Matern 1/2)
+template <typename Fn>
+void with_deriv_kernel(int kind, Fn&& fn) {
+    switch (kind) {
+        case STE_GP_KERNEL_RBF: fn(stegp::KernRbf{}); break;
+        case STE_GP_KERNEL_MATERN32: fn(stegp::KernMatern32{}); break;
+        default: fn(stegp::KernMatern52{}); break;
+    }
+}
+// the query side of a predict call (every pointer checked by the caller)
+stegp::GpPredict gp_predict_args(const stegp::GpParams& p, const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m,
+                                 const double* xs, double* Kstar, double* W, double* mean, double* var, double* cov) {
+    stegp::GpPredict q;
+    q.B = p.B;
+    q.mmax = mmax;
+    q.mb_max = (mmax + 63) / 64;
+    q.ldk = p.ld;
+    q.m = m;
+    q.xs = xs;
+    q.Kstar = Kstar;
+    q.Kinv = b->Kinv;
+    q.mean = mean;
+    q.var = var;
+    q.W = W;
+    q.cov = cov;
+    return q;
 }
 }  // namespace
 
@@ -1635,19 +1789,7 @@ int ste_gp_predict_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m
     if (rc) return rc;
     if (mmax <= 0 || !m || !xs || !Kstar || !mean || !var || !b->Kinv)
         return gp_fail("mmax > 0, m, xs, Kstar, mean, var and batch.Kinv are required (run ste_gp_lml_f64 with Kinv set first)");
-    stegp::GpPredict q;
-    q.B = p.B;
-    q.mmax = mmax;
-    q.mb_max = (mmax + 63) / 64;
-    q.ldk = p.ld;
-    q.m = m;
-    q.xs = xs;
-    q.Kstar = Kstar;
-    q.Kinv = b->Kinv;
-    q.mean = mean;
-    q.var = var;
-    q.W = nullptr;
-    q.cov = nullptr;
+    const stegp::GpPredict q = gp_predict_args(p, b, mmax, m, xs, Kstar, nullptr, mean, var, nullptr);
     hipStream_t s = (hipStream_t)stream;
     with_kernel(p.kernel, [&](auto f) { hipLaunchKernelGGL(stegp::gp_kstar<decltype(f)>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q); });
     hipLaunchKernelGGL(stegp::gp_predict, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
@@ -1662,19 +1804,7 @@ int ste_gp_predict_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_
     if (mmax <= 0) return gp_fail("mmax must be > 0");
     if (!m || !xs || !Kstar || !W || !mean || !cov || !b->Kinv)
         return gp_fail("m, xs, Kstar, W, mean, cov and batch.Kinv are required (run ste_gp_lml_f64 with Kinv set first)");
-    stegp::GpPredict q;
-    q.B = p.B;
-    q.mmax = mmax;
-    q.mb_max = (mmax + 63) / 64;
-    q.ldk = p.ld;
-    q.m = m;
-    q.xs = xs;
-    q.Kstar = Kstar;
-    q.Kinv = b->Kinv;
-    q.mean = mean;
-    q.var = nullptr;
-    q.W = W;
-    q.cov = cov;
+    const stegp::GpPredict q = gp_predict_args(p, b, mmax, m, xs, Kstar, W, mean, nullptr, cov);
     hipStream_t s = (hipStream_t)stream;
     const unsigned wtiles = (unsigned)(q.mb_max * p.nb_max), ctiles = (unsigned)(q.mb_max * (q.mb_max + 1) / 2);
     with_kernel(p.kernel, [&](auto f) {
@@ -1683,6 +1813,47 @@ int ste_gp_predict_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_
         hipLaunchKernelGGL(stegp::gp_pcov<decltype(f)>, dim3(ctiles, p.B), dim3(256), 0, s, p, q);
     });
     return gp_hip(hipGetLastError(), "gp_pcov launch");
+}
+
+// The derivative calls: the position calls' launches with KernD1<K> in gp_kstar (K'* in the Kstar workspace) and KernD2<K>
+// in the prior (gp_predict_deriv, gp_pcov).
+int ste_gp_predict_deriv_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs, double* Kstar,
+                             double* dmean, double* dvar, void* stream) {
+    stegp::GpParams p;
+    int rc = gp_params(b, &p);
+    if (rc) return rc;
+    if ((rc = gp_deriv_kernel(p))) return rc;
+    if (mmax <= 0 || !m || !xs || !Kstar || !dmean || !dvar || !b->Kinv)
+        return gp_fail("mmax > 0, m, xs, Kstar, dmean, dvar and batch.Kinv are required (run ste_gp_lml_f64 with Kinv set first)");
+    const stegp::GpPredict q = gp_predict_args(p, b, mmax, m, xs, Kstar, nullptr, dmean, dvar, nullptr);
+    hipStream_t s = (hipStream_t)stream;
+    with_deriv_kernel(p.kernel, [&](auto f) {
+        using K = decltype(f);
+        hipLaunchKernelGGL(stegp::gp_kstar<stegp::KernD1<K>>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
+        hipLaunchKernelGGL(stegp::gp_predict_deriv<stegp::KernD2<K>>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
+    });
+    return gp_hip(hipGetLastError(), "gp_predict_deriv launch");
+}
+
+int ste_gp_predict_deriv_cov_f64(const ste_gp_batch_f64* b, int32_t mmax, const int32_t* m, const double* xs,
+                                 double* Kstar, double* W, double* dmean, double* dcov, void* stream) {
+    stegp::GpParams p;
+    int rc = gp_params(b, &p);
+    if (rc) return rc;
+    if ((rc = gp_deriv_kernel(p))) return rc;
+    if (mmax <= 0) return gp_fail("mmax must be > 0");
+    if (!m || !xs || !Kstar || !W || !dmean || !dcov || !b->Kinv)
+        return gp_fail("m, xs, Kstar, W, dmean, dcov and batch.Kinv are required (run ste_gp_lml_f64 with Kinv set first)");
+    const stegp::GpPredict q = gp_predict_args(p, b, mmax, m, xs, Kstar, W, dmean, nullptr, dcov);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned wtiles = (unsigned)(q.mb_max * p.nb_max), ctiles = (unsigned)(q.mb_max * (q.mb_max + 1) / 2);
+    with_deriv_kernel(p.kernel, [&](auto f) {
+        using K = decltype(f);
+        hipLaunchKernelGGL(stegp::gp_kstar<stegp::KernD1<K>>, dim3(q.mb_max, p.B), dim3(256), 0, s, p, q);
+        hipLaunchKernelGGL(stegp::gp_pcov_w, dim3(wtiles, p.B), dim3(256), 0, s, p, q);
+        hipLaunchKernelGGL(stegp::gp_pcov<stegp::KernD2<K>>, dim3(ctiles, p.B), dim3(256), 0, s, p, q);
+    });
+    return gp_hip(hipGetLastError(), "gp_pcov (derivative) launch");
 }
 
 }  // extern "C"

@@ -149,6 +149,28 @@ class GpDeviceBatch:
         (mean (m_b, nout), cov (m_b, m_b)) per track instead (``ste_gp_predict_cov_f64``; cost:
         ``predict_cov_bytes_per_track``, a MemoryError names it when the device cannot hold it)."""
         torch = self.torch
+        m, mmax, t_m, t_xs, t_ks = self._queries(thetas, xq, return_cov)
+        if return_cov:
+            return self._predict_cov(m, mmax, t_m, t_xs, t_ks)
+        t_mean = torch.zeros((self.B, self.nout, mmax), dtype=torch.float64, device=self.device)
+        t_var = torch.zeros((self.B, mmax), dtype=torch.float64, device=self.device)
+        binding.check(self.lib.ste_gp_predict_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
+                                                  t_ks.data_ptr(), t_mean.data_ptr(), t_var.data_ptr(), self._stream()),
+                      "ste_gp_predict_f64")
+        mean = t_mean.cpu().numpy()
+        var = t_var.cpu().numpy()
+        out = []
+        for b in range(self.B):
+            v = var[b, : m[b]]
+            v = np.where(v < 0, 0.0, v)  # GaussianProcessRegressor.predict clips negative variances to 0
+            std = np.sqrt(v)
+            out.append((mean[b, :, : m[b]].T.copy(), np.repeat(std[:, None], self.nout, axis=1)))
+        return out
+
+    def _queries(self, thetas, xq, return_cov):
+        """K^-1 and alpha at ``thetas``, then the query side of a predict call on the device: (m, mmax, t_m, t_xs, t_ks).
+        With ``return_cov`` the MemoryError check comes first."""
+        torch = self.torch
         m = np.array([len(q) for q in xq], dtype=np.int32)
         mmax = int(m.max())
         mb = (mmax + 63) // 64
@@ -166,21 +188,41 @@ class GpDeviceBatch:
         t_m = torch.from_numpy(m).to(self.device)
         t_xs = torch.from_numpy(xs).to(self.device)
         t_ks = torch.empty((self.B, mb * 64, self.ld), dtype=torch.float64, device=self.device)
+        return m, mmax, t_m, t_xs, t_ks
+
+    def predict_derivative(self, thetas, xq: Sequence[np.ndarray], return_cov: bool = False):
+        """Posterior of the time derivative of the latent function per track at query inputs xq[b]: (dmean (m_b, nout),
+        dstd (m_b, nout)) in units of y per unit x (``ste_gp_predict_deriv_f64``); with ``return_cov`` (dmean (m_b, nout),
+        dcov (m_b, m_b)) (``ste_gp_predict_deriv_cov_f64``, same cost and MemoryError as ``predict(return_cov=True)``).
+        The WhiteKernel's noise is not part of it.  A Matern nu = 1/2 batch raises ValueError: that kernel has no
+        derivative."""
+        if self.kernel == binding.STE_GP_KERNEL_MATERN12:
+            raise ValueError("the Matern nu = 1/2 kernel is not differentiable: it has no derivative prediction")
+        torch = self.torch
+        m, mmax, t_m, t_xs, t_ks = self._queries(thetas, xq, return_cov)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        t_dmean = torch.zeros((self.B, self.nout, mmax), **f64)
         if return_cov:
-            return self._predict_cov(m, mmax, t_m, t_xs, t_ks)
-        t_mean = torch.zeros((self.B, self.nout, mmax), dtype=torch.float64, device=self.device)
-        t_var = torch.zeros((self.B, mmax), dtype=torch.float64, device=self.device)
-        binding.check(self.lib.ste_gp_predict_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
-                                                  t_ks.data_ptr(), t_mean.data_ptr(), t_var.data_ptr(), self._stream()),
-                      "ste_gp_predict_f64")
-        mean = t_mean.cpu().numpy()
-        var = t_var.cpu().numpy()
+            t_w = torch.empty_like(t_ks)
+            t_dcov = torch.empty((self.B, mmax, mmax), **f64)  # (every element is written)
+            binding.check(self.lib.ste_gp_predict_deriv_cov_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
+                                                                t_ks.data_ptr(), t_w.data_ptr(), t_dmean.data_ptr(),
+                                                                t_dcov.data_ptr(), self._stream()),
+                          "ste_gp_predict_deriv_cov_f64")
+            del t_w, t_ks
+            dmean = t_dmean.cpu().numpy()
+            return [(dmean[b, :, : m[b]].T.copy(), t_dcov[b, : m[b], : m[b]].cpu().numpy()) for b in range(self.B)]
+        t_dvar = torch.zeros((self.B, mmax), **f64)
+        binding.check(self.lib.ste_gp_predict_deriv_f64(C.byref(self.struct), mmax, t_m.data_ptr(), t_xs.data_ptr(),
+                                                        t_ks.data_ptr(), t_dmean.data_ptr(), t_dvar.data_ptr(), self._stream()),
+                      "ste_gp_predict_deriv_f64")
+        dmean = t_dmean.cpu().numpy()
+        dvar = t_dvar.cpu().numpy()
         out = []
         for b in range(self.B):
-            v = var[b, : m[b]]
-            v = np.where(v < 0, 0.0, v)  # GaussianProcessRegressor.predict clips negative variances to 0
-            std = np.sqrt(v)
-            out.append((mean[b, :, : m[b]].T.copy(), np.repeat(std[:, None], self.nout, axis=1)))
+            v = dvar[b, : m[b]]
+            dstd = np.sqrt(np.where(v < 0, 0.0, v))  # negative variances clipped to 0, as predict does
+            out.append((dmean[b, :, : m[b]].T.copy(), np.repeat(dstd[:, None], self.nout, axis=1)))
         return out
 
     def _predict_cov(self, m, mmax, t_m, t_xs, t_ks):

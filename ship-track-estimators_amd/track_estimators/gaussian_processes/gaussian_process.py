@@ -18,6 +18,10 @@ computed on the device (``ste_gp_predict_cov_f64``), the draws of ``sample_y`` o
 Additive extra: ``fit_batch`` / ``predict_batch`` fit many tracks at once, advancing all their optimisers in lock-step so
 that each objective evaluation is one batched launch (the reference loops over ships in Python,
 examples/example_gaussian_process_batch.py:19).
+
+Additive extra: the posterior of the time derivative -- the velocity of a track, in deg/h -- on the device
+(``predict_derivative``, ``GPRegression.predict_velocity`` / ``predict_velocity_batch``), and speed and course over ground
+derived from it (``predict_sog_cog``, ``velocity_to_sog_cog``).  scikit-learn has no counterpart.
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import scipy.optimize
 
+from ..constants import EARTH_RADIUS
 from ..ship_track import ShipTrack
 from .._hip import binding
 from .device import GpDeviceBatch
@@ -223,6 +228,24 @@ def _undo_normalization(mean, std_or_cov, y_mean, y_std, cov):
     return mean, std_or_cov * y_std
 
 
+def velocity_to_sog_cog(lat_deg, dlon, dlat):
+    """Speed over ground (km/h) and course over ground (degrees in [0, 360)) of a velocity (dlon, dlat) in deg/h at latitude
+    ``lat_deg``, on the sphere of radius ``EARTH_RADIUS``: v_n = R rad(dlat), v_e = R cos(rad(lat)) rad(dlon),
+    sog = hypot(v_e, v_n), cog = atan2(v_e, v_n) in degrees, the convention of ``utils.heading`` (0 = north, 90 = east).
+
+    Given the posterior mean velocity this is the speed and course OF the mean velocity, not the posterior mean of the speed
+    (which is larger by an amount that grows with the velocity's variance), nor that of the course."""
+    lat = np.radians(np.asarray(lat_deg, dtype=np.float64))
+    v_n = EARTH_RADIUS * np.radians(np.asarray(dlat, dtype=np.float64))
+    v_e = EARTH_RADIUS * np.cos(lat) * np.radians(np.asarray(dlon, dtype=np.float64))
+    return np.hypot(v_e, v_n), (np.degrees(np.arctan2(v_e, v_n)) + 360) % 360
+
+
+def _refuse_matern12(kernel):
+    if _kernel_kind(kernel) == binding.STE_GP_KERNEL_MATERN12:
+        raise ValueError("the Matern nu = 0.5 kernel is not differentiable: it has no derivative prediction")
+
+
 def _check_random_state(seed):
     if seed is None or seed is np.random:
         return np.random.mtrand._rand
@@ -291,6 +314,26 @@ class DeviceGaussianProcessRegressor:
             mean, spread = mean[:, 0], spread[..., 0]
         return (mean, spread) if (return_std or return_cov) else mean
 
+    def predict_derivative(self, X, return_std=False, return_cov=False):
+        """Posterior of the derivative of the latent function with respect to the input, at X: the mean (m,) or (m, nout);
+        with ``return_std`` also its std of the same shape, with ``return_cov`` also its covariance (m, m) or (m, m, nout)
+        -- the shape conventions of ``predict`` (``ste_gp_predict_deriv_f64`` / ``ste_gp_predict_deriv_cov_f64``).  Units
+        are those of y per unit of X.  With ``normalize_y`` the result scales by y_std (covariances by y_std**2) with no
+        offset: the mean of y is a constant.  A Matern nu = 0.5 kernel raises ValueError before any device work (it is
+        not differentiable).  Not in scikit-learn."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
+        _refuse_matern12(self.kernel)
+        X = np.asarray(X, dtype=np.float64).reshape(-1)
+        dmean, spread = self._batch.predict_derivative(self.kernel_.theta[None], [X], return_cov=return_cov)[0]
+        if self.normalize_y:
+            dmean, spread = _undo_normalization(dmean, spread, 0.0, self._y_train_std, return_cov)
+        elif return_cov:
+            spread = np.repeat(spread[:, :, None], self.y_train_.shape[1], axis=2)
+        if self.y_train_.shape[1] == 1:
+            dmean, spread = dmean[:, 0], spread[..., 0]
+        return (dmean, spread) if (return_std or return_cov) else dmean
+
     def sample_y(self, X, n_samples=1, random_state=0):
         """Draws from the posterior at X: (m, n_samples) for one output, (m, nout, n_samples) for several.  scikit-learn's
         procedure: ``RandomState.multivariate_normal`` per output on the mean and covariance of
@@ -344,6 +387,21 @@ class GPRegression:
         predicted, std = self._model.predict(np.asarray(times).reshape(-1, 1), return_std=True)
         return predicted, std
 
+    # -- velocity (not in the reference) ------------------------------------------------------------------------
+    def predict_velocity(self, times: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Posterior mean and standard deviation of the velocity (d lon / dt, d lat / dt), each (m, 2), in deg/h at
+        ``times`` (hours since the first observation, as ``predict``).  Needs the default regressor."""
+        assert self._model is not None, "Model has not been fit yet."
+        return self._model.predict_derivative(np.asarray(times).reshape(-1, 1), return_std=True)
+
+    def predict_sog_cog(self, times: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Speed over ground (km/h) and course over ground (degrees in [0, 360)), each (m,), at ``times``: the posterior
+        mean velocity converted at the posterior mean latitude by ``velocity_to_sog_cog`` -- the speed of the mean
+        velocity, not the posterior mean of the speed."""
+        mean, _ = self.predict(times)
+        dmean, _ = self.predict_velocity(times)
+        return velocity_to_sog_cog(mean[:, 1], dmean[:, 0], dmean[:, 1])
+
     # -- batched extras (not in the reference) ------------------------------------------------------------------
     def fit_batch(self, ship_tracks: Sequence[ShipTrack], gpr_kwargs: Optional[Dict[str, Any]] = None):
         """Fit every track with the same kernel description; returns the fitted thetas (B, 3) and lml (B,)."""
@@ -375,4 +433,15 @@ class GPRegression:
             return [_undo_normalization(mean, spread, mu, sd, return_cov) for (mean, spread), (mu, sd) in zip(out, self._norm)]
         if return_cov:
             return [(mean, np.repeat(cov[:, :, None], self._batch.nout, axis=2)) for mean, cov in out]
+        return out
+
+    def predict_velocity_batch(self, times: Sequence[np.ndarray], return_cov: bool = False):
+        """[(dmean (m_b, 2), dstd (m_b, 2)) for every track] after ``fit_batch``: the velocity in deg/h as
+        ``predict_velocity`` gives it; with ``return_cov`` [(dmean (m_b, 2), dcov (m_b, m_b, 2))].  ``normalize_y`` is undone
+        per track (a scale by that track's y_std)."""
+        out = self._batch.predict_derivative(self._thetas, [np.asarray(t).reshape(-1) for t in times], return_cov=return_cov)
+        if self._norm is not None:
+            return [_undo_normalization(dm, spread, 0.0, sd, return_cov) for (dm, spread), (_, sd) in zip(out, self._norm)]
+        if return_cov:
+            return [(dm, np.repeat(dcov[:, :, None], self._batch.nout, axis=2)) for dm, dcov in out]
         return out
