@@ -235,6 +235,51 @@ typedef struct ste_ukf_loglik_f64 {
  * and whatever ste_ukf_forward_f64 refuses. */
 int ste_ukf_forward_loglik_f64(const ste_ukf_batch_f64* b, const ste_ukf_loglik_f64* l, void* stream);
 
+/*
+ * Per-track process and measurement noise.  In the reference every ship has a filter object of its own
+ * (UnscentedKalmanFilter(H=H, Q=Q, R=R, ...) inside the per-ship loop, examples/example_ukf_rts_smoother_batch.py:46-64,
+ * unscented.py:55-61), so Q and R are per-track quantities there; the batch struct carries one shared pair.  This struct
+ * travels beside it (an unnumbered addition, like ste_ukf_loglik_f64) and gives track t its own matrices:
+ *   - Track t of a window reads Q[e * track_stride + t] (R likewise): the pointers name the window's first track, like every
+ *     other per-track array.  Only the upper triangle exists, so the matrices are symmetric by construction.  b->H stays
+ *     shared; b->Q / b->R are still required and are what a NULL member falls back on.
+ *   - Route.  The closed-form update is taken when b->H == diag(1, 1, 0, 0) and R is confined to the leading 2 x 2 block: for a
+ *     shared R (nz->R NULL) as in the plain calls, from b->R; for a per-track R when STE_NOISE_R_BLOCK2 is set -- the library
+ *     cannot look into device memory before a launch, so this is the caller's promise (track_estimators.batch checks it when
+ *     it packs).  With the promise the kernels read entries 00, 01, 11 of R only.  Without it every track takes the general
+ *     4 x 4 route (where the pseudo-inverse's 2 x 2 shortcut is decided per track, not per wave, and taken only for an S
+ *     that is exactly confined to the block; a non-finite S goes the 4 x 4 way, as in a shared launch with a general R).
+ *   - The result for a track is the result of the plain call on a batch whose shared Q / R are that track's matrices, bit for
+ *     bit, given the same route, the lane-per-track mapping and the same flags / tuning: histories, rts_work, status, sm_mean,
+ *     sm_cov, sm_pos, and loglik / dof / nupd / nis.  A track's results do not depend on the other tracks' matrices.
+ *   - Accepted: everything ste_ukf_forward_loglik_f64 accepts (recorded noise, STE_FLAG_ROBUST, STE_FLAG_NO_INITIAL_UPDATE,
+ *     STE_FLAG_SHARED_P0, STE_FLAG_PACKED_COV, ragged nsteps, windows, the likelihood without histories), plus time slices
+ *     (step_begin / step_end) when l == NULL; every smoother form ste_urtss_backward_f64 can pick (stand-alone without
+ *     rts_work, one kernel from rts_work, two kernels with the quad or the lane recurrence -- tuning bits 0x200 / 0x400 /
+ *     0x800 -- and smoother rates of their own).
+ *   - Refused with STE_EINVAL and a message before any launch: nz NULL; nz->Q and nz->R both NULL (that is the plain call);
+ *     STE_FLAG_LANES_4 (the quad forward kernel has no per-track noise; without a lane flag the call takes the lane-per-track
+ *     mapping whatever the batch size, as the likelihood call does); unknown bits in nz->flags; and whatever the underlying
+ *     plain call refuses.  The scheduled launches (ste_ukf_forward_sched_f64, ste_urtss_backward_sched_f64) have no
+ *     per-track form.
+ */
+#define STE_NOISE_R_BLOCK2 0x1u /* caller's promise: every track's R is zero outside its leading 2 x 2 block */
+
+typedef struct ste_ukf_noise_f64 {
+    const double* Q;  /* DEVICE [10][track_stride]: upper triangles, row-major 00 01 02 03 11 12 13 22 23 33 (the order of
+                         STE_FLAG_PACKED_COV), track index fastest; NULL = the batch's shared Q for every track */
+    const double* R;  /* the same for R; NULL = the batch's shared R */
+    uint32_t flags;   /* STE_NOISE_* */
+    uint32_t reserved;
+} ste_ukf_noise_f64;   /* 24 bytes */
+
+/* ste_ukf_forward_f64 (l == NULL) or ste_ukf_forward_loglik_f64 (l != NULL) with track t using its own Q / R */
+int ste_ukf_forward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_loglik_f64* l, void* stream);
+/* ste_urtss_backward_f64 with track t's own Q (the smoother never reads R; nz->R is ignored) */
+int ste_urtss_backward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream);
+/* both, back to back on one stream */
+int ste_ukf_urtss_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream);
+
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop
  * (examples/example_ukf_rts_smoother_batch.py:19-90); a fleet goes through the GPU as windows (track_stride above), and

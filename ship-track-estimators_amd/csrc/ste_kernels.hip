@@ -21,6 +21,9 @@
 //     / urtss_recur_lean_q4              every (step, track) at once, written back into the work rows, then the bare
 //                                        recurrence, one lane or one DPP quad per track -- bit-identical to urtss_recur_l1
 //   urtss_backward_l1                    stand-alone smoother that recomputes everything (rts_work == NULL)
+//   ukf_forward_tn, urtss_recur_tn,      the lane-per-track forward pass (with or without the likelihood) and the smoothers
+//     urtss_gains_all_tn,                that read Q, with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
+//     urtss_backward_tn                  device functions, the track's matrices loaded from NoiseParams
 //   predict / update / robust_terms / geodetic / sigma_points kernels   single-step API parity
 // All per-step inputs/outputs are SoA with the track index fastest, so a wave's accesses are contiguous runs.
 //
@@ -487,9 +490,16 @@ __device__ __forceinline__ int robust_terms(const double (&H)[4][4], const doubl
 // Linear Kalman update with pseudo-inverse gain and Joseph-form covariance (unscented.py:219-265).
 // kLik: also the update's log-likelihood terms into *lik (UpdLik, ste_math.h), from the eigenvalues the pseudo-inverse
 // already has and the innovation it already forms.
-template <bool kLik = false>
+// kTrackR: per-track noise (ste_ukf_forward_noise_f64): with `Rt` the track's own R, read here from its upper triangle
+// Rt[e * B] (the order of STE_FLAG_PACKED_COV) -- per-track constants that stay in L2, loaded where they are used instead
+// of held in registers across the step loop; Rt == nullptr: the shared R.  The arithmetic below is the same source either
+// way.  One difference in control flow: the 2 x 2 shortcut of the pseudo-inverse is taken per lane instead of per wave, and
+// only where the lane's own S is exactly confined to the block (no waiver for a non-finite S), so that a track's result
+// does not depend on its neighbours' matrices (with a shared R the test is uniform anyway).
+template <bool kLik = false, bool kTrackR = false>
 __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double (&P)[4][4], const double (&zin)[4],
-                                          const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr) {
+                                          const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr,
+                                          const double* Rt = nullptr) {
     double H[4][4], R[4][4];
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
@@ -497,6 +507,19 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
         for (int c = 0; c < 4; ++c) {
             H[r][c] = p.H[r * 4 + c];
             R[r][c] = p.R[r * 4 + c];
+        }
+    }
+    if constexpr (kTrackR) {
+        if (Rt) {
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                STE_UNROLL
+                for (int c = r; c < 4; ++c) {
+                    const double v = Rt[(size_t)tix(r, c) * B];
+                    R[r][c] = v;
+                    R[c][r] = v;
+                }
+            }
         }
     }
     double z[4];
@@ -543,9 +566,13 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
                 fin += S[r][c];
             }
         }
-        blk = blk || !(fin * 0.0 == 0.0);  // a non-finite S is NaN on either route: no veto against the fast one
+        // a non-finite S is NaN on either route: no veto against the fast one.  (Per lane -- kTrackR -- there is no one to
+        // veto: the lane takes the route its shared launch takes, which with a general R is sym_pinv4 whatever S holds, so
+        // that the status bits of an already non-finite track are the shared launch's too.)
+        if constexpr (!kTrackR) blk = blk || !(fin * 0.0 == 0.0);
+        const bool take_blk = kTrackR ? blk : (bool)__all(blk);
         if constexpr (kLik) {
-            if (__all(blk)) {
+            if (take_blk) {
                 double w[2];
                 sym_pinv4_block2(S, Si, w);
                 pinv_loglik_terms(w, *lik);
@@ -555,7 +582,7 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
                 pinv_loglik_terms(w, *lik);
             }
         } else {
-            if (__all(blk))
+            if (take_blk)
                 sym_pinv4_block2(S, Si);
             else
                 st |= sym_pinv4(S, Si);
@@ -769,14 +796,23 @@ __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], doubl
 // Measurement update on packed (x, P): the closed form for H = diag(1, 1, 0, 0) (kFastUpd, chosen by launch_forward from
 // the matrices), otherwise the general 4x4 route (any H, R; the opt-in robust rescaling).
 // kLik: also the update's log-likelihood terms into *lik (either route).
-template <bool kFastUpd, bool kRobust = false, bool kLik = false>
+// kTrackR: the track's own R from Rt[e * B] when Rt is given (see ukf_update); the closed form reads entries 00, 01, 11.
+template <bool kFastUpd, bool kRobust = false, bool kLik = false, bool kTrackR = false>
 __device__ __forceinline__ int lane_update(const Mats& p, double (&x)[4], double (&P)[10], const double (&zin)[4],
-                                           const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr) {
+                                           const double* noise, size_t nrow, size_t B, size_t t, UpdLik* lik = nullptr,
+                                           const double* Rt = nullptr) {
     if (kFastUpd) {
         double z[4];
         STE_UNROLL
         for (int c = 0; c < 4; ++c) z[c] = zin[c];
         double r00 = p.R[0], r01 = p.R[1], r11 = p.R[5];
+        if constexpr (kTrackR) {
+            if (Rt) {
+                r00 = Rt[(size_t)tix(0, 0) * B];
+                r01 = Rt[(size_t)tix(0, 1) * B];
+                r11 = Rt[(size_t)tix(1, 1) * B];
+            }
+        }
         int st = 0;
         if (kRobust) st = robust_rescale_sel2(p, x, P, z, r00, r01, r11);  // on the un-noised observation (unscented.py:228)
         if (noise) {
@@ -792,7 +828,7 @@ __device__ __forceinline__ int lane_update(const Mats& p, double (&x)[4], double
             STE_UNROLL
             for (int c = 0; c < 4; ++c) Pf[r][c] = P[tix(r, c)];
         }
-        const int st = ukf_update<kLik>(p, x, Pf, zin, noise, nrow, B, t, lik);
+        const int st = ukf_update<kLik, kTrackR>(p, x, Pf, zin, noise, nrow, B, t, lik, Rt);
         STE_UNROLL
         for (int r = 0; r < 4; ++r) {
             STE_UNROLL
@@ -828,9 +864,18 @@ struct LikParams {
     int32_t* nupd;   // [ld] or nullptr
     double* nis;     // [Nmax+1][ld] or nullptr
 };
+// kTrackNoise: per-track Q and R (ste_ukf_noise_f64), a further kernel argument of the *_tn entry kernels: upper triangles
+// [10][ld] in the order of STE_FLAG_PACKED_COV, track index fastest; nullptr = the shared matrix of KParams.  Q goes into
+// the ten Qv registers once per track (forward) or is read once per track before the backward loop (smoothers); R is
+// read at each update (lane_update / ukf_update).
+struct NoiseParams {
+    const double* Q;
+    const double* R;
+};
 
-template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff>
-__device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t, const LikParams* lk = nullptr) {
+template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff, bool kTrackNoise = false>
+__device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t, const LikParams* lk = nullptr,
+                                                const NoiseParams* nz = nullptr) {
     static_assert(kLik != kLikOnly || (!kGains && !kSched), "the likelihood-only pass writes no histories and no work rows");
     const size_t B = (size_t)p.ld;  // row pitch of every per-track array (= the batch's own width unless it is a window)
     if (t >= (size_t)p.B) return;
@@ -887,6 +932,14 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
         STE_UNROLL
         for (int c = r; c < 4; ++c) Qv[tix(r, c)] = in_vgpr(p.m.Q[r * 4 + c]);
     }
+    const double* Rt = nullptr;  // kTrackNoise: this track's R triangle, or nullptr = the shared R
+    if constexpr (kTrackNoise) {
+        if (nz->Q) {
+            STE_UNROLL
+            for (int e = 0; e < 10; ++e) Qv[e] = nz->Q[(size_t)e * B + t];
+        }
+        if (nz->R) Rt = nz->R + t;
+    }
     double V[4][4];
     if (kGains && initial_update && ns > 0) {
         // History row 0 is the PRIOR (kalman_filter.py:76-77) while the first predict starts from the state after the
@@ -907,13 +960,13 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
         load_vec(p.z, 0, B, t, z0);
         if constexpr (kLik != kLikOff) {
             UpdLik u;
-            st |= lane_update<kFastUpd, kRobust, true>(p.m, x, P, z0, p.noise_upd, 0, B, t, &u);
+            st |= lane_update<kFastUpd, kRobust, true, kTrackNoise>(p.m, x, P, z0, p.noise_upd, 0, B, t, &u, Rt);
             lik_sum += update_loglik(u);
             lik_dof += u.rank;
             lik_nupd += 1;
             if (lk->nis) st_stream(&lk->nis[t], u.nis);
         } else {
-            st |= lane_update<kFastUpd, kRobust>(p.m, x, P, z0, p.noise_upd, 0, B, t);  // kalman_filter.py:81
+            st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, z0, p.noise_upd, 0, B, t, nullptr, Rt);  // kalman_filter.py:81
         }
     } else if (kLik != kLikOff && lk->nis) {
         st_stream(&lk->nis[t], __builtin_nan(""));
@@ -958,14 +1011,14 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
                 UpdLik u;
                 u.nis = __builtin_nan("");
                 if (upd) {
-                    st |= lane_update<kFastUpd, kRobust, true>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t, &u);
+                    st |= lane_update<kFastUpd, kRobust, true, kTrackNoise>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t, &u, Rt);
                     lik_sum += update_loglik(u);
                     lik_dof += u.rank;
                     lik_nupd += 1;
                 }
                 if (lk->nis) st_stream(&lk->nis[((size_t)k + 1) * B + t], u.nis);
             } else {
-                if (upd) st |= lane_update<kFastUpd, kRobust>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t);
+                if (upd) st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t, nullptr, Rt);
             }
             if (!ui_ok) st |= STE_STATUS_BAD_INDEX;
             if (kLik != kLikOnly) store_hist(p, (size_t)k + 1, B, t, x, P);
@@ -995,6 +1048,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 template <bool kGains, bool kFastUpd, bool kRobust, int kLik>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_lik(const KParams p, const LikParams l) {
     forward_tile_l1<kGains, kFastUpd, kRobust, false, kLik>(p, (size_t)blockIdx.x * 64 + threadIdx.x, &l);
+}
+
+// The lane-per-track forward pass with per-track noise (ste_ukf_forward_noise_f64): the bodies of ukf_forward_l1 (kLikOff;
+// `l` is not read) and ukf_forward_lik with the track's own Q / R.  KParams stays the first argument (late_k0).
+template <bool kGains, bool kFastUpd, bool kRobust, int kLik>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_tn(const KParams p, const LikParams l,
+                                                                                                 const NoiseParams nz) {
+    forward_tile_l1<kGains, kFastUpd, kRobust, false, kLik, true>(p, (size_t)blockIdx.x * 64 + threadIdx.x, &l, &nz);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1539,129 +1600,18 @@ __device__ __forceinline__ void store_pos(const KParams& p, size_t row, size_t B
     }
 }
 
+// (the body lives in ste_urtss_backward_body.h, shared with urtss_backward_tn below)
 __global__ __launch_bounds__(64) void urtss_backward_l1(const KParams p) {
-    const size_t B = (size_t)p.ld;
-    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (size_t)p.B) return;
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    const double* srp = p.sog_rate_rts ? p.sog_rate_rts : p.sog_rate;
-    const double* crp = p.cog_rate_rts ? p.cog_rate_rts : p.cog_rate;
-
-    // row ns: smoothed = filtered
-    double xs[4], Ps[4][4];
-    load_vec(p.fwd_mean, (size_t)ns, B, t, xs);
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    load_cov_m(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
-    store_vec(p.sm_mean, (size_t)ns, B, t, xs);
-    store_cov_m(p.sm_cov, packed, (size_t)ns, B, t, Ps);
-    store_pos(p, (size_t)ns, B, t, xs);
-
-    // filtered row of the first step to process, prefetched
-    double xn[4] = {0, 0, 0, 0}, Pn[4][4] = {};
-    double dt_n = 0.0, sr_n = 0.0, cr_n = 0.0;
-    if (ns > 0) {
-        load_vec(p.fwd_mean, (size_t)ns - 1, B, t, xn);
-        load_cov_m(p.fwd_cov, packed, (size_t)ns - 1, B, t, Pn);
-        const size_t o = (size_t)(ns - 1) * B + t;
-        dt_n = p.dt[o];
-        sr_n = srp[o];
-        cr_n = crp[o];
-    }
-    int st = 0;
-    EigBasis fan_basis, pb_basis;
-    fan_basis.valid = false;
-    pb_basis.valid = false;
-    for (int k = p.Nmax - 1; k >= 0; --k) {
-        if (!__any(k < ns)) continue;  // ragged batch: nobody in this wave has reached its last step yet
-        if (k < ns) {
-            double xk[4], Pk[4][4];
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                xk[r] = xn[r];
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) Pk[r][c] = Pn[r][c];
-            }
-            const double dt = dt_n, sr = sr_n, cr = cr_n;
-            if (k > 0) {
-                load_vec(p.fwd_mean, (size_t)k - 1, B, t, xn);
-                load_cov_m(p.fwd_cov, packed, (size_t)k - 1, B, t, Pn);
-                const size_t o = (size_t)(k - 1) * B + t;
-                dt_n = p.dt[o];
-                sr_n = srp[o];
-                cr_n = crp[o];
-            }
-            double sig0[9][4], sig[9][4];
-            if ((k & (kColdEvery - 1)) == kColdEvery - 1) {
-                fan_basis.valid = false;
-                pb_basis.valid = false;
-            }
-            st |= propagate_fan<true>(xk, Pk, p.m.fan_scale, dt, sr, cr, sig0, sig, fan_basis);
-            double xb[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                double acc = 0.0;
-                STE_UNROLL
-                for (int j = 1; j < 9; ++j) acc += sig[j][c];
-                xb[c] = fma(p.m.w0, sig[0][c], p.m.wi * acc);
-            }
-            if (p.noise_rts) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) xb[c] += p.noise_rts[((size_t)k * 4 + c) * B + t];
-            }
-            // P_b is centred on the filtered mean x_k, not on x_b (unscented.py:324-325)
-            double dk[9][4], db[9][4];
-            STE_UNROLL
-            for (int j = 0; j < 9; ++j) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) {
-                    dk[j][c] = sig[j][c] - xk[c];
-                    db[j][c] = sig[j][c] - xb[c];
-                    sig0[j][c] -= xk[c];
-                }
-            }
-            double Pb[4][4], D[4][4], Pbi[4][4], K[4][4];
-            weighted_outer<true>(dk, dk, p.m.w0, p.m.wi, Pb);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) Pb[r][c] += p.m.Q[r * 4 + c];
-            }
-            weighted_outer<false>(sig0, db, p.m.w0, p.m.wi, D);  // unscented.py:328-330
-            st |= sym_pinv4<true>(Pb, Pbi, pb_basis);
-            pb_basis.valid = true;
-            mm(D, Pbi, K);  // unscented.py:333
-            double y[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) y[c] = xs[c] - xb[c];
-            y[3] = wrap180(y[3]);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                double acc = xk[r];
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) acc = fma(K[r][c], y[c], acc);
-                xs[r] = acc;
-            }
-            xs[3] = floored_mod(xs[3], 360.0);
-            double dP[4][4], KdP[4][4], U[4][4];
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) dP[r][c] = Ps[r][c] - Pb[r][c];
-            }
-            mm(K, dP, KdP);
-            mmt_sym(KdP, K, U);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) Ps[r][c] = Pk[r][c] + U[r][c];
-            }
-            store_vec(p.sm_mean, (size_t)k, B, t, xs);
-            store_cov_m(p.sm_cov, packed, (size_t)k, B, t, Ps);
-            store_pos(p, (size_t)k, B, t, xs);
-        }
-    }
-    if (!all_finite(xs, Ps)) st |= STE_STATUS_NAN;
-    if (st) atomicOr(&p.status[t], st);
+#define STE_BWD_Q(r, c) p.m.Q[(r) * 4 + (c)]
+#include "ste_urtss_backward_body.h"
+#undef STE_BWD_Q
+}
+// The same smoother with track t's own Q (ste_urtss_backward_noise_f64): nz.Q[tix(r, c) * ld + t], loaded where it is
+// used.  nz.Q is not NULL here: without a per-track Q launch_backward_tn takes urtss_backward_l1.
+__global__ __launch_bounds__(64) void urtss_backward_tn(const KParams p, const NoiseParams nz) {
+#define STE_BWD_Q(r, c) nz.Q[(size_t)tix(r, c) * B + t]
+#include "ste_urtss_backward_body.h"
+#undef STE_BWD_Q
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1715,11 +1665,13 @@ __device__ __forceinline__ void load_recur_row(const KParams& p, size_t k, size_
 // k + 1) and the gain K = D pinv(P_b) (unscented.py:315-333).  `cur` = work-row / history data of step k, (xn, Pn) = filtered
 // row k + 1, `full` = work row k holds x_b and P_b.  Shared by the one-kernel smoother (urtss_recur_l1) and the two-kernel
 // form for small batches (urtss_gains_all + urtss_recur_lean): same code, same bits.
-template <bool kShift>
+// kTrackNoise: the four entries of Q it reads come from `q4` (Q[0][2], Q[0][3], Q[1][2], Q[1][3] of this track, see
+// track_q4) instead of from the kernel arguments.
+template <bool kShift, bool kTrackNoise = false>
 __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_t B, size_t t, const RecurRow& cur,
                                                   const double (&xn)[4], const double (&Pn)[10], bool full, bool always_full,
                                                   bool all_eig, double kappa, double first_bad, double (&xb)[4],
-                                                  double (&Pb)[10], double (&K)[4][4]) {
+                                                  double (&Pb)[10], double (&K)[4][4], const double* q4 = nullptr) {
     // x_b, P_b: stored (a quarter of the steps of the bench batch: loaded here, not a row ahead, to keep the
     // registers of a whole row free), or the prediction itself -- the step was not followed by an update, so row
     // k + 1 of the filtered history is x^-, P^-, and P_b = P^- + b b^T with b = x^- - x_k
@@ -1791,7 +1743,10 @@ __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_
             STE_UNROLL
             for (int c = 0; c < 2; ++c) {
                 const double pm = full ? fma(-bv[c], bv[r], Pb[tix(c, r)]) : Pn[tix(c, r)];
-                D[r][c] = pm - p.m.Q[c * 4 + r];
+                if constexpr (kTrackNoise)
+                    D[r][c] = pm - q4[c * 2 + (r - 2)];
+                else
+                    D[r][c] = pm - p.m.Q[c * 4 + r];
             }
         }
     }
@@ -1809,11 +1764,22 @@ __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_
 
 }
 
+// Per-track noise: the entries (0,2) (0,3) (1,2) (1,3) of track t's Q, once per track (or per lane of urtss_gains_all)
+__device__ __forceinline__ void track_q4(const KParams& p, const NoiseParams& nz, size_t B, size_t t, double (&q4)[4]) {
+    STE_UNROLL
+    for (int c = 0; c < 2; ++c) {
+        STE_UNROLL
+        for (int r = 2; r < 4; ++r) q4[c * 2 + (r - 2)] = nz.Q ? nz.Q[(size_t)tix(c, r) * B + t] : p.m.Q[c * 4 + r];
+    }
+}
+
 // kShift: the smoother has rates of its own (sog_rate_rts / cog_rate_rts); compiled out for batches that share them.
-template <bool kShift>
-__device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t) {
+template <bool kShift, bool kTrackNoise = false>
+__device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t, const NoiseParams* nz = nullptr) {
     const size_t B = (size_t)p.ld;
     if (t >= (size_t)p.B) return;
+    double q4[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (kTrackNoise) track_q4(p, *nz, B, t, q4);
     const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
     const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
     const bool all_eig = (p.tuning & 0x100) != 0;
@@ -1850,7 +1816,7 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t)
             const RecurRow cur = nxt;
             const bool full = work_row_full(p, k, ui_n, always_full);
             double xb[4], Pb[10], K[4][4];
-            st |= smoother_step_gain<kShift>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K);
+            st |= smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
             // the row of the next step: in flight during the recurrence arithmetic below (and across the loop edge)
             {
                 const int kn = clampk(k - 1);
@@ -1917,6 +1883,10 @@ template <bool kShift>
 __global__ __launch_bounds__(64) void urtss_recur_l1(const KParams p) {
     smooth_tile_l1<kShift>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
 }
+template <bool kShift>
+__global__ __launch_bounds__(64) void urtss_recur_tn(const KParams p, const NoiseParams nz) {
+    smooth_tile_l1<kShift, true>(p, (size_t)blockIdx.x * 64 + threadIdx.x, &nz);
+}
 
 // The smoothers of every window of a scheduled forward launch as ONE launch (ste_urtss_backward_sched_f64): a wave per
 // (window, 64-track tile), in the order the schedule finishes the tiles, each waiting (bounded) for ITS tile's last slice
@@ -1970,6 +1940,8 @@ __global__ __launch_bounds__(64) void urtss_recur_sched(const SmoothSchedParams 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kLeanK01 = kWorkD, kLeanK23 = kWorkD23;  // K[r][0:2] at kLeanK01 + 2 r, K[r][2:4] at kLeanK23 + 2 r
 
+// (urtss_gains_all_tn below repeats this load / store wrapper for batches with per-track Q: an edit here belongs there too,
+//  or the two stop writing the same bits -- tests/test_ukf_track_noise.py.)
 template <bool kShift>
 __global__ __launch_bounds__(64) void urtss_gains_all(const KParams p) {
     const size_t B = (size_t)p.ld;
@@ -1993,6 +1965,46 @@ __global__ __launch_bounds__(64) void urtss_gains_all(const KParams p) {
     const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
     double xb[4], Pb[10], K[4][4];
     const int st = smoother_step_gain<kShift>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K);
+    double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
+    STE_UNROLL
+    for (int r = 0; r < 4; ++r) {
+        w[(kLeanK01 + 2 * r + 0) * B] = K[r][0];
+        w[(kLeanK01 + 2 * r + 1) * B] = K[r][1];
+        w[(kLeanK23 + 2 * r + 0) * B] = K[r][2];
+        w[(kLeanK23 + 2 * r + 1) * B] = K[r][3];
+    }
+    STE_UNROLL
+    for (int c = 0; c < 4; ++c) w[(kWorkXb + c) * B] = xb[c];
+    STE_UNROLL
+    for (int e = 0; e < 10; ++e) w[(kWorkPb + e) * B] = Pb[e];
+    if (st) atomicOr(&p.status[t], st);
+}
+// urtss_gains_all for a batch with per-track Q: the same loads, the same gain function (smoother_step_gain, with this
+// lane's track's four entries of Q), the same stores.
+template <bool kShift>
+__global__ __launch_bounds__(64) void urtss_gains_all_tn(const KParams p, const NoiseParams nz) {
+    const size_t B = (size_t)p.ld;
+    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (g >= (size_t)p.B * (size_t)p.Nmax) return;
+    const size_t t = g % (size_t)p.B;
+    const int k = (int)(g / (size_t)p.B);
+    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
+    if (k >= ns) return;
+    const double fb_raw = p.first_bad[t];
+    if (fb_raw < 0.0) return;  // the rows of this track already hold gains (a repeated backward call)
+    const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
+    const bool all_eig = (p.tuning & 0x100) != 0;
+    const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;
+    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
+    RecurRow cur;
+    load_recur_row<kShift>(p, (size_t)k, B, t, always_full, cur);
+    double xn[4], Pn[10];
+    load_vec(p.fwd_mean, (size_t)k + 1, B, t, xn);
+    load_cov_p(p.fwd_cov, packed, (size_t)k + 1, B, t, Pn);
+    const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
+    double xb[4], Pb[10], K[4][4], q4[4];
+    track_q4(p, nz, B, t, q4);
+    const int st = smoother_step_gain<kShift, true>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K, q4);
     double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
@@ -2649,6 +2661,84 @@ int launch_backward(const ste::KParams& kp, hipStream_t s) {
     return check_hip(hipGetLastError(), "urtss_backward launch");
 }
 
+// ---- per-track noise (ste_ukf_noise_f64) -----------------------------------------------------------------------------
+// The checks the three *_noise entry points share, and the route: with a per-track R the closed-form update is the caller's
+// promise (STE_NOISE_R_BLOCK2) instead of a look at b->R -- the library cannot read device memory before a launch.
+int noise_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, ste::NoiseParams* np) {
+    if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
+    if (!nz) return fail(STE_EINVAL, "%s: the per-track noise (nz) is NULL", fn);
+    if (!nz->Q && !nz->R)
+        return fail(STE_EINVAL, "%s: nz->Q and nz->R are both NULL: that is the plain call (without the _noise suffix)", fn);
+    if (nz->flags & ~(uint32_t)STE_NOISE_R_BLOCK2) return fail(STE_EINVAL, "%s: unknown bits in nz->flags", fn);
+    if (b->flags & STE_FLAG_LANES_4)
+        return fail(STE_EINVAL, "%s: the quad forward kernel has no per-track noise: STE_FLAG_LANES_4 is refused", fn);
+    np->Q = nz->Q;
+    np->R = nz->R;
+    return STE_OK;
+}
+void noise_route(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, ste::KParams* kp) {
+    kp->flags |= STE_FLAG_LANES_1;
+    if (!nz->R) return;  // shared R: make_params has looked at it
+    bool sel = true;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) sel = sel && b->H[r * 4 + c] == ((r == c && r < 2) ? 1.0 : 0.0);
+    kp->fast_upd = sel && (nz->flags & STE_NOISE_R_BLOCK2) != 0;
+}
+
+// launch_forward / launch_forward_lik for the per-track instantiations: the same choice of kGains / kFastUpd / kRobust / kLik
+int launch_forward_tn(const ste::KParams& kp, const ste::LikParams* lp, const ste::NoiseParams& np, hipStream_t s) {
+    const bool robust = kp.m.robust_iters > 0;
+    const unsigned grid = (unsigned)((kp.B + 63) / 64);
+    const ste::LikParams l0 = lp ? *lp : ste::LikParams{nullptr, nullptr, nullptr, nullptr};
+    const int which = (lp ? (kp.fwd_mean ? 8 : 16) : 0) | (kp.rts_work ? 4 : 0) | (kp.fast_upd ? (robust ? 2 : 1) : 0);
+    switch (which) {
+#define STE_TN(n, g, f, r, m) \
+    case n: hipLaunchKernelGGL((ste::ukf_forward_tn<g, f, r, m>), dim3(grid), dim3(64), 0, s, kp, l0, np); break;
+        STE_TN(0, false, false, false, ste::kLikOff) STE_TN(1, false, true, false, ste::kLikOff)
+        STE_TN(2, false, true, true, ste::kLikOff) STE_TN(4, true, false, false, ste::kLikOff)
+        STE_TN(5, true, true, false, ste::kLikOff) STE_TN(6, true, true, true, ste::kLikOff)
+        STE_TN(8, false, false, false, ste::kLikHist) STE_TN(9, false, true, false, ste::kLikHist)
+        STE_TN(10, false, true, true, ste::kLikHist) STE_TN(12, true, false, false, ste::kLikHist)
+        STE_TN(13, true, true, false, ste::kLikHist) STE_TN(14, true, true, true, ste::kLikHist)
+        STE_TN(16, false, false, false, ste::kLikOnly) STE_TN(17, false, true, false, ste::kLikOnly)
+        STE_TN(18, false, true, true, ste::kLikOnly)
+#undef STE_TN
+        default: return fail(STE_EINVAL, "ste_ukf_forward_noise_f64: rts_work needs the histories");
+    }
+    return check_hip(hipGetLastError(), "ukf_forward_tn launch");
+}
+
+// launch_backward for a batch with per-track Q: the same choice of smoother form; the lean recurrences read no Q and run as they are
+int launch_backward_tn(const ste::KParams& kp, const ste::NoiseParams& np, hipStream_t s) {
+    if (!np.Q) return launch_backward(kp, s);  // the smoother never reads R
+    const unsigned grid = (unsigned)((kp.B + 63) / 64);
+    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts;
+    if (kp.rts_work && kp.Nmax > 0 && ((kp.tuning & 0x200) || (!(kp.tuning & 0x400) && kp.B <= kLeanSmootherMaxTracks))) {
+        const size_t lanes = (size_t)kp.B * (size_t)kp.Nmax;
+        const unsigned ggrid = (unsigned)((lanes + 63) / 64);
+        if (shift)
+            hipLaunchKernelGGL(ste::urtss_gains_all_tn<true>, dim3(ggrid), dim3(64), 0, s, kp, np);
+        else
+            hipLaunchKernelGGL(ste::urtss_gains_all_tn<false>, dim3(ggrid), dim3(64), 0, s, kp, np);
+        int rc = check_hip(hipGetLastError(), "urtss_gains_all_tn launch");
+        if (rc) return rc;
+        if (kp.tuning & 0x800)
+            hipLaunchKernelGGL(ste::urtss_recur_lean, dim3(grid), dim3(64), 0, s, kp);
+        else
+            hipLaunchKernelGGL(ste::urtss_recur_lean_q4, dim3((unsigned)((kp.B + 15) / 16)), dim3(64), 0, s, kp);
+        return check_hip(hipGetLastError(), "urtss_recur_lean launch");
+    }
+    if (kp.rts_work) {
+        if (shift)
+            hipLaunchKernelGGL(ste::urtss_recur_tn<true>, dim3(grid), dim3(64), 0, s, kp, np);
+        else
+            hipLaunchKernelGGL(ste::urtss_recur_tn<false>, dim3(grid), dim3(64), 0, s, kp, np);
+        return check_hip(hipGetLastError(), "urtss_recur_tn launch");
+    }
+    hipLaunchKernelGGL(ste::urtss_backward_tn, dim3(grid), dim3(64), 0, s, kp, np);
+    return check_hip(hipGetLastError(), "urtss_backward_tn launch");
+}
+
 // which instantiation of the lane-per-track forward kernel a batch takes (launch_forward's own choice, as a number)
 int forward_variant(const ste::KParams& kp) {
     const bool robust = kp.m.robust_iters > 0;
@@ -3039,6 +3129,62 @@ int ste_ukf_urtss_f64(const ste_ukf_batch_f64* b, void* stream) {
     rc = launch_forward(kp, (hipStream_t)stream);
     if (rc) return rc;
     return launch_backward(kp, (hipStream_t)stream);
+}
+
+int ste_ukf_forward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_loglik_f64* l, void* stream) {
+    const char* fn = "ste_ukf_forward_noise_f64";
+    ste::NoiseParams np;
+    int rc = noise_params(fn, b, nz, &np);
+    if (rc) return rc;
+    ste::KParams kp;
+    if (l) {  // ste_ukf_forward_loglik_f64's own checks
+        if (!l->loglik) return fail(STE_EINVAL, "%s: l->loglik is required", fn);
+        const bool hist = b->fwd_mean != nullptr;
+        if (hist != (b->fwd_cov != nullptr))
+            return fail(STE_EINVAL, "%s: fwd_mean and fwd_cov go together: both (histories) or neither (the likelihood alone)", fn);
+        if (!hist && b->rts_work)
+            return fail(STE_EINVAL, "%s: rts_work needs the histories (the smoother reads both); pass fwd_mean and fwd_cov, or no "
+                                    "rts_work", fn);
+        if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
+            return fail(STE_EINVAL, "%s with l != NULL runs whole passes: the likelihood sums over every update, so time slices "
+                                    "(step_begin / step_end) are refused", fn);
+        rc = make_params(b, false, false, &kp, hist);
+        if (rc) return rc;
+        noise_route(b, nz, &kp);
+        const ste::LikParams lp = {l->loglik, l->dof, l->nupd, l->nis};
+        return launch_forward_tn(kp, &lp, np, (hipStream_t)stream);
+    }
+    rc = make_params(b, false, false, &kp);
+    if (rc) return rc;
+    noise_route(b, nz, &kp);
+    rc = slice_params(b, &kp);
+    if (rc) return rc;
+    return launch_forward_tn(kp, nullptr, np, (hipStream_t)stream);
+}
+
+int ste_urtss_backward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream) {
+    ste::NoiseParams np;
+    int rc = noise_params("ste_urtss_backward_noise_f64", b, nz, &np);
+    if (rc) return rc;
+    ste::KParams kp;
+    rc = make_params(b, true, true, &kp);
+    if (rc) return rc;
+    return launch_backward_tn(kp, np, (hipStream_t)stream);
+}
+
+int ste_ukf_urtss_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream) {
+    ste::NoiseParams np;
+    int rc = noise_params("ste_ukf_urtss_noise_f64", b, nz, &np);
+    if (rc) return rc;
+    ste::KParams kp;
+    rc = make_params(b, false, true, &kp);
+    if (rc) return rc;
+    if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
+        return fail(STE_EINVAL, "ste_ukf_urtss_noise_f64 runs whole passes: time slices go through ste_ukf_forward_noise_f64");
+    noise_route(b, nz, &kp);
+    rc = launch_forward_tn(kp, nullptr, np, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_backward_tn(kp, np, (hipStream_t)stream);
 }
 
 int ste_geodetic_dynamics_f64(int64_t count, const double* x, const double* dt, const double* sog_rate,

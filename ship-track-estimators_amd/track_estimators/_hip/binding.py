@@ -21,6 +21,8 @@ STE_FLAG_LANES_1 = 0x10
 STE_FLAG_LANES_4 = 0x20
 STE_FLAG_PACKED_COV = 0x40
 
+STE_NOISE_R_BLOCK2 = 0x1  # ste_ukf_noise_f64.flags: every track's R is zero outside its leading 2 x 2 block
+
 STE_RTS_WORK_ROWS = 30  # doubles per (step, track) of ste_ukf_batch_f64.rts_work
 STE_SLICE_ALIGN = 64  # time slices of the forward pass start and end on multiples of this many steps
 
@@ -87,6 +89,17 @@ class SteUkfLoglikF64(C.Structure):
         ("dof", _dp),
         ("nupd", _dp),
         ("nis", _dp),
+    ]
+
+
+class SteUkfNoiseF64(C.Structure):
+    """Mirror of ``struct ste_ukf_noise_f64`` (include/ste.h): per-track Q / R, upper triangles [10][track_stride]."""
+
+    _fields_ = [
+        ("Q", _dp),
+        ("R", _dp),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
     ]
 
 
@@ -188,6 +201,10 @@ SYMBOLS = {
     "ste_device_count": (C.c_int, []),
     "ste_ukf_forward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_loglik_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfLoglikF64), C.c_void_p]),
+    "ste_ukf_forward_noise_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteUkfLoglikF64),
+                                            C.c_void_p]),
+    "ste_urtss_backward_noise_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.c_void_p]),
+    "ste_ukf_urtss_noise_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -98,7 +98,13 @@ def draw_reference_noise(Q, R, dt, dts, t0=0):
 
 @dataclasses.dataclass
 class HostBatch:
-    """NumPy image of ``struct ste_ukf_batch_f64``; arrays are C-contiguous with the track index last."""
+    """NumPy image of ``struct ste_ukf_batch_f64``; arrays are C-contiguous with the track index last.
+
+    ``Q`` / ``R`` are the shared 4 x 4 matrices.  Per-track noise (include/ste.h: ``ste_ukf_noise_f64``) travels in
+    ``Q_tracks`` / ``R_tracks``: (10, B) upper triangles (row-major 00 01 02 03 11 12 13 22 23 33) in slot order, or None.
+    Where ``Q_tracks`` (``R_tracks``) is set the kernels do not read ``Q`` (``R``): the 4 x 4 field is the fallback only for
+    whichever of the two was not stacked.  ``pack_tracks`` / ``pack_uniform`` leave the stack's first matrix (the caller's
+    track 0) in it, ``with_track_noise`` whatever ``hb`` held before.  ``track_matrices`` gives every track's effective pair."""
 
     B: int
     Nmax: int
@@ -126,6 +132,12 @@ class HostBatch:
     host_status: Optional[np.ndarray] = None  # (B,) int32 bits set while packing (STATUS_HOST_INDEX)
     order: Optional[np.ndarray] = None  # (B,) batch slot -> index of the caller's track (length-bucketed packing)
     lanes: Optional[int] = None  # forward-kernel lane mapping for this batch: 1, 4, 0 = by batch size; None = default_lanes
+    Q_tracks: Optional[np.ndarray] = None  # (10, B) per-track Q, upper triangles, or None = Q for every track
+    R_tracks: Optional[np.ndarray] = None  # (10, B) per-track R, upper triangles, or None = R for every track
+
+    @property
+    def track_noise(self) -> bool:
+        return self.Q_tracks is not None or self.R_tracks is not None
 
     @property
     def shared_p0(self) -> bool:
@@ -167,6 +179,76 @@ def _as44(M, name, symmetric: bool = False):
     return M
 
 
+_TRI = np.triu_indices(4)  # row-major upper triangle: 00 01 02 03 11 12 13 22 23 33 (STE_FLAG_PACKED_COV's order)
+
+
+def _noise_arg(M, name, B, order=None):
+    """One 4 x 4 matrix, or a stack (B, 4, 4) / sequence of B matrices in the caller's track order (``order``: slot ->
+    caller's track).  Returns (the shared 4 x 4, (10, B) upper triangles in slot order or None)."""
+    A = np.asarray(M, dtype=np.float64)
+    if A.ndim == 2:
+        return _as44(A, name, True), None
+    if A.shape != (B, 4, 4):
+        raise ValueError(f"{name} must be one 4x4 matrix or a stack of one per track, ({B}, 4, 4); got {A.shape}")
+    for i in range(B):
+        require_symmetric(A[i], f"{name}[{i}]")  # the message names the track
+    first = np.ascontiguousarray(A[0])
+    if order is not None:
+        A = A[order]
+    return first, np.ascontiguousarray(A[:, _TRI[0], _TRI[1]].T)
+
+
+def r_tracks_block2(R_tracks) -> bool:
+    """Is every track's R zero outside its leading 2 x 2 block (entries 00, 01, 11 of the triangle)?  What
+    ``STE_NOISE_R_BLOCK2`` promises to the library, which cannot look into device memory before a launch."""
+    rest = np.delete(np.asarray(R_tracks), (0, 1, 4), axis=0)
+    return bool(np.all(rest == 0.0))
+
+
+def track_matrices(hb: "HostBatch"):
+    """(Q, R) as (B, 4, 4) stacks in slot order: what every track of ``hb`` filters with -- its own triangle expanded where
+    ``Q_tracks`` / ``R_tracks`` is set, the shared matrix otherwise."""
+    full = np.zeros((4, 4), dtype=np.intp)
+    full[_TRI] = np.arange(10)
+    full = np.maximum(full, full.T)  # position of (r, c) in the packed triangle
+    out = []
+    for shared, tri in ((hb.Q, hb.Q_tracks), (hb.R, hb.R_tracks)):
+        out.append(np.broadcast_to(shared, (hb.B, 4, 4)) if tri is None else np.ascontiguousarray(tri.T[:, full]))
+    return out[0], out[1]
+
+
+def with_track_noise(hb: "HostBatch", Q=None, R=None) -> "HostBatch":
+    """A copy of ``hb`` (arrays shared) with per-track noise: ``Q`` / ``R`` are stacks (B, 4, 4) in SLOT order (the order
+    of ``hb``'s arrays; ``hb.order`` maps slots to the caller's tracks), each checked for symmetry per matrix; None leaves
+    that one as it is in ``hb`` (shared, or the stack ``hb`` already carries).  ``hb.Q`` / ``hb.R`` are not touched."""
+    new = {}
+    for name, M in (("Q", Q), ("R", R)):
+        if M is None:
+            continue
+        A = np.asarray(M, dtype=np.float64)
+        if A.shape != (hb.B, 4, 4):
+            raise ValueError(f"{name} must be a stack of one 4x4 matrix per track, ({hb.B}, 4, 4); got {A.shape}")
+        new[name + "_tracks"] = _noise_arg(A, name, hb.B)[1]
+    return dataclasses.replace(hb, **new)
+
+
+def apply_noise_choice(hb: "HostBatch", candidates: Sequence, choice: "NoiseChoice") -> "HostBatch":
+    """The step after ``log_likelihood_grid`` and ``best_noise(grid, per_track=True)``: a copy of ``hb`` in which track
+    (slot) b filters and smooths with ``candidates[choice.index[b]]``; a track with index -1 keeps the pair it has in
+    ``hb``: the shared one, or its own if ``hb`` already carries stacks (``track_matrices``)."""
+    cands = [(_as44(Q, "Q", True), _as44(R, "R", True)) for Q, R in candidates]
+    idx = np.asarray(choice.index)
+    if idx.shape != (hb.B,):
+        raise ValueError(f"choice.index must hold one candidate index per track, ({hb.B},): take it from "
+                         f"best_noise(grid, per_track=True); got shape {idx.shape}")
+    if ((idx < -1) | (idx >= len(cands))).any():
+        raise ValueError(f"choice.index out of range for {len(cands)} candidates")
+    Q0, R0 = track_matrices(hb)
+    Qs = np.stack([cands[i][0] if i >= 0 else Q0[b] for b, i in enumerate(idx)])
+    Rs = np.stack([cands[i][1] if i >= 0 else R0[b] for b, i in enumerate(idx)])
+    return with_track_noise(hb, Qs, Rs)
+
+
 STATUS_HOST_INDEX = binding.STE_STATUS_HOST_INDEX  # the reference would raise IndexError for this track (update index past the last observation)
 
 # Lane mapping used by batches that do not name one (HostBatch.lanes is None): 0 = the library picks by batch size.
@@ -185,6 +267,8 @@ def pack_tracks(tracks: Sequence, dts_per_track: Sequence, x0s: Sequence, H, Q, 
     Pack B tracks (objects carrying ``z`` (4,T), ``dts`` (T-1,), ``sog_rate`` (T,), ``cog_rate`` (T,) like a
     reference ``ShipTrack``, ship_track.py:70-83) with their per-track ``dt`` arrays and priors into a HostBatch.
     Ragged batches are padded to the longest track.  ``P0`` is one 4x4 shared matrix or a sequence of B matrices.
+    ``Q`` and ``R`` likewise: one shared 4x4 matrix each, or a stack (B, 4, 4) / sequence of B matrices -- per-track noise,
+    checked per matrix and laid out like the tracks (``HostBatch.Q_tracks`` / ``R_tracks``).
     ``noise`` (test-only) is a per-track list of dicts with ``noise_pred`` (N,4), ``noise_upd`` (N+1,4), ``noise_rts`` (N,4).
     ``on_error``: a track whose update index runs past its last observation (duplicate timestamps make the
     float-equality trigger fire twice per gap) raises IndexError in the reference (kalman_filter.py:105).  "raise" does
@@ -197,6 +281,7 @@ def pack_tracks(tracks: Sequence, dts_per_track: Sequence, x0s: Sequence, H, Q, 
     B = len(tracks)
     if B == 0:
         raise ValueError("empty batch")
+    Q_in, R_in = Q, R
     order = None
     if bucket_by_length and B > 1:
         lens = np.array([len(d) for d in dts_per_track])
@@ -210,7 +295,8 @@ def pack_tracks(tracks: Sequence, dts_per_track: Sequence, x0s: Sequence, H, Q, 
             P0a = np.asarray(P0, dtype=np.float64)
             if P0a.ndim == 3:
                 P0 = P0a[order]
-    H, Q, R = _as44(H, "H"), _as44(Q, "Q", True), _as44(R, "R", True)
+    H = _as44(H, "H")
+    (Q, Qt), (R, Rt) = _noise_arg(Q_in, "Q", B, order), _noise_arg(R_in, "R", B, order)
     Ns = [len(d) for d in dts_per_track]
     Ts = [np.asarray(tr.z).shape[1] for tr in tracks]
     Nmax, Tmax = max(Ns), max(Ts)
@@ -279,16 +365,18 @@ def pack_tracks(tracks: Sequence, dts_per_track: Sequence, x0s: Sequence, H, Q, 
     return HostBatch(B=B, Nmax=Nmax, Tmax=Tmax, H=H, Q=Q, R=R, nsteps=nsteps, x0=x0, P0=P0p, dt=dt, sog_rate=sr,
                      cog_rate=cr, sog_rate_rts=None if same_rts else srr, cog_rate_rts=None if same_rts else crr,
                      upd_idx=ui, z=z, noise_pred=npred, noise_upd=nupd, noise_rts=nrts, host_status=host_status,
-                     order=order)
+                     order=order, Q_tracks=Qt, R_tracks=Rt)
 
 
 def pack_uniform(sb, substeps: int, H, Q, R, P0) -> HostBatch:
     """
     Fast path for a batch where every track has the same number of observations (``synthetic.SyntheticBatch``):
     vectorised over tracks.  x0 = z[:, 0] (example_ukf_rts_smoother_batch.py:60); dt = generate_dts(dts, substeps).
+    ``Q`` / ``R``: one 4x4 matrix each or a stack (B, 4, 4), as in ``pack_tracks``.
     """
-    H, Q, R = _as44(H, "H"), _as44(Q, "Q", True), _as44(R, "R", True)
     B, T = sb.lon.shape
+    H = _as44(H, "H")
+    (Q, Qt), (R, Rt) = _noise_arg(Q, "Q", B), _noise_arg(R, "R", B)
     s = int(substeps)
     N = s * (T - 1)
     dt = np.repeat(sb.dts / s, s, axis=1)  # (B, N): utils.py:194-198
@@ -319,7 +407,7 @@ def pack_uniform(sb, substeps: int, H, Q, R, P0) -> HostBatch:
         B=B, Nmax=N, Tmax=T, H=H, Q=Q, R=R, nsteps=np.full(B, N, dtype=np.int32), x0=c(sb.z[:, :, 0].T),
         P0=c(P0.reshape(16)), dt=np.repeat(c(sb.dts.T) / s, s, axis=0), sog_rate=sr, cog_rate=cr,
         sog_rate_rts=None if same_rts else srr, cog_rate_rts=None if same_rts else crr,
-        upd_idx=c(upd_idx.T), z=c(sb.z.transpose(2, 1, 0)),
+        upd_idx=c(upd_idx.T), z=c(sb.z.transpose(2, 1, 0)), Q_tracks=Qt, R_tracks=Rt,
     )
 
 
@@ -331,6 +419,7 @@ class DeviceBatch:
 
     _IN = ("nsteps", "x0", "P0", "dt", "sog_rate", "cog_rate", "sog_rate_rts", "cog_rate_rts", "upd_idx", "z",
            "noise_pred", "noise_upd", "noise_rts")
+    _NOISE_IN = ("Q_tracks", "R_tracks")  # per-track noise: inputs like the others, named by ``noise`` instead of ``struct``
 
     # position of (r, c) in a packed upper triangle, for all 16 entries of the full matrix (include/ste.h: STE_FLAG_PACKED_COV)
     _PACKED_INDEX = [min(r, c) * 4 - (min(r, c) * (min(r, c) - 1)) // 2 + abs(r - c) for r in range(4) for c in range(4)]
@@ -350,7 +439,11 @@ class DeviceBatch:
         self.hb = hb
         self.device = torch.device(device)
         self.t = {}
-        for name in self._IN:
+        lanes = default_lanes if hb.lanes is None else hb.lanes
+        if lanes == 4 and hb.track_noise:
+            raise ValueError("per-track noise (Q_tracks / R_tracks) runs the lane-per-track mapping only: the quad forward "
+                             "kernel has none, so lanes=4 is refused for this batch")
+        for name in self._IN + self._NOISE_IN:
             a = getattr(hb, name)
             if a is None:
                 self.t[name] = None
@@ -382,7 +475,6 @@ class DeviceBatch:
         self._keep = (hb.H, hb.Q, hb.R)
         s = binding.SteUkfBatchF64()
         s.B, s.Nmax, s.Tmax, s.n = B, N, hb.Tmax, 4
-        lanes = default_lanes if hb.lanes is None else hb.lanes
         if lanes not in (0, 1, 4):
             raise ValueError(f"lanes must be 0 (automatic), 1 or 4, got {lanes!r}")
         s.flags = (binding.STE_FLAG_SHARED_P0 if hb.shared_p0 else 0) | (
@@ -406,6 +498,13 @@ class DeviceBatch:
         s.sm_pos = None if self.sm_pos is None else self.sm_pos.data_ptr()
         s.step_begin = s.step_end = 0
         self.struct = s
+        # per-track noise beside the batch struct (include/ste.h: ste_ukf_noise_f64), or None
+        self.noise = None
+        tq, tr = self.t["Q_tracks"], self.t["R_tracks"]
+        if tq is not None or tr is not None:
+            block2 = tr is not None and r_tracks_block2(hb.R_tracks)
+            self.noise = binding.SteUkfNoiseF64(None if tq is None else tq.data_ptr(), None if tr is None else tr.data_ptr(),
+                                                binding.STE_NOISE_R_BLOCK2 if block2 else 0, 0)
         # The uploads above were queued on the current stream.  One event, recorded now, is what other streams wait on
         # before the first launch (SmootherPipeline.submit): waiting on the current stream *at submit time* would put a
         # marker on the legacy default stream, which every blocking stream synchronises with -- a device-wide barrier in
@@ -441,6 +540,9 @@ class DeviceBatch:
         if not self.hb.shared_p0:
             s.P0 = s.P0 + lo * 8
         w.struct = s
+        if self.noise is not None:  # the two triangles are [10][track_stride] like every per-track array
+            w.noise = binding.SteUkfNoiseF64((self.noise.Q + lo * 8) if self.noise.Q else None,
+                                             (self.noise.R + lo * 8) if self.noise.R else None, self.noise.flags, 0)
         for name in ("fwd_mean", "fwd_cov", "sm_mean", "sm_cov", "sm_pos"):
             t = getattr(self, name)
             setattr(w, name, None if t is None else t[..., lo:hi])
@@ -457,7 +559,7 @@ class DeviceBatch:
         torch = self.torch
         stream = stream or torch.cuda.current_stream(self.device)
         jobs = []
-        for name in self._IN:
+        for name in self._IN + self._NOISE_IN:
             ten = self.t[name]
             if ten is None or (name == "P0" and self.hb.shared_p0):
                 continue
@@ -520,6 +622,10 @@ class DeviceBatch:
         try:
             for k0, k1 in self.slice_bounds(int(s.Nmax), int(slices)):
                 s.step_begin, s.step_end = k0, k1
+                if self.noise is not None:
+                    binding.check(self.lib.ste_ukf_forward_noise_f64(C.byref(s), C.byref(self.noise), None, self._stream(stream)),
+                                  "ste_ukf_forward_noise_f64")
+                    continue
                 binding.check(self.lib.ste_ukf_forward_f64(C.byref(s), self._stream(stream)), "ste_ukf_forward_f64")
         finally:
             s.step_begin = s.step_end = 0
@@ -528,14 +634,22 @@ class DeviceBatch:
 
     def backward(self, stream=None, mark: bool = True):
         self._require_histories("backward()")
-        binding.check(self.lib.ste_urtss_backward_f64(C.byref(self.struct), self._stream(stream)),
-                      "ste_urtss_backward_f64")
+        if self.noise is not None:
+            binding.check(self.lib.ste_urtss_backward_noise_f64(C.byref(self.struct), C.byref(self.noise), self._stream(stream)),
+                          "ste_urtss_backward_noise_f64")
+        else:
+            binding.check(self.lib.ste_urtss_backward_f64(C.byref(self.struct), self._stream(stream)),
+                          "ste_urtss_backward_f64")
         if mark:
             self._mark_use(stream)
 
     def run(self, stream=None):
         self._require_histories("run()")
-        binding.check(self.lib.ste_ukf_urtss_f64(C.byref(self.struct), self._stream(stream)), "ste_ukf_urtss_f64")
+        if self.noise is not None:
+            binding.check(self.lib.ste_ukf_urtss_noise_f64(C.byref(self.struct), C.byref(self.noise), self._stream(stream)),
+                          "ste_ukf_urtss_noise_f64")
+        else:
+            binding.check(self.lib.ste_ukf_urtss_f64(C.byref(self.struct), self._stream(stream)), "ste_ukf_urtss_f64")
         self._mark_use(stream)
 
     def log_likelihood(self, stream=None, nis: bool = False) -> "LogLikelihood":
@@ -568,8 +682,12 @@ class DeviceBatch:
             s.flags = (s.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
             lk = binding.SteUkfLoglikF64(ll.data_ptr(), dof.data_ptr(), nupd.data_ptr(),
                                          None if nis_t is None else nis_t.data_ptr() + 8 * col)
-            binding.check(self.lib.ste_ukf_forward_loglik_f64(C.byref(s), C.byref(lk), self._stream(st)),
-                          "ste_ukf_forward_loglik_f64")
+            if self.noise is not None:
+                binding.check(self.lib.ste_ukf_forward_noise_f64(C.byref(s), C.byref(self.noise), C.byref(lk), self._stream(st)),
+                              "ste_ukf_forward_noise_f64")
+            else:
+                binding.check(self.lib.ste_ukf_forward_loglik_f64(C.byref(s), C.byref(lk), self._stream(st)),
+                              "ste_ukf_forward_loglik_f64")
             self._mark_use(st)
             return LogLikelihood(loglik=ll.cpu().numpy(), dof=dof.cpu().numpy(), nupd=nupd.cpu().numpy(),
                                  status=self.status.cpu().numpy(),
@@ -893,6 +1011,11 @@ class SmootherPipeline:
         torch = self.torch
         if self.closed:
             raise RuntimeError("SmootherPipeline is closed")
+        if (db.noise is not None and self.forward_lanes == 4
+                and not (db.struct.flags & (binding.STE_FLAG_LANES_1 | binding.STE_FLAG_LANES_4))):
+            raise ValueError("this pipeline was built with forward_lanes=4 and the batch has per-track noise (Q_tracks / "
+                             "R_tracks), which runs the lane-per-track mapping only: give the batch lanes=1 or use a "
+                             "lane-per-track pipeline")
         k = self._count
         self._count += 1
         fwd_stream = self.fwd_streams[k % len(self.fwd_streams)]
@@ -977,6 +1100,8 @@ class SmootherPipeline:
             return []
         if self.forward_lanes == 4:
             raise ValueError("scheduled forward launches are lane-per-track (this pipeline was built with forward_lanes=4)")
+        if any(db.noise is not None for db in dbs):
+            raise ValueError("scheduled launches have no per-track noise (Q_tracks / R_tracks): submit() the batches one by one")
         seen = set()
         for db in dbs:
             key = (db.fwd_mean.data_ptr(), db.ntracks)
@@ -1570,7 +1695,8 @@ def run_fleet(fleet, chunk: int = FLEET_CHUNK, device="cuda:0", smooth: bool = T
         measured on a 100 000-track fleet: 7.9-8.1 against 8.4-8.6 ms).  Default (None): yes for a
         resident fleet of up to ``SCHEDULED_FLEET_MAX_WINDOWS`` windows on a lane-per-track pipeline -- a job that is mostly
         fill and drain --, no for longer ones (a long stream of windows re-balances by itself) and for a ``HostBatch``
-        (its windows arrive one upload at a time).
+        (its windows arrive one upload at a time); never for a fleet with per-track noise (``Q_tracks`` / ``R_tracks``:
+        the scheduled launches have none, and an explicit True raises ValueError for it).
     Results are those of ``run_batch`` on the same tracks with the lane-per-track mapping, bit for bit.
     """
     import torch
@@ -1602,6 +1728,10 @@ def run_fleet(fleet, chunk: int = FLEET_CHUNK, device="cuda:0", smooth: bool = T
     B = db.ntracks
     wins = fleet_windows(B, chunk)
     own_pipe = pipeline is None
+    if db.noise is not None:  # per-track noise: per-window launches (the scheduled launches have no per-track form)
+        if scheduled:
+            raise ValueError("run_fleet(scheduled=True): scheduled launches have no per-track noise (Q_tracks / R_tracks)")
+        scheduled = False
     if scheduled is None:
         scheduled = (resident and 1 < len(wins) <= SCHEDULED_FLEET_MAX_WINDOWS and (pipeline is None or pipeline.forward_lanes != 4))
     # (a pipeline built for scheduled launches needs two forward streams, not seven: every stream is a hardware queue, the device has
