@@ -682,7 +682,10 @@ __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], doubl
         // Some lane left the validity range of the branch-free transcendentals (a pole, a step of tens of degrees):
         // the whole fan again with the branching version (device-library sincos / atan2 / asin, out
         // of line, through copies so that the hot path's arrays stay in registers), same formulas for the lanes that
-        // were fine, then the same moment sums.
+        // were fine, then the same moment sums.  (Same formulas, not the same bits: the branching version's centre point
+        // and pairs go through one-at-a-time code whose last bits differ in places, so an ordinary track that shares a
+        // wave with a lane out of range gets the fallback's bits for that step -- a known dependence on wave neighbours,
+        // DESIGN.md section 5.)
         double xc[4], Tc[4][4], s0c[9][4], sc[9][4];
         STE_UNROLL
         for (int r = 0; r < 4; ++r) {

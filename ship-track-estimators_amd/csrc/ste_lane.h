@@ -109,25 +109,46 @@ __device__ __forceinline__ void dbg_sweep_probe(const double (&a)[10], int sweep
 }
 #endif
 
+// One cyclic sweep.
+__device__ __forceinline__ void jacobi_sweep_p(double (&a)[10], double (&V)[4][4]) {
+    jacobi_rot_p<0, 1>(a, V);
+    jacobi_rot_p<2, 3>(a, V);
+    jacobi_rot_p<0, 2>(a, V);
+    jacobi_rot_p<1, 3>(a, V);
+    jacobi_rot_p<0, 3>(a, V);
+    jacobi_rot_p<1, 2>(a, V);
+}
+
 // Cyclic sweeps until no lane of the wave asks for one (the criterion of the rotations, evaluated up front, so that a
 // sweep in which nothing would rotate is not run at all); a lane's rotations are gated by its own data only, so a
 // track's result does not depend on which tracks share its wave.
+// kPeel (the forward step's square root, every step): the two unasked sweeps are straight-line code in front of a loop that
+// starts at sweep 2 -- as the loop's first two trips they paid its control and the moves of its loop-carried values twice
+// per solve.  Same rotations in the same order, same criterion, same cap.  The pseudo-inverse (a rare, out-of-line path
+// of the smoothers) keeps the plain loop: peeled, its working set raised the recurrence smoother's allocation from 240
+// registers to 280, and a forward and a smoother wave no longer shared a SIMD.
+template <bool kPeel>
 __device__ __forceinline__ bool jacobi_sweeps_p(double (&a)[10], double (&V)[4][4]) {
-    for (int sweep = 0; sweep <= kMaxSweeps; ++sweep) {
+    // The first two sweeps run unasked: measured on the bench batch, 99.6 % of the solves need at least two (a warm
+    // start leaves off-diagonals of 1e-3 ... 1e-1 of the diagonal, one sweep 1e-6 ... 1e-4), and a sweep over an
+    // already diagonal matrix only rotates by the identity.
+    if constexpr (kPeel) {
 #ifdef STE_DEBUG_SWEEPS  // profiles/tools/jacobi_sweep_probe.py: how many sweeps a fan costs, and how many of their rotations any lane needed
+        dbg_sweep_probe(a, 0);
+#endif
+        jacobi_sweep_p(a, V);
+#ifdef STE_DEBUG_SWEEPS
+        dbg_sweep_probe(a, 1);
+#endif
+        jacobi_sweep_p(a, V);
+    }
+    for (int sweep = kPeel ? 2 : 0; sweep <= kMaxSweeps; ++sweep) {
+#ifdef STE_DEBUG_SWEEPS
         dbg_sweep_probe(a, sweep);
 #endif
-        // The first two sweeps run unasked: measured on the bench batch, 99.6 % of the solves need at least two (a warm
-        // start leaves off-diagonals of 1e-3 ... 1e-1 of the diagonal, one sweep 1e-6 ... 1e-4), and a sweep over an
-        // already diagonal matrix only rotates by the identity.
         if (sweep >= 2 && !__any(jacobi_needs_sweep(a))) return true;
         if (sweep == kMaxSweeps) break;
-        jacobi_rot_p<0, 1>(a, V);
-        jacobi_rot_p<2, 3>(a, V);
-        jacobi_rot_p<0, 2>(a, V);
-        jacobi_rot_p<1, 3>(a, V);
-        jacobi_rot_p<0, 3>(a, V);
-        jacobi_rot_p<1, 2>(a, V);
+        jacobi_sweep_p(a, V);
     }
     return !jacobi_needs_sweep(a);
 }
@@ -171,7 +192,7 @@ __device__ __forceinline__ int sym_sqrt_p(const double (&P)[10], double scale, d
             for (int c = 0; c < 4; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
         }
     }
-    int st = jacobi_sweeps_p(a, V) ? 0 : 0x4;
+    int st = jacobi_sweeps_p<true>(a, V) ? 0 : 0x4;
     double Vf[4][4];
     STE_UNROLL
     for (int i = 0; i < 4; ++i) {
@@ -319,7 +340,7 @@ __device__ __forceinline__ int sym_pinv_p(const double (&A)[10], double (&Ai)[10
         STE_UNROLL
         for (int c = 0; c < 4; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
     }
-    const int st = jacobi_sweeps_p(a, V) ? 0 : 0x4;
+    const int st = jacobi_sweeps_p<false>(a, V) ? 0 : 0x4;
     double smax = 0.0;
     STE_UNROLL
     for (int i = 0; i < 4; ++i) smax = fmax(smax, fabs(a[tix(i, i)]));

@@ -212,8 +212,18 @@ __device__ __forceinline__ void sincos_delta(double d, double& s, double& c) {
 // register before its FMA (two s_mov_b32 or two v_accvgpr_read: there are more coefficients than registers to keep them
 // in), so evaluating the same polynomial for three arguments side by side fetches each coefficient once instead of three
 // times.  They are branch-free: `ok` collects the conditions under which the fast paths are valid and the caller redoes
-// the rare failing case with the branching scalar functions above (same formulas, so lanes that were fine get the same
-// bits either way).
+// the rare failing case with the branching scalar functions above (same formulas for the lanes that were fine; their
+// last bits can differ from the fast path's, see lane_predict).
+//
+// The range tests of one call are folded into an extremum per CLASS of test first -- max |x|, max |d|, min over b and h2
+// (the same limit), max |xs|, min cd -- and each extremum is compared once: a v_max_f64 / v_min_f64 where
+// `ok = ok && (...)` per value cost a v_cmp and an s_and_b64 of the lane mask, a scalar instruction a lone wave pays a full
+// issue slot for.  Only the relational test of the arctangent's operands is made per point.
+// fmax / fmin drop a NaN operand where `!(x <= limit)` caught it.  Nothing is lost for a lane whose inputs are finite, the
+// only lanes whose verdict is read: a tested value is NaN only after an earlier test has failed (a product of finite
+// numbers is finite or inf, never NaN; with every |x| < 2^20 and |d| <= pi/4 all sines and cosines, and so b, h2 and cd, are
+// finite; xs is NaN only for h2 == 0, which the minimum catches).  Every caller reads the verdict as `!ok && (its inputs
+// are finite)`.  (A finiteness test of the fan's outputs ANDed in on top of that was tried and dropped: DESIGN.md section 5.)
 // ---------------------------------------------------------------------------------------------------------------
 // Where the sin / cos kernel polynomials take their coefficients from.  As literals (TrigLit) every use needs the 64-bit
 // constant in a register pair first -- two s_mov_b32, or, once the kernel has more live scalars than SGPRs (the
@@ -287,11 +297,12 @@ __device__ __forceinline__ void sincos_fast_n(const double (&x)[N], double (&s)[
                                               const K& k = K()) {
 #pragma clang fp contract(off)  // explicit fma() only: the same bits in every kernel this is inlined into
     double n[N], r[N], sk[N], ck[N];
+    double x_max = fabs(x[0]);
     STE_UNROLL
-    for (int i = 0; i < N; ++i) {
-        ok = ok && (fabs(x[i]) < 1048576.0);
-        n[i] = rint(x[i] * 0.63661977236758134308);
-    }
+    for (int i = 1; i < N; ++i) x_max = fmax(x_max, fabs(x[i]));
+    ok = ok && (x_max < 1048576.0);
+    STE_UNROLL
+    for (int i = 0; i < N; ++i) n[i] = rint(x[i] * 0.63661977236758134308);
     STE_UNROLL
     for (int i = 0; i < N; ++i) r[i] = fma(-n[i], 1.57079632679489655800e+00, x[i]);
     STE_UNROLL
@@ -312,8 +323,10 @@ template <int N, class K = TrigLit>
 __device__ __forceinline__ void sincos_delta_n(const double (&d)[N], double (&s)[N], double (&c)[N], bool& ok,
                                                const K& k = K()) {
 #pragma clang fp contract(off)  // explicit fma() only: the same bits in every kernel this is inlined into
+    double d_max = fabs(d[0]);
     STE_UNROLL
-    for (int i = 0; i < N; ++i) ok = ok && (fabs(d[i]) <= 0.78539816339744828);
+    for (int i = 1; i < N; ++i) d_max = fmax(d_max, fabs(d[i]));
+    ok = ok && (d_max <= 0.78539816339744828);
     sincos_kernel_n<N, K>(d, s, c, k);
 }
 
@@ -424,9 +437,16 @@ __device__ __forceinline__ void geodetic_finish_n(const double (&lon_r)[N], cons
         const double sdca = sd[i] * ca[i];
         b[i] = fma(cp[i], cd[i], -(sp[i] * sdca));
         sl[i] = fma(sp[i], cd[i], cp[i] * sdca);
-        ok = ok && (b[i] > 1e-300) && (fabs(a[i]) <= 0.4375 * b[i]);
+        ok = ok && (fabs(a[i]) <= 0.4375 * b[i]);
         h2[i] = fma(a[i], a[i], b[i] * b[i]);
     }
+    double bh_min = fmin(b[0], h2[0]), xs_max, cd_min = cd[0];  // b > 1e-300 and h2 > 1e-300; cd > 0: see geodetic_finish
+    STE_UNROLL
+    for (int i = 1; i < N; ++i) {
+        bh_min = fmin(bh_min, fmin(b[i], h2[i]));
+        cd_min = fmin(cd_min, cd[i]);
+    }
+    ok = ok && (bh_min > 1e-300) && (cd_min > 0.0);
     STE_UNROLL
     for (int i = 0; i < N; ++i) qa[i] = div_pos(a[i], b[i]);
     atan_small_n<N, K>(qa, at, k);
@@ -434,8 +454,11 @@ __device__ __forceinline__ void geodetic_finish_n(const double (&lon_r)[N], cons
     for (int i = 0; i < N; ++i) {
         const double cl = h2[i] * rsqrt_fast(h2[i]);
         xs[i] = fma(sl[i], cp[i], -(cl * sp[i]));
-        ok = ok && (fabs(xs[i]) <= 0.5) && (h2[i] > 1e-300) && (cd[i] > 0.0);  // cd > 0: see geodetic_finish
     }
+    xs_max = fabs(xs[0]);
+    STE_UNROLL
+    for (int i = 1; i < N; ++i) xs_max = fmax(xs_max, fabs(xs[i]));
+    ok = ok && (xs_max <= 0.5);
     asin_small_n<N, K>(xs, as, k);
     STE_UNROLL
     for (int i = 0; i < N; ++i) {
