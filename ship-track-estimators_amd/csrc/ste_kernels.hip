@@ -22,8 +22,8 @@
 //                                        recurrence, one lane or one DPP quad per track -- bit-identical to urtss_recur_l1
 //   urtss_backward_l1                    stand-alone smoother that recomputes everything (rts_work == NULL)
 //   ukf_forward_tn, urtss_recur_tn,      the lane-per-track forward pass (with or without the likelihood) and the smoothers
-//     urtss_gains_all_tn,                that read Q, with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
-//     urtss_backward_tn                  device functions, the track's matrices loaded from NoiseParams
+//     urtss_gains_all<.., true>,         that read Q, with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
+//     urtss_backward_l1<true>            device functions and kernels, the track's matrices loaded from NoiseParams
 //   predict / update / robust_terms / geodetic / sigma_points kernels   single-step API parity
 // All per-step inputs/outputs are SoA with the track index fastest, so a wave's accesses are contiguous runs.
 //
@@ -1603,18 +1603,139 @@ __device__ __forceinline__ void store_pos(const KParams& p, size_t row, size_t B
     }
 }
 
-// (the body lives in ste_urtss_backward_body.h, shared with urtss_backward_tn below)
-__global__ __launch_bounds__(64) void urtss_backward_l1(const KParams p) {
-#define STE_BWD_Q(r, c) p.m.Q[(r) * 4 + (c)]
-#include "ste_urtss_backward_body.h"
-#undef STE_BWD_Q
-}
-// The same smoother with track t's own Q (ste_urtss_backward_noise_f64): nz.Q[tix(r, c) * ld + t], loaded where it is
-// used.  nz.Q is not NULL here: without a per-track Q launch_backward_tn takes urtss_backward_l1.
-__global__ __launch_bounds__(64) void urtss_backward_tn(const KParams p, const NoiseParams nz) {
-#define STE_BWD_Q(r, c) nz.Q[(size_t)tix(r, c) * B + t]
-#include "ste_urtss_backward_body.h"
-#undef STE_BWD_Q
+// kTrackNoise: track t's own Q (ste_urtss_backward_noise_f64), nz.Q[tix(r, c) * ld + t], instead of the shared p.m.Q.  nz.Q is
+// not NULL there (launch_backward takes <false> without a per-track Q), and <false> never reads nz.  The body stays in the
+// kernel: moved into an inline function it is optimised before it meets the kernel's arguments and comes out differently.
+template <bool kTrackNoise>
+__global__ __launch_bounds__(64) void urtss_backward_l1(const KParams p, const NoiseParams nz) {
+    const size_t B = (size_t)p.ld;
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= (size_t)p.B) return;
+    auto track_Q = [&](int r, int c) -> double {  // entry (r, c) of this track's process noise, loaded where it is used
+        if constexpr (kTrackNoise)
+            return nz.Q[(size_t)tix(r, c) * B + t];
+        else
+            return p.m.Q[r * 4 + c];
+    };
+    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
+    const double* srp = p.sog_rate_rts ? p.sog_rate_rts : p.sog_rate;
+    const double* crp = p.cog_rate_rts ? p.cog_rate_rts : p.cog_rate;
+
+    // row ns: smoothed = filtered
+    double xs[4], Ps[4][4];
+    load_vec(p.fwd_mean, (size_t)ns, B, t, xs);
+    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
+    load_cov_m(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
+    store_vec(p.sm_mean, (size_t)ns, B, t, xs);
+    store_cov_m(p.sm_cov, packed, (size_t)ns, B, t, Ps);
+    store_pos(p, (size_t)ns, B, t, xs);
+
+    // filtered row of the first step to process, prefetched
+    double xn[4] = {0, 0, 0, 0}, Pn[4][4] = {};
+    double dt_n = 0.0, sr_n = 0.0, cr_n = 0.0;
+    if (ns > 0) {
+        load_vec(p.fwd_mean, (size_t)ns - 1, B, t, xn);
+        load_cov_m(p.fwd_cov, packed, (size_t)ns - 1, B, t, Pn);
+        const size_t o = (size_t)(ns - 1) * B + t;
+        dt_n = p.dt[o];
+        sr_n = srp[o];
+        cr_n = crp[o];
+    }
+    int st = 0;
+    EigBasis fan_basis, pb_basis;
+    fan_basis.valid = false;
+    pb_basis.valid = false;
+    for (int k = p.Nmax - 1; k >= 0; --k) {
+        if (!__any(k < ns)) continue;  // ragged batch: nobody in this wave has reached its last step yet
+        if (k < ns) {
+            double xk[4], Pk[4][4];
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                xk[r] = xn[r];
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) Pk[r][c] = Pn[r][c];
+            }
+            const double dt = dt_n, sr = sr_n, cr = cr_n;
+            if (k > 0) {
+                load_vec(p.fwd_mean, (size_t)k - 1, B, t, xn);
+                load_cov_m(p.fwd_cov, packed, (size_t)k - 1, B, t, Pn);
+                const size_t o = (size_t)(k - 1) * B + t;
+                dt_n = p.dt[o];
+                sr_n = srp[o];
+                cr_n = crp[o];
+            }
+            double sig0[9][4], sig[9][4];
+            if ((k & (kColdEvery - 1)) == kColdEvery - 1) {
+                fan_basis.valid = false;
+                pb_basis.valid = false;
+            }
+            st |= propagate_fan<true>(xk, Pk, p.m.fan_scale, dt, sr, cr, sig0, sig, fan_basis);
+            double xb[4];
+            STE_UNROLL
+            for (int c = 0; c < 4; ++c) {
+                double acc = 0.0;
+                STE_UNROLL
+                for (int j = 1; j < 9; ++j) acc += sig[j][c];
+                xb[c] = fma(p.m.w0, sig[0][c], p.m.wi * acc);
+            }
+            if (p.noise_rts) {
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) xb[c] += p.noise_rts[((size_t)k * 4 + c) * B + t];
+            }
+            // P_b is centred on the filtered mean x_k, not on x_b (unscented.py:324-325)
+            double dk[9][4], db[9][4];
+            STE_UNROLL
+            for (int j = 0; j < 9; ++j) {
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) {
+                    dk[j][c] = sig[j][c] - xk[c];
+                    db[j][c] = sig[j][c] - xb[c];
+                    sig0[j][c] -= xk[c];
+                }
+            }
+            double Pb[4][4], D[4][4], Pbi[4][4], K[4][4];
+            weighted_outer<true>(dk, dk, p.m.w0, p.m.wi, Pb);
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) Pb[r][c] += track_Q(r, c);
+            }
+            weighted_outer<false>(sig0, db, p.m.w0, p.m.wi, D);  // unscented.py:328-330
+            st |= sym_pinv4<true>(Pb, Pbi, pb_basis);
+            pb_basis.valid = true;
+            mm(D, Pbi, K);  // unscented.py:333
+            double y[4];
+            STE_UNROLL
+            for (int c = 0; c < 4; ++c) y[c] = xs[c] - xb[c];
+            y[3] = wrap180(y[3]);
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                double acc = xk[r];
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) acc = fma(K[r][c], y[c], acc);
+                xs[r] = acc;
+            }
+            xs[3] = floored_mod(xs[3], 360.0);
+            double dP[4][4], KdP[4][4], U[4][4];
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) dP[r][c] = Ps[r][c] - Pb[r][c];
+            }
+            mm(K, dP, KdP);
+            mmt_sym(KdP, K, U);
+            STE_UNROLL
+            for (int r = 0; r < 4; ++r) {
+                STE_UNROLL
+                for (int c = 0; c < 4; ++c) Ps[r][c] = Pk[r][c] + U[r][c];
+            }
+            store_vec(p.sm_mean, (size_t)k, B, t, xs);
+            store_cov_m(p.sm_cov, packed, (size_t)k, B, t, Ps);
+            store_pos(p, (size_t)k, B, t, xs);
+        }
+    }
+    if (!all_finite(xs, Ps)) st |= STE_STATUS_NAN;
+    if (st) atomicOr(&p.status[t], st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1943,10 +2064,9 @@ __global__ __launch_bounds__(64) void urtss_recur_sched(const SmoothSchedParams 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kLeanK01 = kWorkD, kLeanK23 = kWorkD23;  // K[r][0:2] at kLeanK01 + 2 r, K[r][2:4] at kLeanK23 + 2 r
 
-// (urtss_gains_all_tn below repeats this load / store wrapper for batches with per-track Q: an edit here belongs there too,
-//  or the two stop writing the same bits -- tests/test_ukf_track_noise.py.)
-template <bool kShift>
-__global__ __launch_bounds__(64) void urtss_gains_all(const KParams p) {
+// kTrackNoise: this lane's track's four entries of Q (track_q4) go to smoother_step_gain; the shared instantiations never read nz.
+template <bool kShift, bool kTrackNoise>
+__global__ __launch_bounds__(64) void urtss_gains_all(const KParams p, const NoiseParams nz) {
     const size_t B = (size_t)p.ld;
     const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (g >= (size_t)p.B * (size_t)p.Nmax) return;
@@ -1966,48 +2086,9 @@ __global__ __launch_bounds__(64) void urtss_gains_all(const KParams p) {
     load_vec(p.fwd_mean, (size_t)k + 1, B, t, xn);
     load_cov_p(p.fwd_cov, packed, (size_t)k + 1, B, t, Pn);
     const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
-    double xb[4], Pb[10], K[4][4];
-    const int st = smoother_step_gain<kShift>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K);
-    double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        w[(kLeanK01 + 2 * r + 0) * B] = K[r][0];
-        w[(kLeanK01 + 2 * r + 1) * B] = K[r][1];
-        w[(kLeanK23 + 2 * r + 0) * B] = K[r][2];
-        w[(kLeanK23 + 2 * r + 1) * B] = K[r][3];
-    }
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) w[(kWorkXb + c) * B] = xb[c];
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) w[(kWorkPb + e) * B] = Pb[e];
-    if (st) atomicOr(&p.status[t], st);
-}
-// urtss_gains_all for a batch with per-track Q: the same loads, the same gain function (smoother_step_gain, with this
-// lane's track's four entries of Q), the same stores.
-template <bool kShift>
-__global__ __launch_bounds__(64) void urtss_gains_all_tn(const KParams p, const NoiseParams nz) {
-    const size_t B = (size_t)p.ld;
-    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= (size_t)p.B * (size_t)p.Nmax) return;
-    const size_t t = g % (size_t)p.B;
-    const int k = (int)(g / (size_t)p.B);
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    if (k >= ns) return;
-    const double fb_raw = p.first_bad[t];
-    if (fb_raw < 0.0) return;  // the rows of this track already hold gains (a repeated backward call)
-    const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
-    const bool all_eig = (p.tuning & 0x100) != 0;
-    const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    RecurRow cur;
-    load_recur_row<kShift>(p, (size_t)k, B, t, always_full, cur);
-    double xn[4], Pn[10];
-    load_vec(p.fwd_mean, (size_t)k + 1, B, t, xn);
-    load_cov_p(p.fwd_cov, packed, (size_t)k + 1, B, t, Pn);
-    const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
-    double xb[4], Pb[10], K[4][4], q4[4];
-    track_q4(p, nz, B, t, q4);
-    const int st = smoother_step_gain<kShift, true>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K, q4);
+    double xb[4], Pb[10], K[4][4], q4[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (kTrackNoise) track_q4(p, nz, B, t, q4);
+    const int st = smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K, q4);
     double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
     STE_UNROLL
     for (int r = 0; r < 4; ++r) {
@@ -2456,7 +2537,7 @@ int ste::abi_check_hip(hipError_t e, const char* what) { return check_hip(e, wha
 
 namespace {
 
-int make_params(const ste_ukf_batch_f64* b, bool need_fwd_in, bool need_sm_out, ste::KParams* kp, bool need_hist = true) {
+int make_params(const ste_ukf_batch_f64* b, bool need_sm_out, ste::KParams* kp, bool need_hist = true) {
     if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
     if (b->n != 4) return fail(STE_EINVAL, "state dimension n must be 4 (heading index 3 is hard-wired, unscented.py:250)");
     if (b->B <= 0) return fail(STE_EINVAL, "B must be > 0");
@@ -2470,7 +2551,6 @@ int make_params(const ste_ukf_batch_f64* b, bool need_fwd_in, bool need_sm_out, 
     if (need_hist && (!b->fwd_mean || !b->fwd_cov)) return fail(STE_EINVAL, "fwd_mean, fwd_cov and status are required");
     if (!b->status) return fail(STE_EINVAL, "fwd_mean, fwd_cov and status are required");
     if (need_sm_out && (!b->sm_mean || !b->sm_cov)) return fail(STE_EINVAL, "sm_mean and sm_cov are required");
-    (void)need_fwd_in;
     kp->B = b->B;
     kp->Nmax = b->Nmax;
     kp->Tmax = b->Tmax;
@@ -2569,15 +2649,39 @@ int slice_params(const ste_ukf_batch_f64* b, ste::KParams* kp) {
     return STE_OK;
 }
 
-int launch_forward(const ste::KParams& kp, hipStream_t s) {
-    const bool robust = kp.m.robust_iters > 0;
-    if (choose_lanes(kp.B, kp.flags) == 4) {
+// A run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+auto with_bool(bool v, F&& f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The instantiations of the lane-per-track forward kernels, in one place: kGains (the smoother's work rows) is free, and
+// (kFastUpd, kRobust) is (0, 0), (1, 0) or (1, 1) -- robust rescaling without the closed-form update runs the
+// <..., false, false> kernel, whose general update reads robust_iters itself.  `f` gets the three as std::bool_constants.
+template <class F>
+auto with_forward_variant(const ste::KParams& kp, F&& f) {
+    return with_bool(kp.rts_work != nullptr, [&](auto gains) {
+        if (kp.fast_upd && kp.m.robust_iters > 0) return f(gains, std::true_type{}, std::true_type{});
+        if (kp.fast_upd) return f(gains, std::true_type{}, std::false_type{});
+        return f(gains, std::false_type{}, std::false_type{});
+    });
+}
+// ... as a number: do two batches take the same instantiation?
+int forward_variant(const ste::KParams& kp) {
+    return with_forward_variant(kp, [](auto gains, auto fast, auto robust) { return gains() | fast() << 1 | robust() << 2; });
+}
+
+// Every forward launch but the scheduled one.  `lp`: with the innovation log-likelihood (lane per track, whole passes: the
+// entry points check); with histories the kernel is the plain pass's, plus the likelihood, without them kLikOnly.  `np`:
+// per-track noise.  Both NULL: the plain pass, quad or lane per track.  `fn`: the entry point, for the message.
+int launch_forward(const char* fn, const ste::KParams& kp, const ste::LikParams* lp, const ste::NoiseParams* np, hipStream_t s) {
+    if (choose_lanes(kp.B, kp.flags) == 4) {  // (never with lp or np: their entry points set STE_FLAG_LANES_1)
         // quads per wave: 16 fill a wave; with fewer tracks than SIMDs to spare every track gets a wave (and a SIMD) of its own,
         // so that no track waits for another's extra sweep, rescaling or slow-path fan (see ukf_forward_q4)
         ste::KParams kq = kp;
         kq.qpw = (int)std::min<size_t>(16, std::max<size_t>(1, ((size_t)kp.B + kQuadSpreadWaves - 1) / kQuadSpreadWaves));
         const unsigned gridq = (unsigned)(((size_t)kp.B + kq.qpw - 1) / kq.qpw);
-        const int which = (robust ? 4 : 0) | (kp.rts_work ? 2 : 0) | (kp.fast_upd ? 1 : 0);
+        const int which = (kp.m.robust_iters > 0 ? 4 : 0) | (kp.rts_work ? 2 : 0) | (kp.fast_upd ? 1 : 0);
         switch (which) {
 #define STE_Q4(n, g, r, f) \
     case n: hipLaunchKernelGGL((ste::ukf_forward_q4<g, r, f>), dim3(gridq), dim3(64), 0, s, kq); break;
@@ -2587,44 +2691,29 @@ int launch_forward(const ste::KParams& kp, hipStream_t s) {
         }
         return check_hip(hipGetLastError(), "ukf_forward_q4 launch");
     }
-    const unsigned grid = (unsigned)((kp.B + 63) / 64);
-    if (kp.fast_upd && robust) {
-        if (kp.rts_work)
-            hipLaunchKernelGGL((ste::ukf_forward_l1<true, true, true>), dim3(grid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL((ste::ukf_forward_l1<false, true, true>), dim3(grid), dim3(64), 0, s, kp);
-    } else if (kp.fast_upd) {
-        if (kp.rts_work)
-            hipLaunchKernelGGL((ste::ukf_forward_l1<true, true>), dim3(grid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL((ste::ukf_forward_l1<false, true>), dim3(grid), dim3(64), 0, s, kp);
-    } else {
-        if (kp.rts_work)
-            hipLaunchKernelGGL((ste::ukf_forward_l1<true, false>), dim3(grid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL((ste::ukf_forward_l1<false, false>), dim3(grid), dim3(64), 0, s, kp);
-    }
-    return check_hip(hipGetLastError(), "ukf_forward launch");
-}
-
-// The forward pass with the innovation log-likelihood: lane per track, whole passes (ste_ukf_forward_loglik_f64 checks).
-// With histories the kernel is the one launch_forward takes (same kGains / kFastUpd / kRobust choice), plus the likelihood.
-int launch_forward_lik(const ste::KParams& kp, const ste::LikParams& lp, hipStream_t s) {
-    const bool robust = kp.m.robust_iters > 0;
-    const unsigned grid = (unsigned)((kp.B + 63) / 64);
-    const int which = (kp.fwd_mean ? 0 : 8) | (kp.rts_work ? 4 : 0) | (kp.fast_upd ? (robust ? 2 : 1) : 0);
-    switch (which) {
-#define STE_LK(n, g, f, r, m) \
-    case n: hipLaunchKernelGGL((ste::ukf_forward_lik<g, f, r, m>), dim3(grid), dim3(64), 0, s, kp, lp); break;
-        STE_LK(0, false, false, false, ste::kLikHist) STE_LK(1, false, true, false, ste::kLikHist)
-        STE_LK(2, false, true, true, ste::kLikHist) STE_LK(4, true, false, false, ste::kLikHist)
-        STE_LK(5, true, true, false, ste::kLikHist) STE_LK(6, true, true, true, ste::kLikHist)
-        STE_LK(8, false, false, false, ste::kLikOnly) STE_LK(9, false, true, false, ste::kLikOnly)
-        STE_LK(10, false, true, true, ste::kLikOnly)
-#undef STE_LK
-        default: return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: rts_work needs the histories");
-    }
-    return check_hip(hipGetLastError(), "ukf_forward_lik launch");
+    const bool hist = kp.fwd_mean != nullptr;  // (missing only with a likelihood: make_params)
+    if (!hist && kp.rts_work) return fail(STE_EINVAL, "%s: rts_work needs the histories", fn);
+    const dim3 grid((unsigned)((kp.B + 63) / 64)), block(64);
+    const ste::LikParams l0 = lp ? *lp : ste::LikParams{nullptr, nullptr, nullptr, nullptr};
+    with_forward_variant(kp, [&](auto gains, auto fast, auto robust) {
+        constexpr bool kG = decltype(gains)::value, kF = decltype(fast)::value, kR = decltype(robust)::value;
+        auto launch = [&](auto lik) {
+            constexpr int kLik = decltype(lik)::value;
+            if (np)
+                hipLaunchKernelGGL((ste::ukf_forward_tn<kG, kF, kR, kLik>), grid, block, 0, s, kp, l0, *np);
+            else if constexpr (kLik != ste::kLikOff)
+                hipLaunchKernelGGL((ste::ukf_forward_lik<kG, kF, kR, kLik>), grid, block, 0, s, kp, l0);
+            else
+                hipLaunchKernelGGL((ste::ukf_forward_l1<kG, kF, kR>), grid, block, 0, s, kp);
+        };
+        if (!lp)
+            launch(std::integral_constant<int, ste::kLikOff>{});
+        else if (hist)
+            launch(std::integral_constant<int, ste::kLikHist>{});
+        else if constexpr (!kG)  // (no histories, no work rows: refused above)
+            launch(std::integral_constant<int, ste::kLikOnly>{});
+    });
+    return check_hip(hipGetLastError(), np ? "ukf_forward_tn launch" : lp ? "ukf_forward_lik launch" : "ukf_forward launch");
 }
 
 // Batches of at most this many tracks smooth with the two-kernel form (urtss_gains_all + urtss_recur_lean): up to there the
@@ -2633,34 +2722,41 @@ int launch_forward_lik(const ste::KParams& kp, const ste::LikParams& lp, hipStre
 // tuning bit 9 (0x200) forces the two-kernel form, bit 10 (0x400) the one-kernel form (tests, measurements); the choice must
 // not change between the backward calls made on one forward result (the first two-kernel call turns the work rows into gains).
 constexpr int kLeanSmootherMaxTracks = 4096;
+bool lean_smoother(const ste::KParams& kp) {
+    return kp.rts_work && kp.Nmax > 0 && ((kp.tuning & 0x200) || (!(kp.tuning & 0x400) && kp.B <= kLeanSmootherMaxTracks));
+}
 
-int launch_backward(const ste::KParams& kp, hipStream_t s) {
-    const unsigned grid = (unsigned)((kp.B + 63) / 64);
-    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts;
-    if (kp.rts_work && kp.Nmax > 0 && ((kp.tuning & 0x200) || (!(kp.tuning & 0x400) && kp.B <= kLeanSmootherMaxTracks))) {
-        const size_t lanes = (size_t)kp.B * (size_t)kp.Nmax;
-        const unsigned ggrid = (unsigned)((lanes + 63) / 64);
-        if (shift)
-            hipLaunchKernelGGL(ste::urtss_gains_all<true>, dim3(ggrid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL(ste::urtss_gains_all<false>, dim3(ggrid), dim3(64), 0, s, kp);
+// `np`: per-track noise, or NULL.  The smoother reads Q alone: without a per-track Q it takes the shared instantiations,
+// and the lean recurrences read no Q at all.
+int launch_backward(const ste::KParams& kp, const ste::NoiseParams* np, hipStream_t s) {
+    const dim3 grid((unsigned)((kp.B + 63) / 64)), block(64);
+    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts, tn = np && np->Q;
+    const ste::NoiseParams nz = tn ? *np : ste::NoiseParams{nullptr, nullptr};
+    auto with_shift_tn = [&](auto&& f) { with_bool(shift, [&](auto sh) { with_bool(tn, [&](auto t) { f(sh, t); }); }); };
+    if (lean_smoother(kp)) {
+        const dim3 ggrid((unsigned)(((size_t)kp.B * (size_t)kp.Nmax + 63) / 64));
+        with_shift_tn([&](auto sh, auto t) {
+            hipLaunchKernelGGL((ste::urtss_gains_all<decltype(sh)::value, decltype(t)::value>), ggrid, block, 0, s, kp, nz);
+        });
         int rc = check_hip(hipGetLastError(), "urtss_gains_all launch");
         if (rc) return rc;
         // the recurrence: a quad per track (16 tracks per wave); tuning bit 11 (0x800) keeps the lane-per-track form
         if (kp.tuning & 0x800)
-            hipLaunchKernelGGL(ste::urtss_recur_lean, dim3(grid), dim3(64), 0, s, kp);
+            hipLaunchKernelGGL(ste::urtss_recur_lean, grid, block, 0, s, kp);
         else
-            hipLaunchKernelGGL(ste::urtss_recur_lean_q4, dim3((unsigned)((kp.B + 15) / 16)), dim3(64), 0, s, kp);
+            hipLaunchKernelGGL(ste::urtss_recur_lean_q4, dim3((unsigned)((kp.B + 15) / 16)), block, 0, s, kp);
         return check_hip(hipGetLastError(), "urtss_recur_lean launch");
     }
     if (kp.rts_work) {
-        if (kp.sog_rate_rts || kp.cog_rate_rts)
-            hipLaunchKernelGGL(ste::urtss_recur_l1<true>, dim3(grid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL(ste::urtss_recur_l1<false>, dim3(grid), dim3(64), 0, s, kp);
+        with_shift_tn([&](auto sh, auto t) {
+            if constexpr (decltype(t)::value)
+                hipLaunchKernelGGL(ste::urtss_recur_tn<decltype(sh)::value>, grid, block, 0, s, kp, nz);
+            else
+                hipLaunchKernelGGL(ste::urtss_recur_l1<decltype(sh)::value>, grid, block, 0, s, kp);
+        });
         return check_hip(hipGetLastError(), "urtss_recur launch");
     }
-    hipLaunchKernelGGL(ste::urtss_backward_l1, dim3(grid), dim3(64), 0, s, kp);
+    with_bool(tn, [&](auto t) { hipLaunchKernelGGL(ste::urtss_backward_l1<decltype(t)::value>, grid, block, 0, s, kp, nz); });
     return check_hip(hipGetLastError(), "urtss_backward launch");
 }
 
@@ -2688,64 +2784,29 @@ void noise_route(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, ste::K
     kp->fast_upd = sel && (nz->flags & STE_NOISE_R_BLOCK2) != 0;
 }
 
-// launch_forward / launch_forward_lik for the per-track instantiations: the same choice of kGains / kFastUpd / kRobust / kLik
-int launch_forward_tn(const ste::KParams& kp, const ste::LikParams* lp, const ste::NoiseParams& np, hipStream_t s) {
-    const bool robust = kp.m.robust_iters > 0;
-    const unsigned grid = (unsigned)((kp.B + 63) / 64);
-    const ste::LikParams l0 = lp ? *lp : ste::LikParams{nullptr, nullptr, nullptr, nullptr};
-    const int which = (lp ? (kp.fwd_mean ? 8 : 16) : 0) | (kp.rts_work ? 4 : 0) | (kp.fast_upd ? (robust ? 2 : 1) : 0);
-    switch (which) {
-#define STE_TN(n, g, f, r, m) \
-    case n: hipLaunchKernelGGL((ste::ukf_forward_tn<g, f, r, m>), dim3(grid), dim3(64), 0, s, kp, l0, np); break;
-        STE_TN(0, false, false, false, ste::kLikOff) STE_TN(1, false, true, false, ste::kLikOff)
-        STE_TN(2, false, true, true, ste::kLikOff) STE_TN(4, true, false, false, ste::kLikOff)
-        STE_TN(5, true, true, false, ste::kLikOff) STE_TN(6, true, true, true, ste::kLikOff)
-        STE_TN(8, false, false, false, ste::kLikHist) STE_TN(9, false, true, false, ste::kLikHist)
-        STE_TN(10, false, true, true, ste::kLikHist) STE_TN(12, true, false, false, ste::kLikHist)
-        STE_TN(13, true, true, false, ste::kLikHist) STE_TN(14, true, true, true, ste::kLikHist)
-        STE_TN(16, false, false, false, ste::kLikOnly) STE_TN(17, false, true, false, ste::kLikOnly)
-        STE_TN(18, false, true, true, ste::kLikOnly)
-#undef STE_TN
-        default: return fail(STE_EINVAL, "ste_ukf_forward_noise_f64: rts_work needs the histories");
-    }
-    return check_hip(hipGetLastError(), "ukf_forward_tn launch");
+// "whole passes only", for the entry point `fn`; `why`: what stands in the way of time slices, or where they go instead
+int whole_passes(const char* fn, const ste_ukf_batch_f64* b, const char* why) {
+    if (b->step_begin == 0 && (b->step_end == 0 || b->step_end == b->Nmax)) return STE_OK;
+    snprintf(g_err, sizeof(g_err), "%s runs whole passes: %s", fn, why);
+    return STE_EINVAL;
 }
 
-// launch_backward for a batch with per-track Q: the same choice of smoother form; the lean recurrences read no Q and run as they are
-int launch_backward_tn(const ste::KParams& kp, const ste::NoiseParams& np, hipStream_t s) {
-    if (!np.Q) return launch_backward(kp, s);  // the smoother never reads R
-    const unsigned grid = (unsigned)((kp.B + 63) / 64);
-    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts;
-    if (kp.rts_work && kp.Nmax > 0 && ((kp.tuning & 0x200) || (!(kp.tuning & 0x400) && kp.B <= kLeanSmootherMaxTracks))) {
-        const size_t lanes = (size_t)kp.B * (size_t)kp.Nmax;
-        const unsigned ggrid = (unsigned)((lanes + 63) / 64);
-        if (shift)
-            hipLaunchKernelGGL(ste::urtss_gains_all_tn<true>, dim3(ggrid), dim3(64), 0, s, kp, np);
-        else
-            hipLaunchKernelGGL(ste::urtss_gains_all_tn<false>, dim3(ggrid), dim3(64), 0, s, kp, np);
-        int rc = check_hip(hipGetLastError(), "urtss_gains_all_tn launch");
-        if (rc) return rc;
-        if (kp.tuning & 0x800)
-            hipLaunchKernelGGL(ste::urtss_recur_lean, dim3(grid), dim3(64), 0, s, kp);
-        else
-            hipLaunchKernelGGL(ste::urtss_recur_lean_q4, dim3((unsigned)((kp.B + 15) / 16)), dim3(64), 0, s, kp);
-        return check_hip(hipGetLastError(), "urtss_recur_lean launch");
-    }
-    if (kp.rts_work) {
-        if (shift)
-            hipLaunchKernelGGL(ste::urtss_recur_tn<true>, dim3(grid), dim3(64), 0, s, kp, np);
-        else
-            hipLaunchKernelGGL(ste::urtss_recur_tn<false>, dim3(grid), dim3(64), 0, s, kp, np);
-        return check_hip(hipGetLastError(), "urtss_recur_tn launch");
-    }
-    hipLaunchKernelGGL(ste::urtss_backward_tn, dim3(grid), dim3(64), 0, s, kp, np);
-    return check_hip(hipGetLastError(), "urtss_backward_tn launch");
-}
-
-// which instantiation of the lane-per-track forward kernel a batch takes (launch_forward's own choice, as a number)
-int forward_variant(const ste::KParams& kp) {
-    const bool robust = kp.m.robust_iters > 0;
-    return (kp.fast_upd ? (robust ? 4 : 2) : 0) | (kp.rts_work ? 1 : 0);
+// What a forward pass with the innovation log-likelihood asks of its arguments, before make_params (b is not NULL).  `hist`:
+// the pass writes its histories too.  The likelihood kernels are lane per track (ste_ukf_forward_noise_f64 has refused the
+// quad mapping before it comes here, in words of its own).
+int lik_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_loglik_f64* l, ste::LikParams* lp, bool* hist) {
+    if (!l) return fail(STE_EINVAL, "%s: the likelihood outputs (l) are NULL", fn);
+    if (!l->loglik) return fail(STE_EINVAL, "%s: l->loglik is required", fn);
+    *hist = b->fwd_mean != nullptr;
+    if (*hist != (b->fwd_cov != nullptr))
+        return fail(STE_EINVAL, "%s: fwd_mean and fwd_cov go together: both (histories) or neither (the likelihood alone)", fn);
+    if (!*hist && b->rts_work)
+        return fail(STE_EINVAL, "%s: rts_work needs the histories (the smoother reads both); pass fwd_mean and fwd_cov, or no "
+                                "rts_work", fn);
+    if (b->flags & STE_FLAG_LANES_4)
+        return fail(STE_EINVAL, "%s runs the lane-per-track mapping only: STE_FLAG_LANES_4 is refused", fn);
+    *lp = {l->loglik, l->dof, l->nupd, l->nis};
+    return whole_passes(fn, b, "the likelihood sums over every update, so time slices (step_begin / step_end) are refused");
 }
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -2836,35 +2897,25 @@ int ste_stream_destroy(void* stream) {
 
 int ste_ukf_forward_f64(const ste_ukf_batch_f64* b, void* stream) {
     ste::KParams kp;
-    int rc = make_params(b, false, false, &kp);
+    int rc = make_params(b, false, &kp);
     if (rc) return rc;
     rc = slice_params(b, &kp);
     if (rc) return rc;
-    return launch_forward(kp, (hipStream_t)stream);
+    return launch_forward("ste_ukf_forward_f64", kp, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ste_ukf_forward_loglik_f64(const ste_ukf_batch_f64* b, const ste_ukf_loglik_f64* l, void* stream) {
+    const char* fn = "ste_ukf_forward_loglik_f64";
     if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
-    if (!l) return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: the likelihood outputs (l) are NULL");
-    if (!l->loglik) return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: l->loglik is required");
-    const bool hist = b->fwd_mean != nullptr;
-    if (hist != (b->fwd_cov != nullptr))
-        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: fwd_mean and fwd_cov go together: both (histories) or neither "
-                                "(the likelihood alone)");
-    if (!hist && b->rts_work)
-        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64: rts_work needs the histories (the smoother reads both); pass "
-                                "fwd_mean and fwd_cov, or no rts_work");
-    if (b->flags & STE_FLAG_LANES_4)
-        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64 runs the lane-per-track mapping only: STE_FLAG_LANES_4 is refused");
-    if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
-        return fail(STE_EINVAL, "ste_ukf_forward_loglik_f64 runs whole passes: the likelihood sums over every update, so time "
-                                "slices (step_begin / step_end) are refused");
+    ste::LikParams lp;
+    bool hist;
+    int rc = lik_params(fn, b, l, &lp, &hist);
+    if (rc) return rc;
     ste::KParams kp;
-    int rc = make_params(b, false, false, &kp, hist);
+    rc = make_params(b, false, &kp, hist);
     if (rc) return rc;
     kp.flags |= STE_FLAG_LANES_1;
-    const ste::LikParams lp = {l->loglik, l->dof, l->nupd, l->nis};
-    return launch_forward_lik(kp, lp, (hipStream_t)stream);
+    return launch_forward(fn, kp, &lp, nullptr, (hipStream_t)stream);
 }
 
 size_t ste_ukf_forward_sched_workspace(int32_t nwindows, int32_t max_slices, int64_t ntiles_total, int32_t nrounds,
@@ -2910,7 +2961,7 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
     char* hw = (char*)sc->host_ws;
     ste::KParams* kps = (ste::KParams*)(hw + lay.kps);
     // parameter block of window w for the run of slices [q0, q1]: built when a (merged) item first needs it
-    int variant = -1;
+    const ste::KParams* first = nullptr;  // the first block built: every other takes the same kernel
     std::vector<char> have(nkp, 0);
     auto run_index = [&](int w, int q0, int q1) { return kp0[w] + q0 * nslices[w] - q0 * (q0 - 1) / 2 + (q1 - q0); };
     auto run_params = [&](int w, int q0, int q1, int* index) -> int {
@@ -2922,14 +2973,13 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
         b.step_begin = q0 * step;
         b.step_end = std::min(b.Nmax, (q1 + 1) * step);
         ste::KParams* kp = kps + k;
-        int rc = make_params(&b, false, false, kp);
+        int rc = make_params(&b, false, kp);
         if (rc) return rc;
         rc = slice_params(&b, kp);
         if (rc) return rc;
-        const int v = forward_variant(*kp);
-        if (variant >= 0 && v != variant)
+        if (first && forward_variant(*kp) != forward_variant(*first))
             return fail(STE_EINVAL, "scheduled forward pass: the windows must agree on H / R structure, robust flag and rts_work (one kernel runs them all)");
-        variant = v;
+        if (!first) first = kp;
         have[(size_t)k] = 1;
         return STE_OK;
     };
@@ -3018,14 +3068,11 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
     sp.timeout_ticks = (unsigned long long)((sc->timeout_s > 0 ? sc->timeout_s : 2.0) * 1e8);
     sp.started = sc->started;
     const dim3 grid((unsigned)sc->nwaves), block(64);
-    switch (variant) {
-#define STE_SCHED(n, g, f, r) \
-    case n: hipLaunchKernelGGL((ste::ukf_forward_sched<g, f, r>), grid, block, 0, s, sp); break;
-        STE_SCHED(0, false, false, false) STE_SCHED(1, true, false, false) STE_SCHED(2, false, true, false)
-        STE_SCHED(3, true, true, false) STE_SCHED(4, false, true, true) STE_SCHED(5, true, true, true)
-#undef STE_SCHED
-        default: return fail(STE_EINVAL, "scheduled forward pass: no kernel variant");
-    }
+    if (!first) return fail(STE_EINVAL, "scheduled forward pass: no kernel variant");
+    with_forward_variant(*first, [&](auto gains, auto fast, auto robust) {
+        hipLaunchKernelGGL((ste::ukf_forward_sched<decltype(gains)::value, decltype(fast)::value, decltype(robust)::value>), grid, block,
+                           0, s, sp);
+    });
     return check_hip(hipGetLastError(), "ukf_forward_sched launch");
 }
 
@@ -3069,12 +3116,12 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
         const ste_ukf_batch_f64& b = sc->windows[w];
         if (b.B <= 0 || b.Nmax <= 0) return fail(STE_EINVAL, "scheduled smoother: a window has B <= 0 or Nmax <= 0");
         if (b.step_begin != 0 || b.step_end != 0) return fail(STE_EINVAL, "scheduled smoother: windows must not carry a step range of their own");
-        int rc = make_params(&b, true, true, kps + w);
+        int rc = make_params(&b, true, kps + w);
         if (rc) return rc;
         const ste::KParams& kp = kps[w];
         // one kernel runs every window: the one-kernel smoother from the forward pass's work rows (what launch_backward picks
         // for a batch of more than kLeanSmootherMaxTracks tracks), with or without rates of its own
-        if (!kp.rts_work || (kp.tuning & 0x200) || (!(kp.tuning & 0x400) && kp.B <= kLeanSmootherMaxTracks))
+        if (!kp.rts_work || lean_smoother(kp))
             return fail(STE_EINVAL, "scheduled smoother: every window must take the one-kernel smoother (rts_work, more than 4096 tracks or tuning bit 10)");
         const int sh = (kp.sog_rate_rts || kp.cog_rate_rts) ? 1 : 0;
         if (shift >= 0 && sh != shift) return fail(STE_EINVAL, "scheduled smoother: the windows must agree on smoother rates (one kernel runs them all)");
@@ -3118,20 +3165,21 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
 
 int ste_urtss_backward_f64(const ste_ukf_batch_f64* b, void* stream) {
     ste::KParams kp;
-    int rc = make_params(b, true, true, &kp);
+    int rc = make_params(b, true, &kp);
     if (rc) return rc;
-    return launch_backward(kp, (hipStream_t)stream);
+    return launch_backward(kp, nullptr, (hipStream_t)stream);
 }
 
 int ste_ukf_urtss_f64(const ste_ukf_batch_f64* b, void* stream) {
+    const char* fn = "ste_ukf_urtss_f64";
     ste::KParams kp;
-    int rc = make_params(b, false, true, &kp);
+    int rc = make_params(b, true, &kp);
     if (rc) return rc;
-    if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
-        return fail(STE_EINVAL, "ste_ukf_urtss_f64 runs whole passes: time slices go through ste_ukf_forward_f64");
-    rc = launch_forward(kp, (hipStream_t)stream);
+    rc = whole_passes(fn, b, "time slices go through ste_ukf_forward_f64");
     if (rc) return rc;
-    return launch_backward(kp, (hipStream_t)stream);
+    rc = launch_forward(fn, kp, nullptr, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_backward(kp, nullptr, (hipStream_t)stream);
 }
 
 int ste_ukf_forward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_loglik_f64* l, void* stream) {
@@ -3139,30 +3187,21 @@ int ste_ukf_forward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f6
     ste::NoiseParams np;
     int rc = noise_params(fn, b, nz, &np);
     if (rc) return rc;
-    ste::KParams kp;
-    if (l) {  // ste_ukf_forward_loglik_f64's own checks
-        if (!l->loglik) return fail(STE_EINVAL, "%s: l->loglik is required", fn);
-        const bool hist = b->fwd_mean != nullptr;
-        if (hist != (b->fwd_cov != nullptr))
-            return fail(STE_EINVAL, "%s: fwd_mean and fwd_cov go together: both (histories) or neither (the likelihood alone)", fn);
-        if (!hist && b->rts_work)
-            return fail(STE_EINVAL, "%s: rts_work needs the histories (the smoother reads both); pass fwd_mean and fwd_cov, or no "
-                                    "rts_work", fn);
-        if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
-            return fail(STE_EINVAL, "%s with l != NULL runs whole passes: the likelihood sums over every update, so time slices "
-                                    "(step_begin / step_end) are refused", fn);
-        rc = make_params(b, false, false, &kp, hist);
+    ste::LikParams lp;
+    bool hist = true;
+    if (l) {
+        rc = lik_params(fn, b, l, &lp, &hist);
         if (rc) return rc;
-        noise_route(b, nz, &kp);
-        const ste::LikParams lp = {l->loglik, l->dof, l->nupd, l->nis};
-        return launch_forward_tn(kp, &lp, np, (hipStream_t)stream);
     }
-    rc = make_params(b, false, false, &kp);
+    ste::KParams kp;
+    rc = make_params(b, false, &kp, hist);
     if (rc) return rc;
     noise_route(b, nz, &kp);
-    rc = slice_params(b, &kp);
-    if (rc) return rc;
-    return launch_forward_tn(kp, nullptr, np, (hipStream_t)stream);
+    if (!l) {  // (with the likelihood: whole passes, lik_params)
+        rc = slice_params(b, &kp);
+        if (rc) return rc;
+    }
+    return launch_forward(fn, kp, l ? &lp : nullptr, &np, (hipStream_t)stream);
 }
 
 int ste_urtss_backward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream) {
@@ -3170,24 +3209,25 @@ int ste_urtss_backward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise
     int rc = noise_params("ste_urtss_backward_noise_f64", b, nz, &np);
     if (rc) return rc;
     ste::KParams kp;
-    rc = make_params(b, true, true, &kp);
+    rc = make_params(b, true, &kp);
     if (rc) return rc;
-    return launch_backward_tn(kp, np, (hipStream_t)stream);
+    return launch_backward(kp, &np, (hipStream_t)stream);
 }
 
 int ste_ukf_urtss_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream) {
+    const char* fn = "ste_ukf_urtss_noise_f64";
     ste::NoiseParams np;
-    int rc = noise_params("ste_ukf_urtss_noise_f64", b, nz, &np);
+    int rc = noise_params(fn, b, nz, &np);
     if (rc) return rc;
     ste::KParams kp;
-    rc = make_params(b, false, true, &kp);
+    rc = make_params(b, true, &kp);
     if (rc) return rc;
-    if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
-        return fail(STE_EINVAL, "ste_ukf_urtss_noise_f64 runs whole passes: time slices go through ste_ukf_forward_noise_f64");
+    rc = whole_passes(fn, b, "time slices go through ste_ukf_forward_noise_f64");
+    if (rc) return rc;
     noise_route(b, nz, &kp);
-    rc = launch_forward_tn(kp, nullptr, np, (hipStream_t)stream);
+    rc = launch_forward(fn, kp, nullptr, &np, (hipStream_t)stream);
     if (rc) return rc;
-    return launch_backward_tn(kp, np, (hipStream_t)stream);
+    return launch_backward(kp, &np, (hipStream_t)stream);
 }
 
 int ste_geodetic_dynamics_f64(int64_t count, const double* x, const double* dt, const double* sog_rate,
