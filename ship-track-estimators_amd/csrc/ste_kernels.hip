@@ -2452,8 +2452,11 @@ __global__ __launch_bounds__(64) void predict_kernel(size_t count, const Mats m,
     double xi[4], Pi[4][4];
     load_vec(x, 0, count, i, xi);
     load_mat(P, 0, count, i, Pi);
+    // the inputs too: the Jacobi sweeps skip a rotation whose pivot is NaN, so a NaN in an off-diagonal entry of P alone can
+    // leave the eigenvalues, and with them every output, finite
+    const bool in_ok = all_finite(xi, Pi);
     int st = ukf_predict(m, xi, Pi, dt[i], sr[i], cr[i], noise, 0, count, i);
-    if (!all_finite(xi, Pi)) st |= STE_STATUS_NAN;
+    if (!in_ok || !all_finite(xi, Pi)) st |= STE_STATUS_NAN;
     store_vec(x_out, 0, count, i, xi);
     store_mat(P_out, 0, count, i, Pi);
     if (status) status[i] = st;

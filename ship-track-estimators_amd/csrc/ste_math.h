@@ -30,8 +30,11 @@ struct Mats {
 // NumPy floored modulo by 360 (unscented.py:250,257,340,346): npy_divmod takes fmod(a, b) (exact) and, when that is
 // negative, adds b once (one rounding); an exact zero comes out as +0.  Here: q = floor(a/360) estimated with one
 // multiply, r = fma(-q, 360, a) -- the product is exact and the difference is representable, so r IS a - 360 q -- and if
-// the estimate was off by one the remainder is recomputed with the neighbouring q.  The result equals NumPy's bit for
-// bit (for a >= 0 it is the exact remainder; for a < 0 it is the correctly rounded fmod(a, 360) + 360).
+// the estimate was off by one the remainder is recomputed with the neighbouring q.  The one case in which the difference is
+// NOT representable is a in [-2^-45, 0): q = -1 and a + 360 rounds to 360.0, which sends r into the `r >= 360` branch, where
+// the remainder recomputed with q = 0 is a itself, negative.  NumPy returns the rounded sum there (360.0), so that branch
+// does too.  The result equals NumPy's bit for bit (for a >= 0 it is the exact remainder; for a < 0 it is the correctly
+// rounded fmod(a, 360) + 360, which can be 360.0 itself); tests/test_math_probe.py holds it to that.
 __device__ __forceinline__ double floored_mod360(double a) {
     if (__builtin_expect(!(fabs(a) < 1e15), 0)) {  // q * 360 would no longer be exact; also inf / NaN
         double r = fmod(a, 360.0);
@@ -50,6 +53,7 @@ __device__ __forceinline__ double floored_mod360(double a) {
     } else if (r >= 360.0) {
         q += 1.0;
         r = fma(-q, 360.0, a);
+        if (r < 0.0) r = 360.0;  // the first r was a + 360 rounded up to 360.0
     }
     return r;
 }
@@ -72,7 +76,11 @@ __device__ __forceinline__ double rsqrt_fast(double x) {
 // ---------------------------------------------------------------------------------------------------------------
 // Transcendentals.  The device library's sincos/atan2/asin cost 40/34/14-42 fp64-FMA issue slots each (measured on
 // gfx950, one wave per SIMD) and the fan needs 27/9/9 of them per step, so the common cases are inlined here with
-// fdlibm's kernels (same minimax polynomials, < 1 ulp on their intervals) and everything unusual drops to the library.
+// fdlibm's kernels (same minimax polynomials) and everything unusual drops to the library.  Measured against a 50-digit
+// reference on their intervals (tests/test_math_probe.py, profiles/math_probe_errors.md): sin, atan, asin < 1 ulp
+// (0.58, 0.56, 0.54); cos <= 1.5 ulp (1.18 next to pi/4: its head 1 - z/2 is rounded before the polynomial tail is added,
+// where fdlibm's __kernel_cos carries that rounding error along -- two more operations per cosine that nothing downstream,
+// compared at 1e-6, would notice).
 // ---------------------------------------------------------------------------------------------------------------
 
 // sin and cos on |r| <= pi/4 (fdlibm __kernel_sin / __kernel_cos polynomials).
@@ -92,8 +100,12 @@ __device__ __forceinline__ void sincos_kernel(double r, double& s, double& c) {
     c = fma(z * z, pc, fma(-0.5, z, 1.0));
 }
 
-// sincos for |x| < 2^20 by two-constant Cody–Waite reduction with FMA (n*pi/2 is removed exactly in the first FMA,
-// the second restores the bits of pi/2 beyond double precision); larger arguments use the library's Payne–Hanek path.
+// sincos for |x| < 2^20 by three-constant Cody–Waite reduction with FMA (n*pi/2 is removed exactly in the first FMA,
+// the second and third restore the bits of pi/2 beyond double precision); larger arguments use the library's Payne–Hanek
+// path.  Two constants carry pi/2 to ~2^-109: next to a multiple of pi/2 (the double nearest 29 pi/2 lies 6e-19 from it, a
+// heading of 2 610 degrees) the n * 1.5e-33 left over is hundreds to tens of thousands of ulps of the reduced argument
+// (316 at n = 29, 31 000 at n = 204 551); with the third constant the reduced argument is good to an ulp for every n < 2^20.
+// Away from those points the third FMA changes nothing (its term is below 2^-100 of a reduced argument of ordinary size).
 __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
     if (__builtin_expect(!(fabs(x) < 1048576.0), 0)) {
         sincos(x, &s, &c);
@@ -102,6 +114,7 @@ __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
     const double n = rint(x * 0.63661977236758134308);  // 2/pi
     double r = fma(-n, 1.57079632679489655800e+00, x);
     r = fma(-n, 6.12323399573676603587e-17, r);
+    r = fma(-n, -1.49738490485916983405e-33, r);
     double sk, ck;
     sincos_kernel(r, sk, ck);
     const int q = (int)n;
@@ -307,6 +320,8 @@ __device__ __forceinline__ void sincos_fast_n(const double (&x)[N], double (&s)[
     for (int i = 0; i < N; ++i) r[i] = fma(-n[i], 1.57079632679489655800e+00, x[i]);
     STE_UNROLL
     for (int i = 0; i < N; ++i) r[i] = fma(-n[i], 6.12323399573676603587e-17, r[i]);
+    STE_UNROLL
+    for (int i = 0; i < N; ++i) r[i] = fma(-n[i], -1.49738490485916983405e-33, r[i]);
     sincos_kernel_n<N, K>(r, sk, ck, k);
     STE_UNROLL
     for (int i = 0; i < N; ++i) {
@@ -805,8 +820,12 @@ __device__ __forceinline__ void ldl_factor4(const double (&au)[10], Ldl4& f) {
     f.l32 = t32 * f.i2;
     const double d3 = fma(-f.l32, t32, fma(-f.l31, t31, fma(-f.l30, a03, a33)));
     f.i3 = rcp_refined(d3);
-    const double dmin = fmin(fmin(fabs(d0), fabs(d1)), fmin(fabs(d2), fabs(d3)));
-    f.bad = !(dmin > kLdlPivotTol * scale);  // also true for NaN anywhere
+    // fmin (and the fmax of `scale`) drop a NaN operand, so a minimum over all four pivots hid a NaN that entered through an
+    // off-diagonal entry (d0 and d1 stay finite).  Every entry of A reaches the last pivot, so d3 is NaN whenever anything
+    // is, and it is compared on its own: true for a NaN anywhere.
+    const double dmin = fmin(fmin(fabs(d0), fabs(d1)), fabs(d2));
+    const double thr = kLdlPivotTol * scale;
+    f.bad = !(dmin > thr && fabs(d3) > thr);
 }
 // k = (row of D) A^-1, i.e. A k^T = (row of D)^T
 __device__ __forceinline__ void ldl_solve_row4(const Ldl4& f, const double (&d)[4], double (&k)[4]) {
