@@ -513,6 +513,7 @@ class DeviceBatch:
         self._uploaded.record(torch.cuda.current_stream(self.device))
         self._pipeline_done = None
         self._last_use = None  # event after the last forward / backward / run issued outside a pipeline
+        self._reader_done = None  # event an after_smoother hook returned: something (a collective) still reads the outputs
 
     # -- windows of a resident batch ----------------------------------------------------------------------------
     _PER_TRACK_F64 = ("x0", "dt", "sog_rate", "cog_rate", "sog_rate_rts", "cog_rate_rts", "z", "noise_pred",
@@ -547,6 +548,7 @@ class DeviceBatch:
             t = getattr(self, name)
             setattr(w, name, None if t is None else t[..., lo:hi])
         w.status = self.status[lo:hi]
+        # the copied __dict__ leaves the window the parent's _uploaded and a pending _reader_done: its first submit waits for both
         w._pipeline_done = None
         w._last_use = None
         return w
@@ -832,9 +834,130 @@ def forward_schedule(ntiles: Sequence[int], nslices: Sequence[int], nwaves: int,
     return items[:r]
 
 
-# the most recent scheduled forward launch per device, of any pipeline of this process: (its counters, index of its
-# started-waves word, its wave count, the event behind its kernel) -- SmootherPipeline.submit_sequence
-_last_scheduled = {}
+def smoother_tile_order(items: np.ndarray, ntiles: Sequence[int]) -> np.ndarray:
+    """The tile list of a sequence's one-launch smoother (include/ste.h: ``ste_bwd_sched_f64.items``): every (window, tile)
+    of the item table ``items`` (``forward_schedule``) once, in the order the schedule finishes them -- by the last round in
+    which a tile appears, ties in window / tile order (a stable sort).  Returns int32 [sum(ntiles)][2]."""
+    tile0 = np.concatenate(([0], np.cumsum(ntiles)))
+    last = np.full(int(tile0[-1]), -1, dtype=np.int64)
+    live = items[..., 0] >= 0
+    rr = np.broadcast_to(np.arange(items.shape[0])[:, None], items.shape[:2])[live]
+    flat = tile0[items[..., 0][live]] + items[..., 1][live]
+    np.maximum.at(last, flat, rr)
+    idx = np.argsort(last, kind="stable")
+    win = np.searchsorted(tile0, idx, side="right") - 1
+    return np.ascontiguousarray(np.stack([win, idx - tile0[win]], axis=1).astype(np.int32))
+
+
+# What decides between the smoother's two forms (csrc/ste_kernels.hip: kLeanSmootherMaxTracks and the tuning bits that
+# lean_smoother() looks at; include/ste.h: ste_ukf_batch_f64.tuning)
+LEAN_SMOOTHER_MAX_TRACKS = 4096  # up to this many tracks: two kernels (all gains, then a lean recurrence); one kernel above
+TUNING_TWO_KERNEL_SMOOTHER = 0x200  # ... two kernels whatever the batch size
+TUNING_ONE_KERNEL_SMOOTHER = 0x400  # ... one kernel whatever the batch size
+
+
+def _one_kernel_smoother(st) -> bool:
+    """Does the batch struct ``st`` smooth from its work rows in one kernel?  Mirrors ``lean_smoother()`` in
+    csrc/ste_kernels.hip: true where that is false for a batch with work rows and steps."""
+    return bool(st.rts_work and st.Nmax > 0 and not (st.tuning & TUNING_TWO_KERNEL_SMOOTHER)
+                and ((st.tuning & TUNING_ONE_KERNEL_SMOOTHER) or st.B > LEAN_SMOOTHER_MAX_TRACKS))
+
+
+@dataclasses.dataclass(slots=True)
+class _SequencePlan:
+    """Shape and schedule of one ``submit_sequence`` call."""
+
+    step: int  # steps per time slice
+    ntiles: list  # per window: 64-track tiles
+    nslices: list  # per window: time slices
+    nwaves: int  # resident forward waves: one per SIMD the pipeline's forward streams may use
+    key: tuple  # of the item table in SmootherPipeline._schedules
+    items: np.ndarray  # forward_schedule's table
+
+    def table_shape(self):
+        """What the library sizes a forward launch's workspace by (ste_ukf_forward_sched_workspace / _progress_offset)."""
+        return len(self.ntiles), max(self.nslices), sum(self.ntiles), self.items.shape[0], self.nwaves
+
+
+@dataclasses.dataclass(slots=True)
+class _TileSmootherLaunch:
+    """Tables of a sequence's one-launch smoother; they live as long as the forward launch's record."""
+
+    host_ws: object
+    dev_ws: object
+    order: np.ndarray  # smoother_tile_order's list, which the library reads at launch
+
+
+@dataclasses.dataclass(slots=True)
+class _ScheduledLaunch:
+    """Everything one scheduled forward launch reads, kept alive until the pipeline is synchronised, or every gate and
+    smoother that looks at it has finished (the error word is read then)."""
+
+    host_ws: object  # page-locked (or pageable: _sched_pinned) image of the launch's tables
+    dev_ws: object  # the tables on the device, and the per-tile progress counters behind them
+    counters_all: object  # int32: [0 .. n) window_done, [n] error, [n + 1] waves of the launch that have begun
+    counters: object  # its [:n + 1] view
+    structs: object  # ctypes array of the windows' batch structs
+    items: np.ndarray  # the schedule
+    ready: object = None  # event behind the forward kernel
+    events: list = dataclasses.field(default_factory=list)  # the windows' completion events
+    prev_counters: object = None  # counters of the launch before this one while this launch's residency gate reads them
+    smoother: Optional[_TileSmootherLaunch] = None  # set when the smoothers ran as one launch, a wave per tile
+
+    def finished(self) -> bool:
+        return all(ev.query() for ev in [self.ready] + self.events)
+
+    def error_word(self) -> int:
+        """0, or what could not progress: 1 = a forward wave, 2 = a smoother gate (synchronises with the device)."""
+        return int(self.counters[-1].item())
+
+
+@dataclasses.dataclass(slots=True)
+class _LastScheduled:
+    """The most recent scheduled forward launch on a device, of any pipeline of this process: what the next one's
+    residency gate waits for (SmootherPipeline._wait_for_residency)."""
+
+    counters: object  # the launch's counters_all
+    started: int  # index of its started-waves word
+    nwaves: int
+    ready: object  # event behind its kernel
+    owner: int  # id() of its pipeline
+
+
+_last_scheduled = {}  # device index -> _LastScheduled
+
+
+def _forget_scheduled(owner: int):
+    """Drop ``owner``'s launches from ``_last_scheduled`` (its streams are drained and about to go: nothing to wait for)."""
+    for dkey in [k for k, v in _last_scheduled.items() if v.owner == owner]:
+        del _last_scheduled[dkey]
+
+
+class _WorkspacePool:
+    """Host / device table pairs (and counters) of retired scheduled launches, kept for the next ones: an allocation on the
+    launch path -- pinned host memory above all -- is a driver call of unbounded length in the middle of a sequence of
+    launches.  ``take`` allocates on the current stream, so call it with the launch's stream current."""
+
+    def __init__(self, torch, device, min_bytes: int):
+        self.torch, self.device, self.min_bytes = torch, device, int(min_bytes)
+        self.free = []  # (host_ws, dev_ws, counters or None), most recently retired first
+
+    def take(self, nbytes: int, ncounters: int = 0, pinned: bool = True):
+        """(host_ws, dev_ws, counters) of at least ``nbytes`` bytes and ``ncounters`` int32 words (0: no counters, None):
+        the first retired entry that fits, else new ones -- a power of two, so that the next launch fits as well."""
+        for j, (host_ws, dev_ws, counters) in enumerate(self.free):
+            if host_ws.numel() >= nbytes and (not ncounters or counters.numel() >= ncounters):
+                del self.free[j]
+                return host_ws, dev_ws, counters
+        torch = self.torch
+        cap = max(self.min_bytes, 1 << (nbytes - 1).bit_length())
+        host_ws = torch.empty(cap, dtype=torch.uint8, pin_memory=pinned)
+        dev_ws = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        counters = torch.empty(max(64, ncounters), dtype=torch.int32, device=self.device) if ncounters else None
+        return host_ws, dev_ws, counters
+
+    def give(self, entries):
+        self.free = (list(entries) + self.free)[:16]
 
 
 class SmootherPipeline:
@@ -940,10 +1063,10 @@ class SmootherPipeline:
         self._count = 0
         self._batches = []  # weak references to the DeviceBatches that carry one of this pipeline's events
         self._schedules = {}  # item tables of scheduled forward launches, by shape (submit_sequence)
-        self._sched_live = []  # workspaces / counters of scheduled launches not yet synchronised
-        self._sched_free = []  # ... and of retired ones, kept for the next launch: no allocator call on the launch path
+        self._sched_live = []  # _ScheduledLaunch records of the scheduled launches not yet synchronised
+        self._sched_free = _WorkspacePool(torch, self.device, 1 << 20)  # tables and counters of retired launches
         self._sched_pinned = True  # page-locked host workspaces: the table is uploaded by a kernel (False: staged copy; tests)
-        self._sched_free_bwd = []  # the same for the tables of the sequences' smoother launches
+        self._sched_free_bwd = _WorkspacePool(torch, self.device, 1 << 18)  # the same for the sequences' smoother launches
         self._sched_tile_smoothers = True  # one smoother launch per sequence, a wave per tile (False: a launch per window; tests)
         self.buffers_needed = forward_streams + smoother_streams + 1
         # time slices per forward pass (DeviceBatch.forward): the waves of the passes in flight re-balance over the SIMDs at
@@ -1009,8 +1132,7 @@ class SmootherPipeline:
         ``final``: nothing follows this batch, so its smoother gets an unrestricted stream (the whole chip) instead of the
         smoother partition."""
         torch = self.torch
-        if self.closed:
-            raise RuntimeError("SmootherPipeline is closed")
+        self._require_open()
         if (db.noise is not None and self.forward_lanes == 4
                 and not (db.struct.flags & (binding.STE_FLAG_LANES_1 | binding.STE_FLAG_LANES_4))):
             raise ValueError("this pipeline was built with forward_lanes=4 and the batch has per-track noise (Q_tracks / "
@@ -1022,20 +1144,7 @@ class SmootherPipeline:
         bwd_stream = self.bwd_streams[k % len(self.bwd_streams)]
         if final:
             bwd_stream = self._tail_stream
-        done = getattr(db, "_pipeline_done", None)
-        if done is not None:
-            fwd_stream.wait_event(done)  # the previous use of these buffers has drained
-        else:
-            # uploads queued by the constructor: an event it recorded then.  (Not wait_stream(current stream): that
-            # records on the legacy default stream, which drains every blocking stream -- this pipeline's included.)
-            fwd_stream.wait_event(db._uploaded)
-        for name in ("_last_use", "_reader_done"):
-            # kernels issued on this batch outside the pipeline (forward / backward / run on a stream of the caller's), or a
-            # collective started by an earlier after_smoother that may still be reading its outputs
-            e = getattr(db, name, None)
-            if e is not None:
-                fwd_stream.wait_event(e)
-                setattr(db, name, None)
+        self._wait_for_previous_use(db, fwd_stream)
         if timing is not None:
             timing[0].record(fwd_stream)
         # Lane mapping of the forward pass: with several passes sharing the partition a lane per track is the better
@@ -1051,10 +1160,7 @@ class SmootherPipeline:
         ready = timing[1] if timing is not None else torch.cuda.Event()
         ready.record(fwd_stream)
         if not smooth:
-            if getattr(db, "_pipeline_done", None) is None:
-                self._batches.append(weakref.ref(db))
-            db._pipeline_done = ready
-            return ready
+            return self._set_done(db, ready)
         bwd_stream.wait_event(ready)
         if timing is not None:
             timing[2].record(bwd_stream)
@@ -1066,10 +1172,43 @@ class SmootherPipeline:
                 db._reader_done = after_smoother(bwd_stream)
         done = torch.cuda.Event()
         done.record(bwd_stream)
-        if getattr(db, "_pipeline_done", None) is None:
+        return self._set_done(db, done)
+
+    # -- steps that submit and submit_sequence share -----------------------------------------------------------------------
+    def _require_open(self):
+        if self.closed:
+            raise RuntimeError("SmootherPipeline is closed")
+
+    def _wait_for_previous_use(self, db: "DeviceBatch", stream):
+        """``stream`` waits for whatever used ``db``'s buffers last."""
+        if db._pipeline_done is not None:
+            stream.wait_event(db._pipeline_done)  # the previous use of these buffers has drained
+        else:
+            # uploads queued by the constructor: an event it recorded then.  (Not wait_stream(current stream): that
+            # records on the legacy default stream, which drains every blocking stream -- this pipeline's included.)
+            stream.wait_event(db._uploaded)
+        for name in ("_last_use", "_reader_done"):
+            # kernels issued on this batch outside the pipeline (forward / backward / run on a stream of the caller's), or a
+            # collective started by an earlier after_smoother that may still be reading its outputs
+            e = getattr(db, name)
+            if e is not None:
+                stream.wait_event(e)
+                setattr(db, name, None)
+
+    def _set_done(self, db: "DeviceBatch", event):
+        """``event`` marks ``db``'s buffers free again; close() / shrink() find the batch to take the event back."""
+        if db._pipeline_done is None:
             self._batches.append(weakref.ref(db))
-        db._pipeline_done = done
-        return done
+        db._pipeline_done = event
+        return event
+
+    def _drop_batch_events(self):
+        """Take this pipeline's events off the batches that carry one (their streams are about to go)."""
+        for ref in self._batches:
+            db = ref()
+            if db is not None:
+                db._pipeline_done = None
+        self._batches = []
 
     # -- many batches (or windows of a fleet) as ONE scheduled forward launch ---------------------------------------------
     def submit_sequence(self, dbs: Sequence["DeviceBatch"], smooth: bool = True, after_smoother=None, timing=None,
@@ -1092,12 +1231,37 @@ class SmootherPipeline:
         than 4 096 tracks (the one-kernel smoother) and no ``after_smoother``.  Default: when ``final`` and no scheduled launch
         is in flight in front of this one (a job that is one sequence: a fleet, a short run).  Same bits either way.
         Returns the list of the batches' completion events."""
-        torch = self.torch
-        if self.closed:
-            raise RuntimeError("SmootherPipeline is closed")
+        self._require_open()
         dbs = list(dbs)
         if not dbs:
             return []
+        self._validate_sequence(dbs)
+        self._prune_finished()
+        k = self._count
+        self._count += 1
+        fwd_stream = self.fwd_streams[k % len(self.fwd_streams)]
+        for db in dbs:
+            self._wait_for_previous_use(db, fwd_stream)
+        structs = self._window_structs(dbs)
+        plan = self._plan(structs, int(slice_steps) or binding.STE_SLICE_ALIGN, stagger)
+        nbytes = int(self.lib.ste_ukf_forward_sched_workspace(*plan.table_shape()))
+        launch, zeroed = self._take_workspace(nbytes, structs, plan.items, fwd_stream)
+        self._wait_for_residency(launch, fwd_stream, timeout_s)
+        self._launch_scheduled_forward(launch, plan, nbytes, fwd_stream, timeout_s, timing)
+        if tile_smoothers is None:
+            # measured (profiles/r05_scheduled_forward.txt): ONE sequence of 20 batches 14.5-14.7 ms with tile smoothers against
+            # 15.0-15.5 with a smoother per window, a fleet the same either way; sequences that overlap (7 + 13) 15.1-15.3
+            # against 14.5-14.7 -- so: when nothing follows this sequence and none is in flight before it
+            tile_smoothers = self._sched_tile_smoothers and final and launch.prev_counters is None
+        # One smoother launch for the whole sequence -- when every window takes the one-kernel smoother and nothing has to
+        # happen behind individual windows; otherwise a gate and a smoother launch per window.
+        if (smooth and after_smoother is None and tile_smoothers and all(_one_kernel_smoother(st) for st in structs)
+                and len({bool(st.sog_rate_rts or st.cog_rate_rts) for st in structs}) == 1):
+            bwd_stream = self._tail_stream if final else self.bwd_streams[k % len(self.bwd_streams)]
+            return self._launch_tile_smoothers(dbs, launch, plan, zeroed, bwd_stream, timeout_s, timing)
+        return self._launch_window_smoothers(dbs, launch, plan, zeroed, k, final, smooth, after_smoother, timeout_s, timing)
+
+    def _validate_sequence(self, dbs):
         if self.forward_lanes == 4:
             raise ValueError("scheduled forward launches are lane-per-track (this pipeline was built with forward_lanes=4)")
         if any(db.noise is not None for db in dbs):
@@ -1108,84 +1272,90 @@ class SmootherPipeline:
             if key in seen:
                 raise ValueError("submit_sequence: every batch of a sequence needs histories of its own (a buffer set appears twice)")
             seen.add(key)
-        if len(self._sched_live) > 8:
-            # a caller that never synchronises the pipeline: retire the launches that have long finished (their tables and
-            # counters are only kept for the error word, which is looked at now)
-            finished = lambda e: all(ev.query() for ev in e[5] + e[6])  # noqa: E731
-            done_ones = [e for e in self._sched_live if finished(e)]
-            if done_ones:
-                keep = [e for e in self._sched_live if not any(e is d for d in done_ones)]
-                self._sched_live = done_ones
-                try:
-                    self._check_scheduled()
-                finally:
-                    self._sched_live = keep
-        k = self._count
-        self._count += 1
-        fwd_stream = self.fwd_streams[k % len(self.fwd_streams)]
-        for db in dbs:
-            done = getattr(db, "_pipeline_done", None)
-            fwd_stream.wait_event(done if done is not None else db._uploaded)
-            for name in ("_last_use", "_reader_done"):
-                e = getattr(db, name, None)
-                if e is not None:
-                    fwd_stream.wait_event(e)
-                    setattr(db, name, None)
-        n = len(dbs)
-        structs = (binding.SteUkfBatchF64 * n)()
+
+    def _prune_finished(self):
+        """For a caller that never synchronises the pipeline: retire the launches that have long finished (their tables and
+        counters are only kept for the error word, which is looked at now)."""
+        if len(self._sched_live) <= 8:
+            return
+        done_ones = [e for e in self._sched_live if e.finished()]
+        if done_ones:
+            keep = [e for e in self._sched_live if not any(e is d for d in done_ones)]
+            self._sched_live = done_ones
+            try:
+                self._check_scheduled()
+            finally:
+                self._sched_live = keep
+
+    @staticmethod
+    def _window_structs(dbs):
+        """The batch structs of a scheduled launch's windows: copies, lane-per-track, no step range of their own."""
+        structs = (binding.SteUkfBatchF64 * len(dbs))()
         for i, db in enumerate(dbs):
             st = binding.SteUkfBatchF64.from_buffer_copy(db.struct)
             st.flags = (st.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
             st.step_begin = st.step_end = 0
             structs[i] = st
-        step = int(slice_steps) or binding.STE_SLICE_ALIGN
+        return structs
+
+    def _plan(self, structs, step: int, stagger: float) -> _SequencePlan:
+        """Tiles, slices and waves of a sequence, and ``forward_schedule``'s item table for them, cached by shape."""
         ntiles = [-(-int(st.B) // 64) for st in structs]
         nslices = [max(1, -(-int(st.Nmax) // step)) for st in structs]
         nwaves = 4 * (self.forward_cus - self.reserve_cus)  # one per SIMD this pipeline's forward streams may use
-        skey = (tuple(ntiles), tuple(nslices), nwaves, float(stagger))
-        items = self._schedules.get(skey)
+        key = (tuple(ntiles), tuple(nslices), nwaves, float(stagger))
+        items = self._schedules.get(key)
         if items is None:
             items = np.ascontiguousarray(forward_schedule(ntiles, nslices, nwaves, stagger=stagger))
             if len(self._schedules) > 16:
                 self._schedules.clear()
-            self._schedules[skey] = items
-        nbytes = int(self.lib.ste_ukf_forward_sched_workspace(n, max(nslices), sum(ntiles), items.shape[0], nwaves))
-        # workspace and counters come from the launches retired before (synchronize / the pruning above): an allocation here
-        # -- pinned host memory above all -- is a driver call of unbounded length in the middle of a sequence of launches
-        host_ws = dev_ws = counters_all = None
-        for j, (cap, h, d, c) in enumerate(self._sched_free):
-            if cap >= nbytes and c.numel() >= n + 2:
-                host_ws, dev_ws, counters_all = h, d, c
-                del self._sched_free[j]
-                break
+            self._schedules[key] = items
+        return _SequencePlan(step, ntiles, nslices, nwaves, key, items)
+
+    def _tile_order(self, plan: _SequencePlan):
+        """``smoother_tile_order`` of the plan's table, cached beside it."""
+        okey = ("order",) + plan.key
+        order = self._schedules.get(okey)
+        if order is None:
+            order = self._schedules[okey] = smoother_tile_order(plan.items, plan.ntiles)
+        return order
+
+    def _take_workspace(self, nbytes, structs, items, fwd_stream):
+        """Tables and counters for a launch, from the launches retired before (synchronize / _prune_finished), the counters
+        zeroed on the forward stream.  Returns the launch's record and the event behind the zeroing."""
+        torch, n = self.torch, len(structs)
         with torch.cuda.stream(fwd_stream):
-            if host_ws is None:
-                cap = max(1 << 20, 1 << (nbytes - 1).bit_length())
-                host_ws = torch.empty(cap, dtype=torch.uint8, pin_memory=self._sched_pinned)
-                dev_ws = torch.empty(cap, dtype=torch.uint8, device=self.device)
-                counters_all = torch.empty(max(64, n + 2), dtype=torch.int32, device=self.device)
-            counters = counters_all[:n + 1]  # [0 .. n) window_done, [n] error; [n + 1]: waves of the launch that have begun
+            host_ws, dev_ws, counters_all = self._sched_free.take(nbytes, n + 2, pinned=self._sched_pinned)
             counters_all[:n + 2].zero_()
             zeroed = torch.cuda.Event()
             zeroed.record(fwd_stream)
-        # One scheduled launch becomes resident at a time: every wave of a launch may wait for any other, so two launches
-        # dispatched together -- this one while the one before it (of this or another pipeline) is still finding its SIMDs
-        # behind a backlog of smoother waves -- could each hold part of the chip and wait for the rest.  The launch before
-        # this one counts its waves as they begin; a one-wave gate on this launch's stream waits for all of them.
-        dkey = self.device.index or 0
-        prev = _last_scheduled.get(dkey)
-        prev_keep = None
-        if prev is not None and not prev[3].query():
-            prev_keep = prev[0]
-            binding.check(self.lib.ste_stream_wait_counter(prev[0].data_ptr() + 4 * prev[1], prev[2], counters.data_ptr() + 4 * n,
-                                                           float(timeout_s) * 4, C.c_void_p(fwd_stream.cuda_stream)),
-                          "ste_stream_wait_counter")
+        return _ScheduledLaunch(host_ws, dev_ws, counters_all, counters_all[:n + 1], structs, items), zeroed
+
+    def _wait_for_residency(self, launch: _ScheduledLaunch, fwd_stream, timeout_s):
+        """One scheduled launch becomes resident at a time: every wave of a launch may wait for any other, so two launches
+        dispatched together -- this one while the one before it (of this or another pipeline) is still finding its SIMDs
+        behind a backlog of smoother waves -- could each hold part of the chip and wait for the rest.  The launch before
+        this one counts its waves as they begin; a one-wave gate on this launch's stream waits for all of them, and this
+        launch's record keeps the counters that gate reads."""
+        prev = _last_scheduled.get(self.device.index or 0)
+        if prev is None or prev.ready.query():
+            return
+        launch.prev_counters = prev.counters
+        binding.check(self.lib.ste_stream_wait_counter(prev.counters.data_ptr() + 4 * prev.started, prev.nwaves,
+                                                       launch.counters.data_ptr() + 4 * len(launch.structs),
+                                                       float(timeout_s) * 4, C.c_void_p(fwd_stream.cuda_stream)),
+                      "ste_stream_wait_counter")
+
+    def _launch_scheduled_forward(self, launch: _ScheduledLaunch, plan: _SequencePlan, nbytes, fwd_stream, timeout_s, timing):
+        """The forward launch itself; records it as live and as the device's last scheduled launch."""
+        torch, n, items = self.torch, len(launch.structs), plan.items
+        counters = launch.counters.data_ptr()
         sc = binding.SteFwdSchedF64()
-        sc.nwindows, sc.windows, sc.slice_steps = n, C.addressof(structs), step
-        sc.nwaves, sc.nrounds, sc.items = nwaves, int(items.shape[0]), items.ctypes.data
-        sc.host_ws, sc.dev_ws, sc.ws_bytes = host_ws.data_ptr(), dev_ws.data_ptr(), nbytes
-        sc.window_done, sc.error, sc.timeout_s = counters.data_ptr(), counters.data_ptr() + 4 * n, float(timeout_s)
-        sc.started = counters_all.data_ptr() + 4 * (n + 1)
+        sc.nwindows, sc.windows, sc.slice_steps = n, C.addressof(launch.structs), plan.step
+        sc.nwaves, sc.nrounds, sc.items = plan.nwaves, int(items.shape[0]), items.ctypes.data
+        sc.host_ws, sc.dev_ws, sc.ws_bytes = launch.host_ws.data_ptr(), launch.dev_ws.data_ptr(), nbytes
+        sc.window_done, sc.error, sc.timeout_s = counters, counters + 4 * n, float(timeout_s)
+        sc.started = launch.counters_all.data_ptr() + 4 * (n + 1)
         if timing is not None:
             timing["forward"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             timing["smoothers"] = []
@@ -1194,88 +1364,57 @@ class SmootherPipeline:
                       "ste_ukf_forward_sched_f64")
         if timing is not None:
             timing["forward"][1].record(fwd_stream)
-        ready = torch.cuda.Event()
-        ready.record(fwd_stream)
-        # the launch's tables and counters stay alive until the pipeline is synchronised, or every gate and smoother that
-        # looks at them has finished (their error word is read then)
-        events = []
-        self._sched_live.append((host_ws, dev_ws, counters, structs, items, [ready], events, counters_all, prev_keep))
-        _last_scheduled[dkey] = (counters_all, n + 1, nwaves, ready, id(self))
-        # One smoother launch for the whole sequence, a wave per tile that waits for ITS tile's forward pass (include/ste.h:
-        # ste_urtss_backward_sched_f64) -- when every window takes the one-kernel smoother and nothing has to happen behind
-        # individual windows; otherwise a gate and a smoother launch per window (below).
-        lean = 4096  # launch_backward's bound (csrc/ste_kernels.hip: kLeanSmootherMaxTracks)
-        if tile_smoothers is None:
-            # measured (profiles/r05_scheduled_forward.txt): ONE sequence of 20 batches 14.5-14.7 ms with tile smoothers against
-            # 15.0-15.5 with a smoother per window, a fleet the same either way; sequences that overlap (7 + 13) 15.1-15.3
-            # against 14.5-14.7 -- so: when nothing follows this sequence and none is in flight before it
-            tile_smoothers = self._sched_tile_smoothers and final and prev_keep is None
-        merged = (smooth and after_smoother is None and tile_smoothers and len({bool(st.sog_rate_rts or st.cog_rate_rts) for st in structs}) == 1
-                  and all(st.rts_work and not (st.tuning & 0x200) and ((st.tuning & 0x400) or st.B > lean) and st.Nmax > 0 for st in structs))
-        if merged:
-            okey = ("order",) + skey
-            order = self._schedules.get(okey)
-            if order is None:
-                # tiles in the order the schedule finishes them: last round in which (window, tile) appears
-                tile0 = np.concatenate(([0], np.cumsum(ntiles)))
-                last = np.full(int(tile0[-1]), -1, dtype=np.int64)
-                live = items[..., 0] >= 0
-                rr = np.broadcast_to(np.arange(items.shape[0])[:, None], items.shape[:2])[live]
-                flat = tile0[items[..., 0][live]] + items[..., 1][live]
-                np.maximum.at(last, flat, rr)
-                idx = np.argsort(last, kind="stable")
-                win = np.searchsorted(tile0, idx, side="right") - 1
-                order = np.ascontiguousarray(np.stack([win, idx - tile0[win]], axis=1).astype(np.int32))
-                self._schedules[okey] = order
-            bwd_stream = self._tail_stream if final else self.bwd_streams[k % len(self.bwd_streams)]
-            bwd_stream.wait_event(zeroed)
-            # behind the forward launch's residency: a waiting smoother wave must not sit where a forward wave still has to go
-            binding.check(self.lib.ste_stream_wait_counter(counters_all.data_ptr() + 4 * (n + 1), nwaves, counters.data_ptr() + 4 * n,
-                                                           float(timeout_s) * 4, C.c_void_p(bwd_stream.cuda_stream)),
-                          "ste_stream_wait_counter")
-            sbytes = int(self.lib.ste_urtss_backward_sched_workspace(n, int(order.shape[0])))
-            s_host = s_dev = None
-            for j, (cap, h, d) in enumerate(self._sched_free_bwd):
-                if cap >= sbytes:
-                    s_host, s_dev = h, d
-                    del self._sched_free_bwd[j]
-                    break
-            if s_host is None:
-                cap = max(1 << 18, 1 << (sbytes - 1).bit_length())
-                with torch.cuda.stream(bwd_stream):
-                    s_host = torch.empty(cap, dtype=torch.uint8, pin_memory=self._sched_pinned)
-                    s_dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
-            bs = binding.SteBwdSchedF64()
-            bs.nwindows, bs.windows, bs.slice_steps = n, C.addressof(structs), step
-            bs.nitems, bs.items = int(order.shape[0]), order.ctypes.data
-            bs.host_ws, bs.dev_ws, bs.ws_bytes = s_host.data_ptr(), s_dev.data_ptr(), sbytes
-            bs.progress = dev_ws.data_ptr() + int(self.lib.ste_ukf_forward_sched_progress_offset(n, max(nslices), sum(ntiles), items.shape[0], nwaves))
-            bs.error, bs.timeout_s = counters.data_ptr() + 4 * n, float(timeout_s) * 4
-            if timing is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                timing["smoothers"].append(ev)
-                timing["tile_smoothers"] = True
-                ev[0].record(bwd_stream)
-            binding.check(self.lib.ste_urtss_backward_sched_f64(C.byref(bs), C.c_void_p(bwd_stream.cuda_stream)),
-                          "ste_urtss_backward_sched_f64")
-            if timing is not None:
-                ev[1].record(bwd_stream)
-            done = torch.cuda.Event()
-            done.record(bwd_stream)
-            self._sched_live[-1] = self._sched_live[-1] + ((s_host, s_dev, order),)
-            for db in dbs:
-                if getattr(db, "_pipeline_done", None) is None:
-                    self._batches.append(weakref.ref(db))
-                db._pipeline_done = done
-                events.append(done)
-            return events
+        launch.ready = torch.cuda.Event()
+        launch.ready.record(fwd_stream)
+        self._sched_live.append(launch)
+        _last_scheduled[self.device.index or 0] = _LastScheduled(launch.counters_all, n + 1, plan.nwaves, launch.ready, id(self))
+
+    def _launch_tile_smoothers(self, dbs, launch: _ScheduledLaunch, plan: _SequencePlan, zeroed, bwd_stream, timeout_s, timing):
+        """The smoothers of the whole sequence as ONE launch on ``bwd_stream``, a wave per tile that waits for ITS tile's
+        forward pass (include/ste.h: ste_urtss_backward_sched_f64).  Returns the windows' completion events."""
+        torch, n = self.torch, len(dbs)
+        order = self._tile_order(plan)
+        error = launch.counters.data_ptr() + 4 * n
+        bwd_stream.wait_event(zeroed)
+        # behind the forward launch's residency: a waiting smoother wave must not sit where a forward wave still has to go
+        binding.check(self.lib.ste_stream_wait_counter(launch.counters_all.data_ptr() + 4 * (n + 1), plan.nwaves, error,
+                                                       float(timeout_s) * 4, C.c_void_p(bwd_stream.cuda_stream)),
+                      "ste_stream_wait_counter")
+        sbytes = int(self.lib.ste_urtss_backward_sched_workspace(n, int(order.shape[0])))
+        with torch.cuda.stream(bwd_stream):
+            s_host, s_dev, _ = self._sched_free_bwd.take(sbytes, pinned=self._sched_pinned)
+        bs = binding.SteBwdSchedF64()
+        bs.nwindows, bs.windows, bs.slice_steps = n, C.addressof(launch.structs), plan.step
+        bs.nitems, bs.items = int(order.shape[0]), order.ctypes.data
+        bs.host_ws, bs.dev_ws, bs.ws_bytes = s_host.data_ptr(), s_dev.data_ptr(), sbytes
+        bs.progress = launch.dev_ws.data_ptr() + int(self.lib.ste_ukf_forward_sched_progress_offset(*plan.table_shape()))
+        bs.error, bs.timeout_s = error, float(timeout_s) * 4
+        if timing is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            timing["smoothers"].append(ev)
+            timing["tile_smoothers"] = True
+            ev[0].record(bwd_stream)
+        binding.check(self.lib.ste_urtss_backward_sched_f64(C.byref(bs), C.c_void_p(bwd_stream.cuda_stream)),
+                      "ste_urtss_backward_sched_f64")
+        if timing is not None:
+            ev[1].record(bwd_stream)
+        done = torch.cuda.Event()
+        done.record(bwd_stream)
+        launch.smoother = _TileSmootherLaunch(s_host, s_dev, order)
+        for db in dbs:
+            launch.events.append(self._set_done(db, done))
+        return launch.events
+
+    def _launch_window_smoothers(self, dbs, launch: _ScheduledLaunch, plan: _SequencePlan, zeroed, k, final, smooth,
+                                 after_smoother, timeout_s, timing):
+        """A one-wave gate and a smoother launch per window, round-robin over the smoother streams (``smooth=False``: none, a
+        window is done when the forward launch is).  Returns the windows' completion events."""
+        torch, n = self.torch, len(dbs)
+        counters = launch.counters.data_ptr()
         waited = set()
         for i, db in enumerate(dbs):
-            if getattr(db, "_pipeline_done", None) is None:
-                self._batches.append(weakref.ref(db))
             if not smooth:
-                db._pipeline_done = ready
-                events.append(ready)
+                launch.events.append(self._set_done(db, launch.ready))
                 continue
             bwd_stream = self.bwd_streams[(k + i) % len(self.bwd_streams)]
             if final and i == n - 1:
@@ -1283,7 +1422,7 @@ class SmootherPipeline:
             if id(bwd_stream) not in waited:  # the counters were zeroed on the forward stream: no gate may read them earlier
                 bwd_stream.wait_event(zeroed)
                 waited.add(id(bwd_stream))
-            binding.check(self.lib.ste_stream_wait_counter(counters.data_ptr() + 4 * i, ntiles[i], counters.data_ptr() + 4 * n,
+            binding.check(self.lib.ste_stream_wait_counter(counters + 4 * i, plan.ntiles[i], counters + 4 * n,
                                                            float(timeout_s) * 4, C.c_void_p(bwd_stream.cuda_stream)),
                           "ste_stream_wait_counter")
             timed = timing is not None and i % int(timing.get("every", 4)) == 0
@@ -1299,16 +1438,16 @@ class SmootherPipeline:
                     db._reader_done = after_smoother(i, bwd_stream)
             done = torch.cuda.Event()
             done.record(bwd_stream)
-            db._pipeline_done = done
-            events.append(done)
-        return events
+            launch.events.append(self._set_done(db, done))
+        return launch.events
 
     def _check_scheduled(self):
-        """After a synchronisation: the error words of the scheduled launches issued since the last one."""
+        """After a synchronisation: the error words of the scheduled launches issued since the last one; their tables and
+        counters go back to the pools."""
         live, self._sched_live = self._sched_live, []
-        bad = [int(e[2][-1].item()) for e in live]
-        self._sched_free = ([(e[0].numel(), e[0], e[1], e[7]) for e in live] + self._sched_free)[:16]
-        self._sched_free_bwd = ([(e[9][0].numel(), e[9][0], e[9][1]) for e in live if len(e) > 9] + self._sched_free_bwd)[:16]
+        bad = [e.error_word() for e in live]
+        self._sched_free.give((e.host_ws, e.dev_ws, e.counters_all) for e in live)
+        self._sched_free_bwd.give((e.smoother.host_ws, e.smoother.dev_ws, None) for e in live if e.smoother is not None)
         if any(bad):
             raise binding.SteError("a scheduled forward launch could not progress (error word %s: 1 = a forward wave, 2 = a smoother "
                                    "gate waited longer than its bound); results of that sequence are incomplete" % bad)
@@ -1329,13 +1468,8 @@ class SmootherPipeline:
         if forward_streams < 1 or smoother_streams < 1:
             raise ValueError("forward_streams and smoother_streams must be >= 1")
         self.synchronize()
-        for ref in self._batches:  # (events recorded on streams that are about to go)
-            db = ref()
-            if db is not None and getattr(db, "_pipeline_done", None) is not None:
-                db._pipeline_done = None
-        self._batches = []
-        for dkey in [k for k, v in _last_scheduled.items() if v[4] == id(self)]:
-            del _last_scheduled[dkey]
+        self._drop_batch_events()
+        _forget_scheduled(id(self))
         drop = self.fwd_streams[forward_streams:] + self.bwd_streams[smoother_streams:]
         self.fwd_streams, self.bwd_streams = self.fwd_streams[:forward_streams], self.bwd_streams[:smoother_streams]
         gone = {int(st.cuda_stream) for st in drop}
@@ -1360,16 +1494,10 @@ class SmootherPipeline:
                 self.synchronize()
         finally:
             # the events recorded on these streams and the ExternalStream wrappers go first, then the streams themselves
-            for ref in self._batches:
-                db = ref()
-                if db is not None and getattr(db, "_pipeline_done", None) is not None:
-                    db._pipeline_done = None
-            self._batches = []
+            self._drop_batch_events()
             self._sched_live = []
-            self._sched_free = []
-            self._sched_free_bwd = []
-            for dkey in [k for k, v in _last_scheduled.items() if v[4] == id(self)]:  # (drained above: nothing to wait for)
-                del _last_scheduled[dkey]
+            self._sched_free.free, self._sched_free_bwd.free = [], []
+            _forget_scheduled(id(self))
             self.fwd_streams, self.bwd_streams, self._tail_stream = [], [], None
             raw, self._raw = self._raw, []
             for h in raw:
@@ -1755,15 +1883,20 @@ def run_fleet(fleet, chunk: int = FLEET_CHUNK, device="cuda:0", smooth: bool = T
                 attr, width = DeviceBatch._OUT[name]
                 host[name] = torch.empty((B, hb.Nmax + 1, width), dtype=torch.float64, pin_memory=True)
         keep = []
+
+        def collect(win, lo, hi, done):
+            """A submitted window: its histories come down behind ``done``; it stays alive until the pipeline has drained."""
+            if stream_down:
+                down.wait_event(done)
+                with torch.cuda.stream(down):
+                    keep.append(win._download_into(outputs, host, lo, hi))
+            keep.append(win)
+
         if scheduled and resident and len(wins) > 1:
             ws = [db.window(lo, hi) for lo, hi in wins]
             dones = pipe.submit_sequence(ws, smooth=smooth)
             for (lo, hi), win, done in zip(wins, ws, dones):
-                if stream_down:
-                    down.wait_event(done)
-                    with torch.cuda.stream(down):
-                        keep.append(win._download_into(outputs, host, lo, hi))
-                keep.append(win)
+                collect(win, lo, hi, done)
             wins_left = []
         else:
             wins_left = wins
@@ -1771,12 +1904,7 @@ def run_fleet(fleet, chunk: int = FLEET_CHUNK, device="cuda:0", smooth: bool = T
             win = db.window(lo, hi) if len(wins) > 1 else db
             if not resident:
                 win._uploaded = db.upload_tracks(lo, hi, up)
-            done = pipe.submit(win, final=(i == len(wins) - 1), smooth=smooth)
-            if stream_down:
-                down.wait_event(done)
-                with torch.cuda.stream(down):
-                    keep.append(win._download_into(outputs, host, lo, hi))
-            keep.append(win)
+            collect(win, lo, hi, pipe.submit(win, final=(i == len(wins) - 1), smooth=smooth))
         pipe.synchronize()
         if down is not None:
             down.synchronize()

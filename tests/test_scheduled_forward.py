@@ -59,6 +59,40 @@ def test_forward_schedule_with_staggered_deadlines_is_still_complete():
     assert len(set(done.tolist())) > 6  # the windows finish spread out, not in generations
 
 
+def _rolled(ntiles, nslices, nwaves):
+    """A table whose rounds are rotated, every round by another amount (the hand-over test's): tiles change waves, rounds stay."""
+    items = batch.forward_schedule(ntiles, nslices, nwaves).copy()
+    for r in range(items.shape[0]):
+        items[r] = np.roll(items[r], 131 * (r + 1), axis=0)
+    return items
+
+
+_ORDER_3_1_7 = [[0, 0], [0, 1], [0, 2], [2, 0], [2, 1], [2, 2], [2, 3], [2, 4], [2, 5], [2, 6], [1, 0]]
+
+
+@pytest.mark.parametrize("ntiles,nslices,nwaves,table,expected", [
+    ([3, 1, 7], [2, 9, 1], 4, batch.forward_schedule, _ORDER_3_1_7), ([2, 2], [2, 2], 4, batch.forward_schedule, None),
+    ([1], [1], 1024, batch.forward_schedule, None), ([94] * 3, [5] * 3, 1024, _rolled, None),
+    ([157] * 20, [8] * 20, 1024, batch.forward_schedule, None)])
+def test_smoother_tile_order_lists_every_tile_once_in_finishing_order(ntiles, nslices, nwaves, table, expected):
+    """``batch.smoother_tile_order``: the tiles of a schedule sorted by the last round in which they appear, stably.  The
+    literal is what ``submit_sequence`` computed inline before the function existed."""
+    items = table(ntiles, nslices, nwaves)
+    order = batch.smoother_tile_order(items, ntiles)
+    assert order.dtype == np.int32 and order.flags.c_contiguous and order.shape == (sum(ntiles), 2)
+    assert sorted(map(tuple, order.tolist())) == [(w, t) for w, n in enumerate(ntiles) for t in range(n)]  # each pair once
+    last = {}
+    for r in range(items.shape[0]):
+        for w, t in items[r][items[r][:, 0] >= 0].tolist():
+            last[(w, t)] = r
+    tile0 = np.concatenate(([0], np.cumsum(ntiles)))
+    keys = [(last[(w, t)], int(tile0[w]) + t) for w, t in order.tolist()]  # (last round, flat tile index)
+    assert all(a[0] <= b[0] for a, b in zip(keys, keys[1:]))  # the last round never decreases
+    assert all(a[1] < b[1] for a, b in zip(keys, keys[1:]) if a[0] == b[0])  # ties: ascending flat tile order (stable sort)
+    if expected is not None:
+        assert np.array_equal(order, np.array(expected, dtype=np.int32))
+
+
 def _minimal_windows(n, B=128, Nmax=128, keep=None):
     arr = (binding.SteUkfBatchF64 * n)()
     m = np.eye(4)
@@ -220,22 +254,22 @@ def test_sequence_of_batches_is_the_per_batch_launches_bit_for_bit():
         with pytest.raises(ValueError, match="histories of its own"):
             pipe.submit_sequence([seqs[0], seqs[0]])
         # workspaces of retired launches are kept and reused: the launches above were never more than two at a time
-        assert 1 <= len(pipe._sched_free) <= 2 and not pipe._sched_live
-        kept = {h.data_ptr() for _cap, h, _d, _c in pipe._sched_free}
+        assert 1 <= len(pipe._sched_free.free) <= 2 and not pipe._sched_live
+        kept = {host_ws.data_ptr() for host_ws, _dev_ws, _counters in pipe._sched_free.free}
         for d in seqs:
             _clear(d)
         pipe.submit_sequence(seqs)
-        assert pipe._sched_live[-1][0].data_ptr() in kept
+        assert pipe._sched_live[-1].host_ws.data_ptr() in kept
         pipe.synchronize()
         for r, d in zip(refs, seqs):
             assert _same(r, d)
         # a pageable host workspace (what a caller of the C ABI without page-locked memory hands over) takes the staged copy
         # instead of the upload kernel: same table, same bits
-        pipe._sched_free, pipe._sched_pinned = [], False
+        pipe._sched_free.free, pipe._sched_pinned = [], False
         for d in seqs:
             _clear(d)
         pipe.submit_sequence(seqs)
-        assert not pipe._sched_live[-1][0].is_pinned()
+        assert not pipe._sched_live[-1].host_ws.is_pinned()
         pipe.synchronize()
         for r, d in zip(refs, seqs):
             assert _same(r, d)
@@ -309,7 +343,7 @@ def test_slices_that_change_waves_every_round_hand_over_bit_for_bit():
             # batches of 6 000 tracks, nothing in flight: the smoothers are ONE launch, a wave per tile waiting for its own
             # tile's last slice (every other repetition: a gate and a smoother launch per batch) -- same bits
             pipe.submit_sequence(seqs, tile_smoothers=None if rep % 2 == 0 else False)
-            assert (len(pipe._sched_live[-1]) > 9) == (rep % 2 == 0)
+            assert (pipe._sched_live[-1].smoother is not None) == (rep % 2 == 0)
             pipe.synchronize()
             for d in seqs:
                 assert _same(ref, d), rep
@@ -344,11 +378,11 @@ def test_scheduled_launches_of_two_pipelines_become_resident_one_at_a_time():
             pb.submit_sequence(seqs[1])
             # the second launch holds the first one's counters -- its gate reads them -- unless the first had already finished
             # when the second was submitted (a host that was held up for milliseconds between the two calls)
-            assert pb._sched_live[-1][8] is first[7] or first[5][0].query()
+            assert pb._sched_live[-1].prev_counters is first.counters_all or first.ready.query()
             pb.submit_sequence(seqs[1][:3] + seqs[0][:0], smooth=False)  # (and a third behind the second, same pipeline)
             pa.synchronize()
             pb.synchronize()
-            assert int(first[7][len(seqs[0]) + 1].item()) == nwaves  # every wave of the launch counted itself in
+            assert int(first.counters_all[len(seqs[0]) + 1].item()) == nwaves  # every wave of the launch counted itself in
             for r, group in zip(refs, seqs):
                 for d in group:
                     assert _same(r, d), rep
@@ -386,7 +420,7 @@ def test_pipeline_shrinks_to_the_streams_scheduled_launches_need():
         for d in seqs:
             _clear(d)
         pipe.submit_sequence(seqs)
-        assert len(pipe._sched_live[-1]) > 9  # one smoother launch, a wave per tile
+        assert pipe._sched_live[-1].smoother is not None  # one smoother launch, a wave per tile
         pipe.synchronize()
         assert all(_same(ref, d) for d in seqs)
         with pytest.raises(ValueError):
