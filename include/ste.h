@@ -46,7 +46,8 @@ extern "C" {
 #define STE_VERSION 340 /* 0.3.4: posterior covariance on the GP path (ste_gp_predict_cov_f64).  Unnumbered addition:
                            the innovation log-likelihood of the forward pass (ste_ukf_loglik_f64,
                            ste_ukf_forward_loglik_f64).  Unnumbered addition: the posterior of the time derivative on the
-                           GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).
+                           GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).  Unnumbered addition: posterior tracks
+                           sampled from the smoother (ste_urtss_sample_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -279,6 +280,49 @@ int ste_ukf_forward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f6
 int ste_urtss_backward_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream);
 /* both, back to back on one stream */
 int ste_ukf_urtss_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, void* stream);
+
+/*
+ * Posterior TRACKS from the unscented smoother (an unnumbered addition, like ste_ukf_noise_f64).  sm_mean / sm_cov are the
+ * marginals of every row; what carries a track's uncertainty into something downstream (distance sailed, the time of a
+ * crossing) are whole tracks drawn from the joint posterior, in which neighbouring rows are tied together by the smoother
+ * gains.  Backward simulation with the smoother's own per-step quantities (unscented.py:297-349; m_k, P_k the filtered row k,
+ * x_b, P_b -- about the filtered mean, as there -- and K = D pinv(P_b) of step k), for a track of ns steps:
+ *      row ns:  x_ns = m_ns + T_ns xi_ns,                                        T_ns = symsqrt(P_ns)
+ *      row k :  y = x_{k+1} - x_b,  y[3] wrapped to [-180, 180);   x_k = (m_k + K y) + T_k xi_k,   T_k = symsqrt(P_k - K P_b K^T)
+ *      x_k[3] = x_k[3] mod 360 (floored), row ns included
+ * xi are the caller's standard normal draws; symsqrt is the symmetric square root of the sigma fan (eigenvalues below zero
+ * clamped), which exists where the conditional covariance is only semi-definite (a Q with zero directions).  With xi = 0
+ * the samples are sm_mean, bit for bit; the ensemble covariance of the samples is sm_cov (the recursion
+ * Cov(x_k) = T_k T_k + K Cov(x_{k+1}) K^T is the smoother's own).
+ *   - Precondition: a completed forward pass of this batch WITH rts_work.  The smoother may or may not have run, in either of
+ *     its forms; samples are the same bits whichever state the work rows are in.  The calls only read the batch: rts_work, the
+ *     histories and b->status are not written.
+ *   - prepare turns the work rows into coefficients (K 16 | x_b 4 | T packed 10 per row) in `coef`; draw runs the recurrence from
+ *     them and may be repeated with fresh draws; ste_urtss_sample_f64 is both.  nz: the per-track Q the forward pass ran with
+ *     (NULL, or nz->Q NULL: the shared b->Q); nz->R and nz->flags are not read.
+ *   - Ordering: the calls read rts_work.  A two-kernel smoother (ste_urtss_backward_f64 on a small batch) REWRITES the work rows
+ *     into gains; when it runs on another stream the caller orders prepare before or after it, never beside it.
+ *   - Windows: track_stride works like for every other per-track array -- samples and coef have rows of track_stride tracks
+ *     and the pointers name the window's first track; status is [B] and points at the window's first entry.
+ *   - Rows past nsteps[t] of samples (and of coef) are left as they were.
+ *   - Refused with STE_EINVAL and a message before any launch: b, sm, sm->samples or sm->coef NULL; nsamples < 1 (or > 65535);
+ *     flags != 0; rts_work, fwd_mean or fwd_cov NULL; step_begin / step_end naming a slice; and whatever
+ *     ste_urtss_backward_f64 refuses (sm_mean / sm_cov NULL among it).  STE_FLAG_LANES_1 / _4 are ignored.
+ */
+typedef struct ste_ukf_sample_f64 {
+    int32_t nsamples;  /* S >= 1 */
+    uint32_t flags;    /* must be 0 */
+    double* samples;   /* DEVICE [S][Nmax+1][4][track_stride]; in: N(0, 1) draws, out: sampled states */
+    double* coef;      /* DEVICE workspace [Nmax+1][30][track_stride]: written by prepare, read by draw */
+    int32_t* status;   /* DEVICE [B] out or NULL: overwritten by prepare with STE_STATUS_NAN (a non-finite coefficient),
+                          STE_STATUS_CLAMPED (a negative eigenvalue of a conditional covariance was clamped), STE_STATUS_NOCONV */
+} ste_ukf_sample_f64;  /* 32 bytes */
+
+int ste_urtss_sample_prepare_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64* sm, void* stream);
+/* the recurrence only, from a prepared coef; repeatable with fresh draws */
+int ste_urtss_sample_draw_f64(const ste_ukf_batch_f64* b, const ste_ukf_sample_f64* sm, void* stream);
+/* both, back to back on one stream */
+int ste_urtss_sample_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64* sm, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

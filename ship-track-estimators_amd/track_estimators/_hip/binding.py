@@ -103,6 +103,21 @@ class SteUkfNoiseF64(C.Structure):
     ]
 
 
+class SteUkfSampleF64(C.Structure):
+    """Mirror of ``struct ste_ukf_sample_f64`` (include/ste.h): posterior tracks sampled from the smoother."""
+
+    _fields_ = [
+        ("nsamples", C.c_int32),
+        ("flags", C.c_uint32),
+        ("samples", _dp),
+        ("coef", _dp),
+        ("status", _dp),
+    ]
+
+
+STE_SAMPLE_COEF_ROWS = 30  # doubles per (row, track) of ste_ukf_sample_f64.coef
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -205,6 +220,11 @@ SYMBOLS = {
                                             C.c_void_p]),
     "ste_urtss_backward_noise_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.c_void_p]),
     "ste_ukf_urtss_noise_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.c_void_p]),
+    "ste_urtss_sample_prepare_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteUkfSampleF64),
+                                               C.c_void_p]),
+    "ste_urtss_sample_draw_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfSampleF64), C.c_void_p]),
+    "ste_urtss_sample_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteUkfSampleF64),
+                                       C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

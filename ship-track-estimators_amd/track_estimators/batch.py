@@ -695,6 +695,70 @@ class DeviceBatch:
                                  status=self.status.cpu().numpy(),
                                  nis=None if nis_t is None else nis_t[:, col:col + B].T.cpu().numpy())
 
+    # -- posterior tracks ----------------------------------------------------------------------------------------
+    def _sample_struct(self, samples, nsamples: int):
+        """The ``ste_ukf_sample_f64`` of this batch (or window) for ``samples`` [S][N+1][4][ld], with a coefficient workspace
+        and a status array of its own; returns (struct, status tensor, tensors to keep alive)."""
+        torch = self.torch
+        N, ld = int(self.struct.Nmax), int(self.struct.track_stride or self.struct.B)
+        coef = torch.empty((N + 1, binding.STE_SAMPLE_COEF_ROWS, ld), dtype=torch.float64, device=self.device)
+        status = torch.zeros((self.ntracks,), dtype=torch.int32, device=self.device)
+        sm = binding.SteUkfSampleF64(int(nsamples), 0, samples.data_ptr() + 8 * self.lo, coef.data_ptr() + 8 * self.lo,
+                                     status.data_ptr())
+        return sm, status, (samples, coef)
+
+    def sample_smoothed(self, nsamples: int, seed: int = 0, draws=None, stream=None):
+        """``nsamples`` tracks drawn from the joint smoothing posterior (include/ste.h: ste_urtss_sample_f64), as a device
+        tensor (S, Nmax+1, 4, B); rows past ``nsteps[b]`` hold whatever they held (the draws).  Needs a completed
+        ``forward()`` of this batch; ``backward()`` may or may not have run.  ``draws``: a float64 device tensor of that
+        shape with standard normal draws, consumed in place (it comes back holding the samples); None = ``torch.randn``
+        from a ``torch.Generator`` on the batch's device seeded with ``seed``.  A window of a resident batch
+        (``window(lo, hi)``) samples its own tracks, B = hi - lo; given columns [lo, hi) of the draws of a whole-batch call
+        it returns the same bits as that call.  The sampler's status (STE_STATUS_* per track) is left in
+        ``self.sample_status`` (a device tensor)."""
+        torch = self.torch
+        if self.rts_work is None:
+            raise ValueError("sample_smoothed() draws tracks from the work rows the forward pass leaves for the smoother "
+                             "(rts_work), and this batch has none: it was built with fuse_gains=False, histories=False or "
+                             "alloc_smoothed=False")
+        S, N, B = int(nsamples), int(self.struct.Nmax), self.ntracks
+        if S < 1:
+            raise ValueError(f"nsamples must be >= 1, got {nsamples!r}")
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        with torch.cuda.stream(st):
+            if draws is None:
+                gen = torch.Generator(device=self.device)
+                gen.manual_seed(int(seed))
+                out = torch.randn((S, N + 1, 4, B), generator=gen, dtype=torch.float64, device=self.device)
+            else:
+                if tuple(draws.shape) != (S, N + 1, 4, B) or draws.dtype != torch.float64 or draws.device != self.device:
+                    raise ValueError(f"draws must be a float64 tensor of shape {(S, N + 1, 4, B)} on {self.device}")
+                out = draws
+            if ld == B and self.lo == 0 and out.is_contiguous():
+                full, view = out, out
+            else:  # a window: rows of the fleet's width, this window's columns filled with its draws
+                full = torch.empty((S, N + 1, 4, ld), dtype=torch.float64, device=self.device)
+                view = full[..., self.lo:self.lo + B]
+                view.copy_(out)
+            sm, status, keep = self._sample_struct(full, S)
+            noise = None if self.noise is None else C.byref(self.noise)
+            binding.check(self.lib.ste_urtss_sample_f64(C.byref(self.struct), noise, C.byref(sm), self._stream(st)),
+                          "ste_urtss_sample_f64")
+            if view is not out:
+                out.copy_(view)
+            for ten in keep:
+                ten.record_stream(st)
+            self.sample_status = status
+            self._mark_use(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -1677,6 +1741,24 @@ def _run_batch(hb, device, smooth, fuse_gains, outputs, sm_pos):
     nsteps = hb.nsteps.copy()
     out["status"], out["nsteps"] = (status, nsteps) if inv is None else (status[inv], nsteps[inv])
     return out, db
+
+
+def sample_tracks(hb_or_db, nsamples: int, seed: int = 0, device="cuda:0"):
+    """``nsamples`` posterior tracks per track of a batch, drawn from the joint smoothing posterior on the device
+    (``DeviceBatch.sample_smoothed``).  Given a ``HostBatch`` it uploads it and runs the forward pass first; given a
+    ``DeviceBatch`` (or a window of one) it samples from the forward pass that batch holds.  Returns
+    ``(samples, status)``: samples (S, B, Nmax+1, 4) as NumPy, track-major like ``download`` and in the batch's slot
+    order (``hb.order`` maps slots to the caller's tracks), rows past ``nsteps[b]`` are padding; status (B,) int32, the
+    sampler's own STE_STATUS_* bits per track."""
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.forward()
+    t = db.sample_smoothed(nsamples, seed=seed)
+    dev_t = t.permute(0, 3, 1, 2).contiguous()
+    status = db.sample_status.cpu().numpy()
+    return dev_t.cpu().numpy(), status
 
 
 @dataclasses.dataclass

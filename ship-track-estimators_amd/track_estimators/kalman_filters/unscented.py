@@ -211,6 +211,7 @@ class UnscentedKalmanFilter(KalmanFilterBase):
                                 np.asarray(self.P, dtype=np.float64), t0s=[self.time],
                                 noise=[dict(noise_pred=npred, noise_upd=nupd, noise_rts=np.zeros((N, 4)))],
                                 on_error="raise")
+        self._sample_hb = hb  # what sample_smoothed re-runs: this track as run() packed it, recorded noise included
         out = _batch.run_batch(hb, smooth=False)
         self._status = int(out["status"][0])
         if self._status & 0x1:
@@ -267,6 +268,25 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         if self._status_smoother & 0x1:
             raise np.linalg.LinAlgError("SVD did not converge")
         return sm[0].reshape(nrows, 4, 1), sP[0]
+
+    def sample_smoothed(self, n_samples: int, random_state: int = 0) -> np.ndarray:
+        """``n_samples`` tracks drawn from the joint smoothing posterior of the track ``run`` filtered, (n_samples, N+1, 4):
+        what ``run_rts_smoother`` gives as a mean and a covariance per row, as whole tracks whose rows are tied together by
+        the smoother gains (``track_estimators.batch.sample_tracks``; no counterpart in the reference).  The track is packed
+        as ``run`` packed it -- the noise ``run`` drew included, so the forward pass is the stored one -- and sampled on the
+        device; the noise ``run_rts_smoother`` would inject into its back-predictions is not part of the posterior and is
+        left out.  ``random_state`` seeds the device generator."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("sample_smoothed() samples the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("sample_smoothed() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        samples, status = _batch.sample_tracks(hb, int(n_samples), seed=int(random_state))
+        self._status_sampler = int(status[0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return samples[:, 0]
 
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
