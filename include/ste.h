@@ -100,6 +100,10 @@ typedef struct ste_ukf_batch_f64 {
                        Bit 11 (0x800): the lean recurrence of the two-kernel form with a lane per track instead of a DPP quad per
                        track (same bits; measurements).  Must not change between the backward calls made on one forward result.
                        Other bits are ignored */
+#define STE_TUNING_EIG_GAINS 0x100           /* bit 8: every smoother gain by the eigenvalue route */
+#define STE_TUNING_TWO_KERNEL_SMOOTHER 0x200 /* bit 9: the two-kernel smoother whatever the batch size */
+#define STE_TUNING_ONE_KERNEL_SMOOTHER 0x400 /* bit 10: the one-kernel smoother whatever the batch size */
+#define STE_TUNING_LANE_RECURRENCE 0x800     /* bit 11: the two-kernel form's recurrence with a lane per track */
 
     /* sigma-fan constants, computed by the host exactly as unscented.py:95,125,132 does (HOST values) */
     double fan_scale; /* n / (1 - W0) */

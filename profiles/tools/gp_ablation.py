@@ -39,7 +39,8 @@ rep("                        acc[m][n][e] = K[(size_t)(i * T + 16 * n + r) * ld 
 out = os.path.join(ROOT, "scratch", "gpx")
 os.makedirs(out, exist_ok=True)
 open(os.path.join(out, "ste_gp_x.hip"), "w").write(src)
-objs = [os.path.join(ROOT, "ship-track-estimators_amd", "lib", "obj", f) for f in ("ste_kernels.hip.o", "ste_prep.hip.o")]
+obj_dir = os.path.join(ROOT, "ship-track-estimators_amd", "lib", "obj")  # every object of the library but the GP's own
+objs = [os.path.join(obj_dir, f) for f in sorted(os.listdir(obj_dir)) if f.endswith(".hip.o") and f != "ste_gp.hip.o"]
 for v in ("BASE", "NODIAG", "NOLEFT", "NOINIT", "NOLOOP"):
     o = os.path.join(out, "gp_%s.o" % v)
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=fast-honor-pragmas",

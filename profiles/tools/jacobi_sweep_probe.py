@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """How many Jacobi sweeps a fan's square root costs on the bench batch, and how many of their rotations any lane needed:
 the instrumented build of csrc/ste_lane.h (-DSTE_DEBUG_SWEEPS: device counters g_dbg, read through ste_dbg_counters, which is
-not part of the ABI).  The figures quoted in ste_lane.h / DESIGN.md section 5 (2.2 sweeps per solve, 99.6 % of the solves need two,
+not part of the ABI).  Every code object of the library has its own copy of g_dbg; ste_dbg_counters reads the copy of
+ste_kernels.hip, which holds the lane-per-track forward pass this script measures.  The figures quoted in ste_lane.h / DESIGN.md section 5 (2.2 sweeps per solve, 99.6 % of the solves need two,
 15 % of the executed rotations are identities) come from this script.
 
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -ffp-contract=fast-honor-pragmas -mllvm -disable-machine-licm \

@@ -75,7 +75,7 @@ __device__ __forceinline__ bool jacobi_needs_sweep(const double (&a)[10]) {
 }
 
 #ifdef STE_DEBUG_SWEEPS
-__device__ unsigned long long g_dbg[64];
+static __device__ unsigned long long g_dbg[64];  // internal linkage: one copy per code object that includes this header
 __device__ __forceinline__ void dbg_sweep_probe(const double (&a)[10], int sweep) {
     const bool need = jacobi_needs_sweep(a);
     int pairs_wave = 0, pairs_lane = 0;

@@ -21,6 +21,12 @@ STE_FLAG_LANES_1 = 0x10
 STE_FLAG_LANES_4 = 0x20
 STE_FLAG_PACKED_COV = 0x40
 
+# ste_ukf_batch_f64.tuning
+STE_TUNING_EIG_GAINS = 0x100  # every smoother gain by the eigenvalue route
+STE_TUNING_TWO_KERNEL_SMOOTHER = 0x200  # the two-kernel smoother whatever the batch size
+STE_TUNING_ONE_KERNEL_SMOOTHER = 0x400  # the one-kernel smoother whatever the batch size
+STE_TUNING_LANE_RECURRENCE = 0x800  # the two-kernel form's recurrence with a lane instead of a quad per track
+
 STE_NOISE_R_BLOCK2 = 0x1  # ste_ukf_noise_f64.flags: every track's R is zero outside its leading 2 x 2 block
 
 STE_RTS_WORK_ROWS = 30  # doubles per (step, track) of ste_ukf_batch_f64.rts_work

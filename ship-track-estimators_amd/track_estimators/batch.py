@@ -914,10 +914,10 @@ def smoother_tile_order(items: np.ndarray, ntiles: Sequence[int]) -> np.ndarray:
 
 
 # What decides between the smoother's two forms (csrc/ste_kernels.hip: kLeanSmootherMaxTracks and the tuning bits that
-# lean_smoother() looks at; include/ste.h: ste_ukf_batch_f64.tuning)
+# lean_smoother() looks at; include/ste.h: STE_TUNING_*)
 LEAN_SMOOTHER_MAX_TRACKS = 4096  # up to this many tracks: two kernels (all gains, then a lean recurrence); one kernel above
-TUNING_TWO_KERNEL_SMOOTHER = 0x200  # ... two kernels whatever the batch size
-TUNING_ONE_KERNEL_SMOOTHER = 0x400  # ... one kernel whatever the batch size
+TUNING_TWO_KERNEL_SMOOTHER = binding.STE_TUNING_TWO_KERNEL_SMOOTHER  # ... two kernels whatever the batch size
+TUNING_ONE_KERNEL_SMOOTHER = binding.STE_TUNING_ONE_KERNEL_SMOOTHER  # ... one kernel whatever the batch size
 
 
 def _one_kernel_smoother(st) -> bool:
