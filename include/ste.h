@@ -16,6 +16,8 @@
  *   ste_sigma_points_f64     UnscentedKalmanFilter.compute_sigma_points  unscented.py:76-107
  *   ste_track_prep_f64       ShipTrack.calculate_sog / _cog / _sog_rate / _cog_rate / get_measurements
  *                            src/track_estimators/ship_track.py:197-338 (distance / heading: utils.py:9-147)
+ *   ste_path_metrics_f64     distance sailed and line-crossing times of tracks that stay on the device (smoothed, filtered or
+ *                            sampled): per-leg utils.haversine_formula / geographiclib_distance (utils.py:9-113), summed
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -47,7 +49,8 @@ extern "C" {
                            the innovation log-likelihood of the forward pass (ste_ukf_loglik_f64,
                            ste_ukf_forward_loglik_f64).  Unnumbered addition: the posterior of the time derivative on the
                            GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).  Unnumbered addition: posterior tracks
-                           sampled from the smoother (ste_urtss_sample_f64).
+                           sampled from the smoother (ste_urtss_sample_f64).  Unnumbered addition: path quantities of tracks on the
+                           device (ste_path_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -327,6 +330,49 @@ int ste_urtss_sample_prepare_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise
 int ste_urtss_sample_draw_f64(const ste_ukf_batch_f64* b, const ste_ukf_sample_f64* sm, void* stream);
 /* both, back to back on one stream */
 int ste_urtss_sample_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64* sm, void* stream);
+
+/*
+ * PATH QUANTITIES of tracks that stay on the device (an unnumbered addition, like ste_ukf_sample_f64): distance sailed and the
+ * time at which a track first crosses a meridian or a parallel.  `states` holds S tracks per ship in the layout of the
+ * sampler's output; sm_mean and fwd_mean have the layout of one sample ([Nmax+1][4][track_stride], S = 1), so the same call
+ * serves a deterministic track.  Values are one or two doubles per (sample, ship): what carries a posterior over tracks into
+ * a posterior over a distance or a crossing time without the samples leaving the device.
+ *   - Leg.  Leg k of track t joins rows k and k + 1, for k < nsteps[t].  Its length in km is the distance ste_track_prep_f64
+ *     computes for two observations under the same `model`: haversine on the 6378.137 km sphere (STE_PREP_SPHERE) or the
+ *     WGS84 geodesic by Karney's algorithm (STE_PREP_WGS84) -- the same formulas, with the heading dropped.
+ *   - Distance.  dist is the sum of the legs in step order, k = 0, 1, ...: a value's bits depend on nothing but that track's
+ *     rows (not on S, the window, the other outputs asked for).  cumdist row 0 is 0, row k the first k legs; dist equals
+ *     cumdist row nsteps[t] bit for bit.  A track with nsteps == 0 has distance 0 and no crossing.
+ *   - Offset from the line, with v = line_value[t] in degrees.  A parallel (line_axis 1): a_k = lat_k - v.  A meridian
+ *     (line_axis 0): a_k = wrap180(lon_k - v), wrap180(x) = floored_mod(x + 180, 360) - 180, in [-180, 180).
+ *   - Crossing.  Step k crosses when (a_k < 0) != (a_{k+1} < 0); for a meridian also |a_{k+1} - a_k| < 180 must hold, which
+ *     excludes passing the antipodal meridian.  ncross counts the crossing steps.
+ *   - Crossing time.  cross_time is that of the FIRST crossing step k, in hours from row 0: T_k + dt_k a_k / (a_k - a_{k+1}),
+ *     T_k the in-order sum dt_0 + ... + dt_{k-1} of that track; NaN when no step crosses.
+ *   - Non-finite values.  A NaN coordinate makes dist (and cumdist from that leg on) NaN and counts as no crossing: a step
+ *     with a non-finite offset at either end does not cross.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch, dt only when a line
+ *     is given, and writes nothing of the batch.  Per-track arrays are addressed a[row * track_stride + t] with the pointers
+ *     naming the window's first track, like the sampler's; nsteps and line_value point at the window's first entry.
+ *   - Rows past nsteps[t] of states are not read; rows past nsteps[t] of cumdist are not written.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or pm NULL; states NULL; nstates < 1 or
+ *     > 65535; an unknown model; line_axis outside {-1, 0, 1}; reserved != 0; a line without line_value or without b->dt;
+ *     cross_time or ncross given without a line; every output NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B.
+ */
+typedef struct ste_path_f64 {
+    int32_t nstates;          /* S >= 1 tracks per ship in `states` */
+    int32_t model;            /* STE_PREP_SPHERE or STE_PREP_WGS84: the leg function of ste_track_prep_f64 */
+    const double* states;     /* DEVICE [S][Nmax+1][4][track_stride]; only components 0 (lon) and 1 (lat) are read */
+    double* dist;             /* DEVICE [S][track_stride] out or NULL: km along rows 0..nsteps[t] */
+    double* cumdist;          /* DEVICE [S][Nmax+1][track_stride] out or NULL: row 0 = 0, row k = first k legs; rows past nsteps[t] untouched */
+    int32_t line_axis;        /* -1 = no line; 0 = a meridian (lon = line_value[t]); 1 = a parallel (lat = line_value[t]) */
+    int32_t reserved;         /* must be 0 */
+    const double* line_value; /* DEVICE [track_stride], degrees, per track; required when line_axis >= 0 */
+    double* cross_time;       /* DEVICE [S][track_stride] out or NULL: hours from row 0 to the FIRST crossing, NaN = none */
+    int32_t* ncross;          /* DEVICE [S][track_stride] out or NULL: number of crossing steps */
+} ste_path_f64;               /* 64 bytes */
+
+int ste_path_metrics_f64(const ste_ukf_batch_f64* b, const ste_path_f64* pm, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

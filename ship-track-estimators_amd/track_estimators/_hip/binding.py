@@ -124,6 +124,23 @@ class SteUkfSampleF64(C.Structure):
 STE_SAMPLE_COEF_ROWS = 30  # doubles per (row, track) of ste_ukf_sample_f64.coef
 
 
+class StePathF64(C.Structure):
+    """Mirror of ``struct ste_path_f64`` (include/ste.h): distance sailed and line-crossing times of tracks on the device."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("dist", _dp),
+        ("cumdist", _dp),
+        ("line_axis", C.c_int32),
+        ("reserved", C.c_int32),
+        ("line_value", _dp),
+        ("cross_time", _dp),
+        ("ncross", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -231,6 +248,7 @@ SYMBOLS = {
     "ste_urtss_sample_draw_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfSampleF64), C.c_void_p]),
     "ste_urtss_sample_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteUkfSampleF64),
                                        C.c_void_p]),
+    "ste_path_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePathF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

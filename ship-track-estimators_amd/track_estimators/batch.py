@@ -759,6 +759,101 @@ class DeviceBatch:
             self._mark_use(st)
         return out
 
+    # -- path quantities ------------------------------------------------------------------------------------------
+    _PATH_MODELS = {"sphere": binding.STE_PREP_SPHERE, "wgs84": binding.STE_PREP_WGS84}
+    _PATH_AXES = {"lon": 0, "lat": 1}
+
+    def path_metrics(self, states, model: str = "sphere", cumulative: bool = False, line_axis=None, line_value=None,
+                     stream=None):
+        """Distance sailed and, given a line, the time of its first crossing, for tracks that are on the device
+        (include/ste.h: ste_path_metrics_f64; DESIGN.md, "Path quantities").  ``states``: a float64 device tensor
+        (S, Nmax+1, 4, B) or (Nmax+1, 4, B) -- what ``sample_smoothed`` returned, ``self.sm_mean``, ``self.fwd_mean`` -- of which
+        rows 0 .. nsteps[b] of components 0 (lon) and 1 (lat) are read.  ``model``: "sphere" (haversine, 6378.137 km) or
+        "wgs84" (Karney's inverse geodesic), the leg functions of ``prepare_observations``.  ``line_axis``: "lon" (a
+        meridian) or "lat" (a parallel) at ``line_value`` degrees, a scalar or one value per track ((B,) array or tensor).
+        Returns a dict of device tensors: ``distance`` (S, B) in km; with ``cumulative`` also ``cumulative`` (S, Nmax+1, B),
+        row k = the first k legs, NaN past ``nsteps[b]``; with a line ``cross_time`` (S, B), hours from row 0 to the first
+        crossing, NaN where the track never crosses, and ``ncross`` (S, B) int32, the number of crossing steps.
+        A window of a resident batch (``window(lo, hi)``) takes its own tracks, B = hi - lo; a tensor that already is a view
+        of the fleet's full-width rows (``window.sm_mean``) is read in place, anything else is made contiguous first.  Every
+        value depends on its own track's rows alone, so a window, a slice of the samples or a call without the line give the
+        same bits.  ``stream`` is ordered as in ``sample_smoothed``."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        if line_axis is not None and line_axis not in self._PATH_AXES:
+            raise ValueError(f"line_axis must be None, 'lon' or 'lat', got {line_axis!r}")
+        if (line_axis is None) != (line_value is None):
+            raise ValueError("line_axis and line_value go together: a line is an axis ('lon' / 'lat') and its value in degrees")
+        S = int(states.shape[0])
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        with torch.cuda.stream(st):
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if line_axis is not None and ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            dist = torch.empty((S, width), **f64)
+            cum = torch.full((S, N + 1, width), float("nan"), **f64) if cumulative else None
+            pm = binding.StePathF64()
+            pm.nstates, pm.model, pm.states = S, self._PATH_MODELS[model], states.data_ptr()
+            pm.dist = dist.data_ptr() + 8 * col
+            pm.cumdist = None if cum is None else cum.data_ptr() + 8 * col
+            pm.line_axis, pm.reserved = -1, 0
+            ct = nc = None
+            if line_axis is not None:
+                lv = torch.as_tensor(line_value, dtype=torch.float64).to(self.device)
+                if lv.dim() == 0:
+                    lv = lv.expand(B)
+                if tuple(lv.shape) != (B,):
+                    raise ValueError(f"line_value must be a scalar or have shape ({B},), got {tuple(lv.shape)}")
+                line = torch.zeros((width,), **f64)
+                line[col:col + B] = lv
+                ct = torch.empty((S, width), **f64)
+                nc = torch.empty((S, width), dtype=torch.int32, device=self.device)
+                pm.line_axis, pm.line_value = self._PATH_AXES[line_axis], line.data_ptr() + 8 * col
+                pm.cross_time, pm.ncross = ct.data_ptr() + 8 * col, nc.data_ptr() + 4 * col
+                keep.append(line)
+            binding.check(self.lib.ste_path_metrics_f64(C.byref(s), C.byref(pm), self._stream(st)), "ste_path_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            out = {"distance": dist[:, col:col + B]}
+            if cum is not None:
+                out["cumulative"] = cum[..., col:col + B]
+            if ct is not None:
+                out["cross_time"], out["ncross"] = ct[:, col:col + B], nc[:, col:col + B]
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -1759,6 +1854,70 @@ def sample_tracks(hb_or_db, nsamples: int, seed: int = 0, device="cuda:0"):
     dev_t = t.permute(0, 3, 1, 2).contiguous()
     status = db.sample_status.cpu().numpy()
     return dev_t.cpu().numpy(), status
+
+
+def path_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, model: str = "sphere", line_axis=None,
+                    line_value=None, quantiles=(0.05, 0.5, 0.95), device="cuda:0"):
+    """Distance sailed -- and, given a line, the time of its first crossing -- with the uncertainty of the smoothing posterior,
+    per track: ``nsamples`` posterior tracks are drawn (``DeviceBatch.sample_smoothed``), reduced to their path quantities
+    (``DeviceBatch.path_metrics``) and discarded, ``chunk`` samples at a time, so ``nsamples`` is not bounded by memory (one
+    draw buffer of ``min(chunk, nsamples)`` samples is allocated once and refilled from one generator; what stays is
+    (nsamples, B)).  Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother first; a ``DeviceBatch``
+    (or a window of one) is taken to hold a completed ``run()``.  ``model``, ``line_axis`` and ``line_value`` as in
+    ``path_metrics``.
+
+    Returns a dict of NumPy arrays in the batch's slot order (``hb.order`` maps slots to the caller's tracks):
+    ``distance_smoothed`` (B,), the distance of the smoothed track ``sm_mean``; ``distance`` (nsamples, B);
+    ``distance_mean``, ``distance_std`` (B,; ddof = 1, 0 for a single sample) and ``distance_quantiles`` (len(quantiles), B);
+    with a line ``cross_time`` (nsamples, B), NaN where a sample never crosses, ``cross_prob`` (B,), the fraction of samples
+    that cross, and ``cross_time_quantiles`` (len(quantiles), B) over the samples that cross, NaN where none does; and
+    ``status`` (B,), the sampler's STE_STATUS_* bits.
+
+    The draws depend on ``(seed, chunk)``: the generator is seeded once and every chunk takes the next draws in the layout of
+    a ``chunk``-sample buffer.  With ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("path_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    line = dict(line_axis=line_axis, line_value=line_value)
+    smoothed = db.path_metrics(db.sm_mean, model=model)["distance"][0]
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), dtype=torch.float64, device=db.device)
+    dist = torch.empty((nsamples, B), dtype=torch.float64, device=db.device)
+    ctime = torch.empty((nsamples, B), dtype=torch.float64, device=db.device) if line_axis is not None else None
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        draws = buf[:n]
+        draws.normal_(generator=gen)
+        m = db.path_metrics(db.sample_smoothed(n, draws=draws), model=model, **line)
+        dist[i:i + n] = m["distance"]
+        if ctime is not None:
+            ctime[i:i + n] = m["cross_time"]
+        status |= db.sample_status
+    q = np.asarray(quantiles, dtype=np.float64)
+    d = dist.cpu().numpy()
+    out = {"distance_smoothed": smoothed.cpu().numpy(), "distance": d, "distance_mean": d.mean(axis=0),
+           "distance_std": d.std(axis=0, ddof=1 if nsamples > 1 else 0), "distance_quantiles": np.quantile(d, q, axis=0)}
+    if ctime is not None:
+        ct = ctime.cpu().numpy()
+        out["cross_time"], out["cross_prob"] = ct, (~np.isnan(ct)).mean(axis=0)
+        with warnings.catch_warnings():  # a track that no sample takes across the line: all-NaN column, NaN quantiles
+            warnings.simplefilter("ignore", RuntimeWarning)
+            out["cross_time_quantiles"] = np.nanquantile(ct, q, axis=0)
+    out["status"] = status.cpu().numpy()
+    return out
 
 
 @dataclasses.dataclass

@@ -288,6 +288,33 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return samples[:, 0]
 
+    def distance_sailed(self, n_samples: int = 0, random_state: int = 0, model: str = "sphere"):
+        """Distance in km along the track ``run`` filtered (``track_estimators.batch.path_statistics``; no counterpart in the
+        reference, whose callers loop over ``utils.haversine_formula`` themselves).  ``n_samples == 0``: the distance of the
+        smoothed track, a float.  Otherwise an ``(n_samples,)`` array: the distances of that many tracks drawn from the joint
+        smoothing posterior, those of ``sample_smoothed(n_samples, random_state)``.  ``model``: "sphere" (haversine on the
+        6378.137 km sphere) or "wgs84".  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("distance_sailed() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("distance_sailed() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            return float(db.path_metrics(db.sm_mean, model=model)["distance"][0, 0].item())
+        out = _batch.path_statistics(hb, n_samples, seed=int(random_state), chunk=n_samples, model=model)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return out["distance"][:, 0]
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
