@@ -1,7 +1,10 @@
 """
 track_estimators.geodesic: the WGS84 inverse problem by Karney's algorithm, the restatement of what the reference's
 geographiclib calls compute (/root/reference/src/track_estimators/utils.py:36,68; geographiclib>=2.0 is a third-party
-dependency, absent on both boxes -> PARITY UNPINNED beyond what is pinned here):
+dependency, absent on both boxes, so parity with it cannot be run; the solver is pinned at the nanometre level to the definition
+of a geodesic by tests/test_mp_geodesy.py -- its (s12, azi1), walked from point 1 by a 50-digit direct solution
+(oracle/mp_geodesy.py), lands within 20 nm of point 2 -- and the device solver likewise by tests/test_geodesy_landing.py).  Pinned
+here:
 
   * the values the reference holds: its utils tests (tests/test_utils.py:36-60,87-100) and the noise-free row 0 of its CLI
     example output -- reproduced to the last bit;

@@ -3,9 +3,13 @@ Observation preparation on the device (ste_track_prep_f64).
 
 Sphere model (haversine_formula + heading): pinned to arrays produced by RUNNING the reference's ShipTrack
 (tests/golden/track_prep.npz, made by tests/golden/make_golden.py ``prep_cases``: 40 ragged random tracks, duplicate
-timestamps, the 0/360 seam).  WGS84 model: geographiclib is not installed anywhere this runs, so beyond the one noise-free
-number the reference's CLI fixture holds (row 0) the WGS84 results are **parity unpinned**; those tests compare the
-device with this package's own host restatement of Karney's algorithm (track_estimators/geodesic.py) and say so in their names.
+timestamps, the 0/360 seam).  WGS84 model: geographiclib is not installed anywhere this runs, so the only number of its own the
+reference holds is the noise-free row 0 of its CLI fixture.  The WGS84 path is pinned to the definition of a geodesic instead:
+tests/test_geodesy_landing.py walks the device's (distance, heading) from point 1 with a 50-digit direct solution
+(oracle/mp_geodesy.py) and requires it to land within 20 nm of point 2, over the solver's branches and reflections, and
+tests/test_mp_geodesy.py does the same for the host solver.  The tests here compare the device with this package's host
+restatement of Karney's algorithm (track_estimators/geodesic.py); their names still say "unpinned-beyond-cli-row0", which is
+true of parity with geographiclib itself.
 
 Floating-point tolerance: the device evaluates the same formulas with its own libm and contracted FMAs; distances and
 headings agree to ~1e-13 relative, and the rates -- differences of neighbouring values divided by the gap -- to 1e-9
