@@ -1,33 +1,28 @@
-// ste_kernels.hip — batched UKF forward pass and unscented RTS smoother for gfx950 (MI355X), plus the C ABI of
-// include/ste.h.  fp64 throughout; no MFMA (4x4 contractions); the whole per-track state lives in VGPRs.  The only
-// LDS a kernel of this file declares is g_sched_word, two words in which ukf_forward_sched parks its slice offset; nothing
-// synchronises through LDS.  The quad forward kernel is in ste_forward_quad.hip, what both files share in ste_ukf.h.
+// ste_kernels.hip — batched UKF forward pass, lane per track, the stand-alone unscented RTS smoother and the single-step
+// kernels for gfx950 (MI355X), plus the C ABI of include/ste.h.  fp64 throughout; no MFMA (4x4 contractions); the whole
+// per-track state lives in VGPRs.  The only LDS a kernel of this file declares is g_sched_word, two words in which
+// ukf_forward_sched parks its slice offset; nothing synchronises through LDS.  Three kernel families are in files of their
+// own, each with its launches: the quad forward kernel in ste_forward_quad.hip, the smoothers that read the forward pass's work
+// rows in ste_smooth.hip, the posterior-track sampler in ste_sample.hip.  What the four share on the device is in ste_ukf.h
+// (and ste_smooth.h), the host functions that cross a file in ste_err.h.  The families of this file stay one code object:
+// hipcc shapes ukf_update, propagate_points and propagate_fan_branching by all their callers (profiles/kernels_split.md).
 //
 // Kernels:
-//   ukf_forward_l1 (/ ukf_forward_q4)    forward filter, one lane or one DPP quad per track (chosen by batch size or by
-//                                        flag); with rts_work they also leave the smoother's cross-covariance D and,
+//   ukf_forward_l1                       forward filter, one lane per track (the quad form is chosen by batch size or by
+//                                        flag); with rts_work it also leaves the smoother's cross-covariance D and,
 //                                        where it does not follow from the history, its x_b and P_b
 //   ukf_forward_sched + sched_gate       the forward passes of MANY batches / fleet windows as one launch of resident waves
 //     + sched_upload                     working through a host-made schedule of (64-track tile, time slice) items -- the
 //                                        body is ukf_forward_l1's --, the one-wave gate a smoother's stream waits behind,
 //                                        and the upload of the schedule's table from page-locked memory
-//   urtss_recur_l1                       smoother from those rows, one lane per track: gain K = D pinv(P_b), recurrence
-//                                        (batches that fill the chip)
-//   urtss_recur_sched                    the same body for every window of a scheduled forward launch as one launch: a wave
-//                                        per tile, waiting for its own tile's forward pass
-//   urtss_gains_all + urtss_recur_lean   the same smoother in two kernels for batches of <= 4 096 tracks: every gain of
-//     / urtss_recur_lean_q4              every (step, track) at once, written back into the work rows, then the bare
-//                                        recurrence, one lane or one DPP quad per track -- bit-identical to urtss_recur_l1
 //   urtss_backward_l1                    stand-alone smoother that recomputes everything (rts_work == NULL)
-//   ukf_forward_tn, urtss_recur_tn,      the lane-per-track forward pass (with or without the likelihood) and the smoothers
-//     urtss_gains_all<.., true>,         that read Q, with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
-//     urtss_backward_l1<true>            device functions and kernels, the track's matrices loaded from NoiseParams
-//   urtss_sample_coef + urtss_sample_recur   posterior tracks by backward simulation from the smoother's own gains: the
-//                                        coefficients of every (row, track) at once, then a lane per track and up to 4 samples per lane
+//   ukf_forward_lik, ukf_forward_tn,     the lane-per-track forward pass with the likelihood, and it and the stand-alone
+//     urtss_backward_l1<true>            smoother with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
+//                                        device functions and kernels, the track's matrices loaded from NoiseParams
 //   predict / update / robust_terms / geodetic / sigma_points kernels   single-step API parity
 // All per-step inputs/outputs are SoA with the track index fastest, so a wave's accesses are contiguous runs.
 //
-// Reference semantics (paths relative to /root/reference/src/track_estimators/kalman_filters/):
+// Reference semantics (paths relative to the reference's src/track_estimators/kalman_filters/):
 //   forward  : kalman_filter.py:61-117 (driver), unscented.py:178-207 (predict), :219-265 (update)
 //   backward : unscented.py:285-351 (rts_step)
 #include <hip/hip_runtime.h>
@@ -43,7 +38,6 @@
 #include "../../include/ste.h"
 #include "ste_err.h"
 #include "ste_ukf.h"
-#include "ste_quad.h"
 
 namespace ste {
 
@@ -708,14 +702,6 @@ struct LikParams {
     int32_t* nupd;   // [ld] or nullptr
     double* nis;     // [Nmax+1][ld] or nullptr
 };
-// kTrackNoise: per-track Q and R (ste_ukf_noise_f64), a further kernel argument of the *_tn entry kernels: upper triangles
-// [10][ld] in the order of STE_FLAG_PACKED_COV, track index fastest; nullptr = the shared matrix of KParams.  Q goes into
-// the ten Qv registers once per track (forward) or is read once per track before the backward loop (smoothers); R is
-// read at each update (lane_update / ukf_update).
-struct NoiseParams {
-    const double* Q;
-    const double* R;
-};
 
 template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff, bool kTrackNoise = false>
 __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t, const LikParams* lk = nullptr,
@@ -940,19 +926,6 @@ struct SchedParams {
     int* started;      // optional, zeroed before the launch: waves that have begun (== nwaves: the launch is resident)
 };
 
-// wave-uniform: spin (sleeping) until *flag >= need or the bound is reached
-__device__ __forceinline__ bool sched_wait(const int* flag, int need, unsigned long long timeout_ticks) {
-    if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-            if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) return false;
-            __builtin_amdgcn_s_sleep(64);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
-}
-
 template <bool kGains, bool kFastUpd, bool kRobust>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_sched(const SchedParams sp) {
     typedef const KParams __attribute__((address_space(4))) ConstKParams;  // the table is constant for the launch: scalar loads,
@@ -1012,13 +985,6 @@ __global__ __launch_bounds__(64) void sched_gate(const int* counter, int need, i
 // ---------------------------------------------------------------------------------------------------------------
 // The literal smoother: recomputes the fan, its nine great-circle steps and both pseudo-inverses per step.  Used when
 // there are no work rows from the forward pass (rts_work == NULL, a history that ste_ukf_forward_f64 did not write).
-__device__ __forceinline__ void store_pos(const KParams& p, size_t row, size_t B, size_t t, const double (&xs)[4]) {
-    if (p.sm_pos) {  // the tensor configs[2] exchanges between GPUs: smoothed lon / lat on their own (ste.h: sm_pos)
-        st_stream(&p.sm_pos[(row * 2 + 0) * B + t], xs[0]);
-        st_stream(&p.sm_pos[(row * 2 + 1) * B + t], xs[1]);
-    }
-}
-
 // kTrackNoise: track t's own Q (ste_urtss_backward_noise_f64), nz.Q[tix(r, c) * ld + t], instead of the shared p.m.Q.  nz.Q is
 // not NULL there (launch_backward takes <false> without a per-track Q), and <false> never reads nz.  The body stays in the
 // kernel: moved into an inline function it is optimised before it meets the kernel's arguments and comes out differently.
@@ -1152,837 +1118,6 @@ __global__ __launch_bounds__(64) void urtss_backward_l1(const KParams p, const N
     }
     if (!all_finite(xs, Ps)) st |= STE_STATUS_NAN;
     if (st) atomicOr(&p.status[t], st);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// URTSS backward pass from the rows the forward pass left in rts_work: per step the gain K = D pinv(P_b)
-// (unscented.py:333) and the recurrence of :337-349,
-//     y = x^s_{k+1} - x_b (heading wrapped),  x^s_k = x_k + K y,  P^s_k = P_k + K (P^s_{k+1} - P_b) K^T,
-// one lane per track.  Columns 0-1 of D come from the work row, columns 2-3 from the filtered covariance of row k (or the
-// work row, at and after the track's first bad square root); x_b and P_b from the work row where they were stored (see
-// kWorkD) and otherwise from the filtered rows k and k + 1 the recurrence reads anyway.  Per track-step it reads 8 + 14
-// doubles (D; mean and upper triangle of the filtered covariance), plus 14 on the steps that were followed by an
-// update, and writes the 20 of the smoothed row.  No LDS, no barriers: the kernel is a chain of ~300 fp64 instructions
-// per step whose loads are one row ahead; it is meant to run beside the forward passes of the next batches, whose waves
-// take the issue slots it leaves (batch.SmootherPipeline).  Only reads the work rows: repeatable.
-// ---------------------------------------------------------------------------------------------------------------
-// Is work row k "full" (x_b and P_b stored)?  Mirrors the forward kernels' choice: full when the step was followed by a
-// measurement update (ui = upd_idx[k] names a valid observation), for row 0 of a run that starts with an update, and
-// throughout a run with recorded noise.
-__device__ __forceinline__ bool work_row_full(const KParams& p, int k, int ui, bool always_full) {
-    return always_full || (ui >= 0 && ui < p.Tmax) || (k == 0 && !(p.flags & STE_FLAG_NO_INITIAL_UPDATE));
-}
-
-struct RecurRow {
-    double D2[8], xk[4], Pk[10];  // columns 0-1 of D of step k (rows 2-3 only with recorded noise); filtered row k
-    double shift[2];              // smoother rates that differ from the forward rates: what they add to x_b[2:4]
-};
-// Speed and heading pass through the process model as x + rate * dt (non_linear_process.py:74-75) and the position
-// components do not see the rates at all, so a smoother step that uses other rates than the forward step did
-// (unscented.py:287-292: the smoother indexes the repeated rate arrays by step) sees the same propagated fan moved by
-// (0, 0, d_sog * dt, d_cog * dt): x_b moves by that much, the fan's spread and D not at all, and P_b -- taken about the
-// filtered mean x_k (:324-325) -- becomes C + b' b'^T with the new b' = x_b' - x_k.
-template <bool kShift>
-__device__ __forceinline__ void load_recur_row(const KParams& p, size_t k, size_t B, size_t t, bool d_rows23, RecurRow& g) {
-    g.shift[0] = g.shift[1] = 0.0;
-    if (kShift) {
-        const double dt = p.dt[k * B + t];
-        if (p.sog_rate_rts) g.shift[0] = (p.sog_rate_rts[k * B + t] - p.sog_rate[k * B + t]) * dt;
-        if (p.cog_rate_rts) g.shift[1] = (p.cog_rate_rts[k * B + t] - p.cog_rate[k * B + t]) * dt;
-    }
-    const double* w = p.rts_work + (k * kWorkElems) * B + t;
-    STE_UNROLL
-    for (int e = 0; e < 4; ++e) g.D2[e] = w[(kWorkD + e) * B];
-    if (d_rows23) {
-        STE_UNROLL
-        for (int e = 4; e < 8; ++e) g.D2[e] = w[(kWorkD + e) * B];
-    }
-    load_vec(p.fwd_mean, k, B, t, g.xk);
-    load_cov_p(p.fwd_cov, (p.flags & STE_FLAG_PACKED_COV) != 0, k, B, t, g.Pk);
-}
-
-// What the smoother's step k needs besides the recurrence itself: x_b, P_b (stored, or rebuilt from history rows k and
-// k + 1) and the gain K = D pinv(P_b) (unscented.py:315-333).  `cur` = work-row / history data of step k, (xn, Pn) = filtered
-// row k + 1, `full` = work row k holds x_b and P_b.  Shared by the one-kernel smoother (urtss_recur_l1) and the two-kernel
-// form for small batches (urtss_gains_all + urtss_recur_lean): same code, same bits.
-// kTrackNoise: the four entries of Q it reads come from `q4` (Q[0][2], Q[0][3], Q[1][2], Q[1][3] of this track, see
-// track_q4) instead of from the kernel arguments.
-template <bool kShift, bool kTrackNoise = false>
-__device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_t B, size_t t, const RecurRow& cur,
-                                                  const double (&xn)[4], const double (&Pn)[10], bool full, bool always_full,
-                                                  bool all_eig, double kappa, double first_bad, double (&xb)[4],
-                                                  double (&Pb)[10], double (&K)[4][4], const double* q4 = nullptr) {
-    // x_b, P_b: stored (a quarter of the steps of the bench batch: loaded here, not a row ahead, to keep the
-    // registers of a whole row free), or the prediction itself -- the step was not followed by an update, so row
-    // k + 1 of the filtered history is x^-, P^-, and P_b = P^- + b b^T with b = x^- - x_k
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) xb[c] = xn[c];
-    if (kShift) {  // the smoother's own rates (load_recur_row)
-        xb[2] += cur.shift[0];
-        xb[3] += cur.shift[1];
-    }
-    {
-        double bv[4];
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) bv[c] = xb[c] - cur.xk[c];
-        STE_UNROLL
-        for (int r = 0; r < 4; ++r) {
-            STE_UNROLL
-            for (int c = r; c < 4; ++c) Pb[tix(r, c)] = fma(bv[r], bv[c], Pn[tix(r, c)]);
-        }
-    }
-    if (full) {
-        const double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) xb[c] = w[(kWorkXb + c) * B];
-        STE_UNROLL
-        for (int e = 0; e < 10; ++e) Pb[e] = w[(kWorkPb + e) * B];
-        if (kShift) {
-            // stored with the forward rates: P_b = C + b b^T with b = (weighted mean of the fan) - x_k, i.e. x_b - x_k
-            // less the recorded noise that was added to x_b (unscented.py:319-325); now b' = b + s, s = (0, 0, shift):
-            // P_b' = P_b + b s^T + s b^T + s s^T
-            double bv[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) bv[c] = xb[c] - cur.xk[c];
-            if (p.noise_rts) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) bv[c] -= p.noise_rts[((size_t)k * 4 + c) * B + t];
-            }
-            const double s2 = cur.shift[0], s3 = cur.shift[1];
-            Pb[tix(0, 2)] = fma(bv[0], s2, Pb[tix(0, 2)]);
-            Pb[tix(1, 2)] = fma(bv[1], s2, Pb[tix(1, 2)]);
-            Pb[tix(0, 3)] = fma(bv[0], s3, Pb[tix(0, 3)]);
-            Pb[tix(1, 3)] = fma(bv[1], s3, Pb[tix(1, 3)]);
-            Pb[tix(2, 2)] = fma(bv[2] + bv[2] + s2, s2, Pb[tix(2, 2)]);
-            Pb[tix(3, 3)] = fma(bv[3] + bv[3] + s3, s3, Pb[tix(3, 3)]);
-            Pb[tix(2, 3)] = fma(bv[2], s3, fma(s2, bv[3] + s3, Pb[tix(2, 3)]));
-            xb[2] += s2;
-            xb[3] += s3;
-        }
-    }
-    // the gain K = D pinv(P_b) (unscented.py:333)
-    double D[4][4];
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        D[r][0] = cur.D2[r * 2 + 0];
-        D[r][1] = cur.D2[r * 2 + 1];
-        D[r][2] = kappa * cur.Pk[tix(r, 2)];
-        D[r][3] = kappa * cur.Pk[tix(r, 3)];
-    }
-    if (!always_full) {
-        // rows 2-3 of D's first two columns are the cross moments of (speed, heading) with (lon, lat) about the
-        // predicted mean, i.e. the corresponding entries of P^- before Q was added.  Where the step was not followed
-        // by an update P^- is row k + 1 of the filtered history itself; on a full row (x_b, P_b stored) it is
-        // P_b - b b^T with b = x_b - x_k (no recorded noise here): D[2:4, 0:2] = (P^- - Q)[0:2, 2:4]^T.  (Forming
-        // P_b = P^- + b b^T first and subtracting b b^T again on every row cost ~eps |b_c b_r| on small cross moments.)
-        double bv[4];
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) bv[c] = xb[c] - cur.xk[c];
-        STE_UNROLL
-        for (int r = 2; r < 4; ++r) {
-            STE_UNROLL
-            for (int c = 0; c < 2; ++c) {
-                const double pm = full ? fma(-bv[c], bv[r], Pb[tix(c, r)]) : Pn[tix(c, r)];
-                if constexpr (kTrackNoise)
-                    D[r][c] = pm - q4[c * 2 + (r - 2)];
-                else
-                    D[r][c] = pm - p.m.Q[c * 4 + r];
-            }
-        }
-    }
-    if (__builtin_expect(__any((double)k >= first_bad), 0)) {
-        if ((double)k >= first_bad) {
-            const double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                D[r][2] = w[(kWorkD23 + r * 2 + 0) * B];
-                D[r][3] = w[(kWorkD23 + r * 2 + 1) * B];
-            }
-        }
-    }
-    return smoother_gain(Pb, D, all_eig, K);
-
-}
-
-// Per-track noise: the entries (0,2) (0,3) (1,2) (1,3) of track t's Q, once per track (or per lane of urtss_gains_all)
-__device__ __forceinline__ void track_q4(const KParams& p, const NoiseParams& nz, size_t B, size_t t, double (&q4)[4]) {
-    STE_UNROLL
-    for (int c = 0; c < 2; ++c) {
-        STE_UNROLL
-        for (int r = 2; r < 4; ++r) q4[c * 2 + (r - 2)] = nz.Q ? nz.Q[(size_t)tix(c, r) * B + t] : p.m.Q[c * 4 + r];
-    }
-}
-
-// kShift: the smoother has rates of its own (sog_rate_rts / cog_rate_rts); compiled out for batches that share them.
-template <bool kShift, bool kTrackNoise = false>
-__device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t, const NoiseParams* nz = nullptr) {
-    const size_t B = (size_t)p.ld;
-    if (t >= (size_t)p.B) return;
-    double q4[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (kTrackNoise) track_q4(p, *nz, B, t, q4);
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
-    const bool all_eig = (p.tuning & STE_TUNING_EIG_GAINS) != 0;
-    const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;  // D[:, 2:4] = kappa P_k[:, 2:4] for an exact square root
-    // first step at and after which this track's columns 2-3 of D are stored (kNeverBad: never)
-    const double first_bad = p.first_bad[t];
-    const int last_row = p.Nmax > 0 ? p.Nmax - 1 : 0;
-    auto clampk = [&](int k) -> int { return min(max(k, 0), last_row); };
-
-    // row ns: smoothed = filtered; it is also "filtered row k + 1" of the first step
-    double xs[4], Ps[10], xn[4], Pn[10];
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    load_vec(p.fwd_mean, (size_t)ns, B, t, xs);
-    load_cov_p(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
-    store_vec(p.sm_mean, (size_t)ns, B, t, xs);
-    store_cov_p(p.sm_cov, packed, (size_t)ns, B, t, Ps);
-    store_pos(p, (size_t)ns, B, t, xs);
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) xn[c] = xs[c];
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) Pn[e] = Ps[e];
-
-    // the row of the first step this lane processes, and the update index of the one after it, in flight
-    RecurRow nxt;
-    int ui_n = -1;
-    if (ns > 0) {
-        load_recur_row<kShift>(p, (size_t)(ns - 1), B, t, always_full, nxt);
-        ui_n = p.upd_idx[(size_t)(ns - 1) * B + t];
-    }
-    int st = 0;
-    for (int k = p.Nmax - 1; k >= 0; --k) {
-        if (!__any(k < ns)) continue;  // ragged batch: nobody in this wave has reached its last step yet
-        if (k < ns) {
-            const RecurRow cur = nxt;
-            const bool full = work_row_full(p, k, ui_n, always_full);
-            double xb[4], Pb[10], K[4][4];
-            st |= smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
-            // the row of the next step: in flight during the recurrence arithmetic below (and across the loop edge)
-            {
-                const int kn = clampk(k - 1);
-                load_recur_row<kShift>(p, (size_t)kn, B, t, always_full, nxt);
-                ui_n = p.upd_idx[(size_t)kn * B + t];
-            }
-            double y[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) y[c] = xs[c] - xb[c];
-            y[3] = wrap180(y[3]);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                double acc = cur.xk[r];
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) acc = fma(K[r][c], y[c], acc);
-                xs[r] = acc;
-            }
-            xs[3] = floored_mod(xs[3], 360.0);
-            // P^s_k = P_k + K (P^s_{k+1} - P_b) K^T, symmetric operands packed
-            double dP[10];
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) dP[e] = Ps[e] - Pb[e];
-            double KdP[4][4];
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) {
-                    double acc = K[r][0] * dP[tix(0, c)];
-                    STE_UNROLL
-                    for (int i = 1; i < 4; ++i) acc = fma(K[r][i], dP[tix(i, c)], acc);
-                    KdP[r][c] = acc;
-                }
-            }
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = r; c < 4; ++c) {
-                    double acc = KdP[r][0] * K[c][0];
-                    STE_UNROLL
-                    for (int i = 1; i < 4; ++i) acc = fma(KdP[r][i], K[c][i], acc);
-                    Ps[tix(r, c)] = cur.Pk[tix(r, c)] + acc;
-                }
-            }
-            store_vec(p.sm_mean, (size_t)k, B, t, xs);
-            store_cov_p(p.sm_cov, packed, (size_t)k, B, t, Ps);
-            store_pos(p, (size_t)k, B, t, xs);
-            // row k becomes "row k + 1" of the next step
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) xn[c] = cur.xk[c];
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) Pn[e] = cur.Pk[e];
-        }
-    }
-    double chk = 0.0;
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) chk += xs[c] * 0.0;
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) chk += Ps[e] * 0.0;
-    if (!(chk == 0.0)) st |= STE_STATUS_NAN;
-    if (st) atomicOr(&p.status[t], st);
-}
-
-template <bool kShift>
-__global__ __launch_bounds__(64) void urtss_recur_l1(const KParams p) {
-    smooth_tile_l1<kShift>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
-}
-template <bool kShift>
-__global__ __launch_bounds__(64) void urtss_recur_tn(const KParams p, const NoiseParams nz) {
-    smooth_tile_l1<kShift, true>(p, (size_t)blockIdx.x * 64 + threadIdx.x, &nz);
-}
-
-// The smoothers of every window of a scheduled forward launch as ONE launch (ste_urtss_backward_sched_f64): a wave per
-// (window, 64-track tile), in the order the schedule finishes the tiles, each waiting (bounded) for ITS tile's last slice
-// -- a tile is smoothed as soon as it has been filtered, not when the last tile of its window has.  The body is
-// urtss_recur_l1's.  Waves that wait hold a wave slot each: the launch goes behind a gate on the forward launch's started-wave
-// count, so that every forward wave has its SIMD before a waiting smoother wave could be in its way (include/ste.h).
-struct SmoothItem {
-    int kp;    // index of the window's parameter block
-    int tile;  // 64-track tile of that window
-    int prog;  // index of the tile's progress counter (the forward launch's)
-    int need;  // slices of a forward pass of that window: the count the tile's counter reaches
-};
-struct SmoothSchedParams {
-    const KParams* kps;
-    const SmoothItem* items;
-    const int* progress;
-    int* error;  // 2 = a smoother wave waited longer than its bound
-    unsigned long long timeout_ticks;
-};
-template <bool kShift>
-__global__ __launch_bounds__(64) void urtss_recur_sched(const SmoothSchedParams sp) {
-    typedef const KParams __attribute__((address_space(4))) ConstKParams;
-    const SmoothItem* ip = sp.items + blockIdx.x;
-    const int kp = __builtin_amdgcn_readfirstlane(ip->kp), tile = __builtin_amdgcn_readfirstlane(ip->tile);
-    const int prog = __builtin_amdgcn_readfirstlane(ip->prog), need = __builtin_amdgcn_readfirstlane(ip->need);
-    if (__hip_atomic_load(sp.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ||
-        !sched_wait(sp.progress + prog, need, sp.timeout_ticks)) {
-        if (threadIdx.x == 0) __hip_atomic_store(sp.error, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    const KParams& p = *(const KParams*)(ConstKParams*)(uintptr_t)(sp.kps + kp);
-    smooth_tile_l1<kShift>(p, (size_t)tile * 64 + threadIdx.x);
-}
-
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// The same smoother in two kernels, for SMALL batches (a few waves: the real-data runs -- BASELINE configs[0] and [3], the
-// reference's 116-ship file).  There a wave of urtss_recur_l1 has a SIMD, indeed most of the chip, to itself, and its step
-// is a chain: the loads of x_b / P_b on full rows issued where they are needed, the gain solve (with the eigenvalue route out
-// of line for lanes whose P_b is close to singular), then the recurrence -- 4.7 us per step on configs[3].  But only the
-// recurrence  x^s_k = x_k + K_k (x^s_{k+1} - x_b),  P^s_k = P_k + K_k (P^s_{k+1} - P_b) K_k^T  is sequential; x_b, P_b and the
-// gain K_k = D_k pinv(P_b) depend on the forward pass alone (unscented.py:297-333).  So:
-//   urtss_gains_all   one lane per (step, track): x_b, P_b, K for every step of every track at once, written back into the
-//                     work row of that step (K over the D columns it was formed from, x_b and P_b into their slots on every row);
-//   urtss_recur_lean  one lane per track: loads K, x_b, P_b and the filtered row a step ahead, runs the recurrence.
-// Same device functions, same arithmetic, same bits as urtss_recur_l1.  The work rows hold K afterwards: the word that keeps
-// a track's first bad square root is stored negated (-(v) - 1) by the second kernel to say so, and a repeated
-// ste_urtss_backward_f64 on the same forward result skips the first kernel (the call stays repeatable).  Not for large
-// batches: 440 B more traffic per track-step, which a batch that fills the chip cannot afford (launch_backward).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kLeanK01 = kWorkD, kLeanK23 = kWorkD23;  // K[r][0:2] at kLeanK01 + 2 r, K[r][2:4] at kLeanK23 + 2 r
-
-// kTrackNoise: this lane's track's four entries of Q (track_q4) go to smoother_step_gain; the shared instantiations never read nz.
-template <bool kShift, bool kTrackNoise>
-__global__ __launch_bounds__(64) void urtss_gains_all(const KParams p, const NoiseParams nz) {
-    const size_t B = (size_t)p.ld;
-    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= (size_t)p.B * (size_t)p.Nmax) return;
-    const size_t t = g % (size_t)p.B;
-    const int k = (int)(g / (size_t)p.B);
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    if (k >= ns) return;
-    const double fb_raw = p.first_bad[t];
-    if (fb_raw < 0.0) return;  // the rows of this track already hold gains (a repeated backward call)
-    const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
-    const bool all_eig = (p.tuning & STE_TUNING_EIG_GAINS) != 0;
-    const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    RecurRow cur;
-    load_recur_row<kShift>(p, (size_t)k, B, t, always_full, cur);
-    double xn[4], Pn[10];
-    load_vec(p.fwd_mean, (size_t)k + 1, B, t, xn);
-    load_cov_p(p.fwd_cov, packed, (size_t)k + 1, B, t, Pn);
-    const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
-    double xb[4], Pb[10], K[4][4], q4[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (kTrackNoise) track_q4(p, nz, B, t, q4);
-    const int st = smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K, q4);
-    double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        w[(kLeanK01 + 2 * r + 0) * B] = K[r][0];
-        w[(kLeanK01 + 2 * r + 1) * B] = K[r][1];
-        w[(kLeanK23 + 2 * r + 0) * B] = K[r][2];
-        w[(kLeanK23 + 2 * r + 1) * B] = K[r][3];
-    }
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) w[(kWorkXb + c) * B] = xb[c];
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) w[(kWorkPb + e) * B] = Pb[e];
-    if (st) atomicOr(&p.status[t], st);
-}
-
-struct LeanRow {
-    double K[4][4], xb[4], Pb[10], xk[4], Pk[10];
-};
-__device__ __forceinline__ void load_lean_row(const KParams& p, size_t k, size_t B, size_t t, bool packed, LeanRow& g) {
-    const double* w = p.rts_work + (k * kWorkElems) * B + t;
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        g.K[r][0] = w[(kLeanK01 + 2 * r + 0) * B];
-        g.K[r][1] = w[(kLeanK01 + 2 * r + 1) * B];
-        g.K[r][2] = w[(kLeanK23 + 2 * r + 0) * B];
-        g.K[r][3] = w[(kLeanK23 + 2 * r + 1) * B];
-    }
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) g.xb[c] = w[(kWorkXb + c) * B];
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) g.Pb[e] = w[(kWorkPb + e) * B];
-    load_vec(p.fwd_mean, k, B, t, g.xk);
-    load_cov_p(p.fwd_cov, packed, k, B, t, g.Pk);
-}
-
-__global__ __launch_bounds__(64) void urtss_recur_lean(const KParams p) {
-    const size_t B = (size_t)p.ld;
-    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (size_t)p.B) return;
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    const int last_row = p.Nmax > 0 ? p.Nmax - 1 : 0;
-    {
-        const double fb = p.first_bad[t];
-        if (fb >= 0.0) p.first_bad[t] = -fb - 1.0;  // the work rows of this track hold gains from here on (see above)
-    }
-    double xs[4], Ps[10];
-    load_vec(p.fwd_mean, (size_t)ns, B, t, xs);
-    load_cov_p(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
-    store_vec(p.sm_mean, (size_t)ns, B, t, xs);
-    store_cov_p(p.sm_cov, packed, (size_t)ns, B, t, Ps);
-    store_pos(p, (size_t)ns, B, t, xs);
-    LeanRow nxt;
-    if (ns > 0) load_lean_row(p, (size_t)(ns - 1), B, t, packed, nxt);
-    for (int k = p.Nmax - 1; k >= 0; --k) {
-        if (!__any(k < ns)) continue;
-        if (k < ns) {
-            const LeanRow cur = nxt;
-            load_lean_row(p, (size_t)min(max(k - 1, 0), last_row), B, t, packed, nxt);  // in flight during this step's arithmetic
-            double y[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) y[c] = xs[c] - cur.xb[c];
-            y[3] = wrap180(y[3]);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                double acc = cur.xk[r];
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) acc = fma(cur.K[r][c], y[c], acc);
-                xs[r] = acc;
-            }
-            xs[3] = floored_mod(xs[3], 360.0);
-            double dP[10];
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) dP[e] = Ps[e] - cur.Pb[e];
-            double KdP[4][4];
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) {
-                    double acc = cur.K[r][0] * dP[tix(0, c)];
-                    STE_UNROLL
-                    for (int i = 1; i < 4; ++i) acc = fma(cur.K[r][i], dP[tix(i, c)], acc);
-                    KdP[r][c] = acc;
-                }
-            }
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                STE_UNROLL
-                for (int c = r; c < 4; ++c) {
-                    double acc = KdP[r][0] * cur.K[c][0];
-                    STE_UNROLL
-                    for (int i = 1; i < 4; ++i) acc = fma(KdP[r][i], cur.K[c][i], acc);
-                    Ps[tix(r, c)] = cur.Pk[tix(r, c)] + acc;
-                }
-            }
-            store_vec(p.sm_mean, (size_t)k, B, t, xs);
-            store_cov_p(p.sm_cov, packed, (size_t)k, B, t, Ps);
-            store_pos(p, (size_t)k, B, t, xs);
-        }
-    }
-    double chk = 0.0;
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) chk += xs[c] * 0.0;
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) chk += Ps[e] * 0.0;
-    if (!(chk == 0.0)) atomicOr(&p.status[t], STE_STATUS_NAN);
-}
-
-// The lean recurrence with ONE DPP QUAD PER TRACK.  A block of a few tracks runs urtss_recur_lean at the pace at which one
-// wave issues its ~450 instructions per step (44 loads and 16-22 stores with their 64-bit address arithmetic, ~180 fp64
-// operations): 1.3 us per step on configs[3], and neither deeper prefetch nor a run-ahead wave warming L2 nor plain instead
-// of nontemporal stores moved it -- it is issue, not latency.  Here lane q of a quad owns row q: K[q][:], x[q], and the part
-// (q, c >= q) of the packed covariances; y and dP are broadcast through the quad, the K rows of the lanes to the right come
-// by quad rotation: ~60 fp64 operations, 52 DPP moves, 14 loads and <= 9 stores per lane and step.  Every element is
-// computed by exactly one lane with urtss_recur_lean's sequence of operations: same bits (tests/test_fleet.py).
-struct LeanRowQ {
-    double K[4], xb, xk, Pb[4], Pk[4];  // row q of K; element q of x_b and x_k; slot j = element (q, q + j) of P_b and P_k
-};
-__device__ __forceinline__ int pidx(int r, int c) { return r * 4 - (r * (r - 1)) / 2 + (c - r); }  // tix for r <= c at run time
-__device__ __forceinline__ void load_lean_row_q(const KParams& p, size_t k, size_t B, size_t t, int q, bool packed, LeanRowQ& g) {
-    const double* w = p.rts_work + (k * kWorkElems) * B + t;
-    g.K[0] = w[(size_t)(kLeanK01 + 2 * q + 0) * B];
-    g.K[1] = w[(size_t)(kLeanK01 + 2 * q + 1) * B];
-    g.K[2] = w[(size_t)(kLeanK23 + 2 * q + 0) * B];
-    g.K[3] = w[(size_t)(kLeanK23 + 2 * q + 1) * B];
-    g.xb = w[(size_t)(kWorkXb + q) * B];
-    g.xk = p.fwd_mean[(k * 4 + (size_t)q) * B + t];
-    STE_UNROLL
-    for (int j = 0; j < 4; ++j) {
-        const int c = min(q + j, 3);  // slots past the row's end repeat its last element and are never used
-        g.Pb[j] = w[(size_t)(kWorkPb + pidx(q, c)) * B];
-        g.Pk[j] = p.fwd_cov[(packed ? k * 10 + (size_t)pidx(q, c) : k * 16 + (size_t)(q * 4 + c)) * B + t];
-    }
-}
-// x[q], P(q, q + j) -> history row `row` (both triangles of the full layout: the lane that computed (r, c) also stores (c, r))
-__device__ __forceinline__ void store_lean_row_q(const KParams& p, size_t row, size_t B, size_t t, int q, bool packed, double x,
-                                                 const double (&P)[4]) {
-    st_stream(&p.sm_mean[(row * 4 + (size_t)q) * B + t], x);
-    if (p.sm_pos && q < 2) st_stream(&p.sm_pos[(row * 2 + (size_t)q) * B + t], x);
-    STE_UNROLL
-    for (int j = 0; j < 4; ++j) {
-        const int c = q + j;
-        if (c < 4) {
-            if (packed) {
-                st_stream(&p.sm_cov[(row * 10 + (size_t)pidx(q, c)) * B + t], P[j]);
-            } else {
-                st_stream(&p.sm_cov[(row * 16 + (size_t)(q * 4 + c)) * B + t], P[j]);
-                if (j) st_stream(&p.sm_cov[(row * 16 + (size_t)(c * 4 + q)) * B + t], P[j]);
-            }
-        }
-    }
-}
-// value held by lane (q + J) mod 4 of the quad
-template <int J>
-__device__ __forceinline__ double quad_rot(double v) {
-    static_assert(J >= 1 && J <= 3, "quad rotation");
-    return dpp_move<(J == 1) ? 0x39 : (J == 2) ? 0x4E : 0x93>(v);  // quad_perm [1,2,3,0] / [2,3,0,1] / [3,0,1,2]
-}
-
-__global__ __launch_bounds__(64) void urtss_recur_lean_q4(const KParams p) {
-    const size_t B = (size_t)p.ld;
-    const int q = threadIdx.x & 3;
-    const size_t t = (size_t)blockIdx.x * 16 + (threadIdx.x >> 2);
-    if (t >= (size_t)p.B) return;  // whole quads leave
-    const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    const int last_row = p.Nmax > 0 ? p.Nmax - 1 : 0;
-    if (q == 0) {
-        const double fb = p.first_bad[t];
-        if (fb >= 0.0) p.first_bad[t] = -fb - 1.0;  // the work rows of this track hold gains from here on (urtss_recur_lean)
-    }
-    double xs, Ps[4];  // x^s[q]; slot j = P^s(q, q + j)
-    xs = p.fwd_mean[((size_t)ns * 4 + (size_t)q) * B + t];
-    STE_UNROLL
-    for (int j = 0; j < 4; ++j) {
-        const int c = min(q + j, 3);
-        Ps[j] = p.fwd_cov[(packed ? (size_t)ns * 10 + (size_t)pidx(q, c) : (size_t)ns * 16 + (size_t)(q * 4 + c)) * B + t];
-    }
-    store_lean_row_q(p, (size_t)ns, B, t, q, packed, xs, Ps);
-    LeanRowQ nxt;
-    if (ns > 0) load_lean_row_q(p, (size_t)(ns - 1), B, t, q, packed, nxt);
-    for (int k = p.Nmax - 1; k >= 0; --k) {
-        if (!__any(k < ns)) continue;
-        if (k < ns) {
-            const LeanRowQ cur = nxt;
-            load_lean_row_q(p, (size_t)min(max(k - 1, 0), last_row), B, t, q, packed, nxt);  // in flight during this step
-            // y = x^s_{k+1} - x_b, the course difference wrapped (lane 3's element)
-            double yq = xs - cur.xb;
-            {
-                const double yw = wrap180(yq);
-                yq = (q == 3) ? yw : yq;
-            }
-            const double y0 = bcast<0>(yq), y1 = bcast<1>(yq), y2 = bcast<2>(yq), y3 = bcast<3>(yq);
-            double acc = cur.xk;
-            acc = fma(cur.K[0], y0, acc);
-            acc = fma(cur.K[1], y1, acc);
-            acc = fma(cur.K[2], y2, acc);
-            acc = fma(cur.K[3], y3, acc);
-            {
-                const double am = floored_mod(acc, 360.0);
-                xs = (q == 3) ? am : acc;
-            }
-            // dP = P^s_{k+1} - P_b on the owner of each element, then the whole symmetric matrix to every lane of the quad
-            double d[4];
-            STE_UNROLL
-            for (int j = 0; j < 4; ++j) d[j] = Ps[j] - cur.Pb[j];
-            double dP[10];
-            dP[tix(0, 0)] = bcast<0>(d[0]);
-            dP[tix(0, 1)] = bcast<0>(d[1]);
-            dP[tix(0, 2)] = bcast<0>(d[2]);
-            dP[tix(0, 3)] = bcast<0>(d[3]);
-            dP[tix(1, 1)] = bcast<1>(d[0]);
-            dP[tix(1, 2)] = bcast<1>(d[1]);
-            dP[tix(1, 3)] = bcast<1>(d[2]);
-            dP[tix(2, 2)] = bcast<2>(d[0]);
-            dP[tix(2, 3)] = bcast<2>(d[1]);
-            dP[tix(3, 3)] = bcast<3>(d[0]);
-            // row q of K dP
-            double KdP[4];
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                double a2 = cur.K[0] * dP[tix(0, c)];
-                STE_UNROLL
-                for (int i = 1; i < 4; ++i) a2 = fma(cur.K[i], dP[tix(i, c)], a2);
-                KdP[c] = a2;
-            }
-            // P^s(q, q + j) = P_k(q, q + j) + sum_i KdP[q][i] K[q + j][i]: the K row of the lane j places to the right
-            {
-                double a2 = KdP[0] * cur.K[0];
-                STE_UNROLL
-                for (int i = 1; i < 4; ++i) a2 = fma(KdP[i], cur.K[i], a2);
-                Ps[0] = cur.Pk[0] + a2;
-            }
-            {
-                const double k0 = quad_rot<1>(cur.K[0]), k1 = quad_rot<1>(cur.K[1]), k2 = quad_rot<1>(cur.K[2]), k3 = quad_rot<1>(cur.K[3]);
-                double a2 = KdP[0] * k0;
-                a2 = fma(KdP[1], k1, a2);
-                a2 = fma(KdP[2], k2, a2);
-                a2 = fma(KdP[3], k3, a2);
-                Ps[1] = cur.Pk[1] + a2;
-            }
-            {
-                const double k0 = quad_rot<2>(cur.K[0]), k1 = quad_rot<2>(cur.K[1]), k2 = quad_rot<2>(cur.K[2]), k3 = quad_rot<2>(cur.K[3]);
-                double a2 = KdP[0] * k0;
-                a2 = fma(KdP[1], k1, a2);
-                a2 = fma(KdP[2], k2, a2);
-                a2 = fma(KdP[3], k3, a2);
-                Ps[2] = cur.Pk[2] + a2;
-            }
-            {
-                const double k0 = quad_rot<3>(cur.K[0]), k1 = quad_rot<3>(cur.K[1]), k2 = quad_rot<3>(cur.K[2]), k3 = quad_rot<3>(cur.K[3]);
-                double a2 = KdP[0] * k0;
-                a2 = fma(KdP[1], k1, a2);
-                a2 = fma(KdP[2], k2, a2);
-                a2 = fma(KdP[3], k3, a2);
-                Ps[3] = cur.Pk[3] + a2;
-            }
-            store_lean_row_q(p, (size_t)k, B, t, q, packed, xs, Ps);
-        }
-    }
-    double chk = xs * 0.0;
-    STE_UNROLL
-    for (int j = 0; j < 4; ++j)
-        if (q + j < 4) chk += Ps[j] * 0.0;
-    if (!(chk == 0.0)) atomicOr(&p.status[t], STE_STATUS_NAN);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Posterior TRACKS from the smoother (ste_urtss_sample_f64): backward simulation with the smoother's own per-step
-// quantities.  The smoother gives marginals (sm_mean, sm_cov per row); a track drawn from the joint posterior ties
-// neighbouring rows together through the gains:
-//     row ns:  x_ns = m_ns + T_ns xi_ns,                         T_ns = symsqrt(P_ns)
-//     row k :  y = x_{k+1} - x_b,k (heading wrapped),  x_k = (m_k + K_k y) + T_k xi_k,   T_k = symsqrt(P_k - K_k P_b,k K_k^T)
-// with m, P the filtered rows, x_b, P_b, K = D pinv(P_b) exactly what smoother_step_gain forms (P_b about the filtered mean,
-// as the reference has it) and xi standard normal draws.  With xi = 0 this IS the smoother's mean recursion (same operation
-// order: same bits), and Cov(x_k) = C_k + K Cov(x_{k+1}) K^T is the smoother's covariance recursion, so the ensemble covariance
-// of the samples is sm_cov.  The root is the symmetric one of the sigma fan (sym_sqrt_p, cold start, negative eigenvalues
-// clamped), not a Cholesky factor: C_k is only semi-definite where Q has zero directions.
-//   urtss_sample_coef    a lane per (row, track), like urtss_gains_all: K (16) | x_b (4) | T packed (10) of every row into a
-//                        coefficient buffer of the caller's; reads the work rows in either form (D: smoother_step_gain; gains:
-//                        as load_lean_row) and writes none of the batch's arrays
-//   urtss_sample_recur   a lane per track and 1, 2 or 4 samples per lane (blockIdx.y walks the sample groups): the
-//                        recurrence, coefficient row and draws one row ahead in flight, draws consumed and samples written in
-//                        the same buffer
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kCoefK = 0, kCoefXb = 16, kCoefT = 20, kCoefElems = 30;  // include/ste.h: ste_ukf_sample_f64.coef
-constexpr int kMaxSamplesPerLane = 4;
-
-struct SampleParams {
-    double* samples;  // [S][Nmax+1][4][ld]
-    double* coef;     // [Nmax+1][kCoefElems][ld]
-    int32_t* status;  // [B] or nullptr
-    int nsamples;
-};
-
-// C = P_k - K P_b K^T, packed
-__device__ __forceinline__ void sample_cond_cov(const double (&Pk)[10], const double (&K)[4][4], const double (&Pb)[10],
-                                                double (&Cc)[10]) {
-#pragma clang fp contract(off)  // explicit fma() only: the same bits whichever form the work rows were in
-    double KPb[4][4];
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) {
-            double acc = K[r][0] * Pb[tix(0, c)];
-            STE_UNROLL
-            for (int i = 1; i < 4; ++i) acc = fma(K[r][i], Pb[tix(i, c)], acc);
-            KPb[r][c] = acc;
-        }
-    }
-    STE_UNROLL
-    for (int r = 0; r < 4; ++r) {
-        STE_UNROLL
-        for (int c = r; c < 4; ++c) {
-            double acc = KPb[r][0] * K[c][0];
-            STE_UNROLL
-            for (int i = 1; i < 4; ++i) acc = fma(KPb[r][i], K[c][i], acc);
-            Cc[tix(r, c)] = Pk[tix(r, c)] - acc;
-        }
-    }
-}
-
-template <bool kShift, bool kTrackNoise>
-__global__ __launch_bounds__(64) void urtss_sample_coef(const KParams p, const NoiseParams nz, const SampleParams sp) {
-    const size_t B = (size_t)p.ld;
-    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= (size_t)p.B * ((size_t)p.Nmax + 1)) return;
-    const size_t t = g % (size_t)p.B;
-    const int k = (int)(g / (size_t)p.B);
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
-    if (k > ns) return;
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
-    double* cw = sp.coef + ((size_t)k * kCoefElems) * B + t;
-    double Cc[10];
-    double chk = 0.0;
-    int st = 0;
-    if (k == ns) {
-        load_cov_p(p.fwd_cov, packed, (size_t)k, B, t, Cc);  // the last row is drawn from the filtered distribution itself
-    } else {
-        double K[4][4], xb[4], Pb[10], Pk[10];
-        const double fb_raw = p.first_bad[t];
-        if (fb_raw >= 0.0) {  // the work rows hold D: the gain as urtss_gains_all forms it
-            const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
-            const bool all_eig = (p.tuning & STE_TUNING_EIG_GAINS) != 0;
-            const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;
-            RecurRow cur;
-            load_recur_row<kShift>(p, (size_t)k, B, t, always_full, cur);
-            double xn[4], Pn[10], q4[4] = {0.0, 0.0, 0.0, 0.0};
-            load_vec(p.fwd_mean, (size_t)k + 1, B, t, xn);
-            load_cov_p(p.fwd_cov, packed, (size_t)k + 1, B, t, Pn);
-            const bool full = work_row_full(p, k, p.upd_idx[(size_t)k * B + t], always_full);
-            if constexpr (kTrackNoise) track_q4(p, nz, B, t, q4);
-            st |= smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, fb_raw, xb, Pb, K, q4);
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) Pk[e] = cur.Pk[e];
-        } else {  // the two-kernel smoother has been here: the rows hold K, x_b and P_b
-            LeanRow lr;
-            load_lean_row(p, (size_t)k, B, t, packed, lr);
-            STE_UNROLL
-            for (int r = 0; r < 4; ++r) {
-                xb[r] = lr.xb[r];
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) K[r][c] = lr.K[r][c];
-            }
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) {
-                Pb[e] = lr.Pb[e];
-                Pk[e] = lr.Pk[e];
-            }
-        }
-        sample_cond_cov(Pk, K, Pb, Cc);
-        STE_UNROLL
-        for (int r = 0; r < 4; ++r) {
-            STE_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                cw[(kCoefK + r * 4 + c) * B] = K[r][c];
-                chk += K[r][c] * 0.0;
-            }
-            cw[(kCoefXb + r) * B] = xb[r];
-            chk += xb[r] * 0.0;
-        }
-    }
-    double T[10], V[4][4];
-    st |= sym_sqrt_p(Cc, 1.0, T, V, false);
-    STE_UNROLL
-    for (int e = 0; e < 10; ++e) {
-        cw[(kCoefT + e) * B] = T[e];
-        chk += T[e] * 0.0;
-    }
-    if (!(chk == 0.0)) st |= STE_STATUS_NAN;
-    if (st && sp.status) atomicOr(&sp.status[t], st);
-}
-
-template <int kSpl>
-struct SampleRow {
-    double c[kCoefElems], m[4], xi[kSpl][4];
-};
-template <int kSpl>
-__device__ __forceinline__ void load_sample_row(const KParams& p, const SampleParams& sp, size_t k, size_t B, size_t t,
-                                                size_t s0, int nloc, SampleRow<kSpl>& g) {
-    const double* cw = sp.coef + (k * kCoefElems) * B + t;
-    STE_UNROLL
-    for (int e = 0; e < kCoefElems; ++e) g.c[e] = cw[(size_t)e * B];
-    load_vec(p.fwd_mean, k, B, t, g.m);
-    const size_t rows = (size_t)p.Nmax + 1;
-    STE_UNROLL
-    for (int j = 0; j < kSpl; ++j) {
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) g.xi[j][c] = j < nloc ? sp.samples[(((s0 + j) * rows + k) * 4 + c) * B + t] : 0.0;
-    }
-}
-
-// The recurrence.  A lane carries kSpl samples against ONE load of the row's 30 coefficients and its filtered mean: like
-// urtss_recur_lean the loop is bound by load and address issue, not by fp64 (per sample and row: 4 loads, 4 stores, ~45 fp64
-// operations), so the 34 shared loads are what sharing saves.  The operation order of m_k + K y is the smoother's (accumulator
-// starts at m_k, fma over the columns); T xi is formed on its own and added afterwards, so that zero draws give the smoother's
-// bits.  Rows past a track's last are neither read nor written.
-template <int kSpl>
-__global__ __launch_bounds__(64) void urtss_sample_recur(const KParams p, const SampleParams sp) {
-#pragma clang fp contract(off)  // explicit fma() only: a sample's bits do not depend on its slot in the lane
-    const size_t B = (size_t)p.ld;
-    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (size_t)p.B) return;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
-    const size_t s0 = (size_t)blockIdx.y * kSpl;
-    const int nloc = min(kSpl, sp.nsamples - (int)s0);
-    const size_t rows = (size_t)p.Nmax + 1;
-    double xs[kSpl][4];
-    STE_UNROLL
-    for (int j = 0; j < kSpl; ++j) {
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) xs[j][c] = 0.0;
-    }
-    SampleRow<kSpl> nxt;
-    load_sample_row<kSpl>(p, sp, (size_t)ns, B, t, s0, nloc, nxt);
-    for (int k = p.Nmax; k >= 0; --k) {
-        if (!__any(k <= ns)) continue;  // ragged batch: nobody in this wave has reached its last row yet
-        if (k <= ns) {
-            const SampleRow<kSpl> cur = nxt;
-            // the next row (its draws included, read before anything of this lane's is written): in flight during the arithmetic
-            load_sample_row<kSpl>(p, sp, (size_t)max(k - 1, 0), B, t, s0, nloc, nxt);
-            STE_UNROLL
-            for (int j = 0; j < kSpl; ++j) {
-                if (j < nloc) {
-                    double x[4];
-                    if (k < ns) {
-                        double y[4];
-                        STE_UNROLL
-                        for (int c = 0; c < 4; ++c) y[c] = xs[j][c] - cur.c[kCoefXb + c];
-                        y[3] = wrap180(y[3]);
-                        STE_UNROLL
-                        for (int r = 0; r < 4; ++r) {
-                            double acc = cur.m[r];
-                            STE_UNROLL
-                            for (int c = 0; c < 4; ++c) acc = fma(cur.c[kCoefK + r * 4 + c], y[c], acc);
-                            x[r] = acc;
-                        }
-                    } else {
-                        STE_UNROLL
-                        for (int r = 0; r < 4; ++r) x[r] = cur.m[r];
-                    }
-                    STE_UNROLL
-                    for (int r = 0; r < 4; ++r) {
-                        double e = cur.c[kCoefT + tix(r, 0)] * cur.xi[j][0];
-                        STE_UNROLL
-                        for (int c = 1; c < 4; ++c) e = fma(cur.c[kCoefT + tix(r, c)], cur.xi[j][c], e);
-                        x[r] += e;
-                    }
-                    x[3] = floored_mod(x[3], 360.0);
-                    STE_UNROLL
-                    for (int c = 0; c < 4; ++c) {
-                        st_stream(&sp.samples[(((s0 + j) * rows + (size_t)k) * 4 + c) * B + t], x[c]);
-                        xs[j][c] = x[c];
-                    }
-                }
-            }
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2157,6 +1292,14 @@ int ste::abi_check_hip(hipError_t e, const char* what) { return check_hip(e, wha
 
 namespace {
 
+// H selects lon / lat: H = diag(1, 1, 0, 0), what the closed-form update needs of it
+static bool selects_lon_lat(const double* H) {
+    bool sel = true;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) sel = sel && H[r * 4 + c] == ((r == c && r < 2) ? 1.0 : 0.0);
+    return sel;
+}
+
 int make_params(const ste_ukf_batch_f64* b, bool need_sm_out, ste::KParams* kp, bool need_hist = true) {
     if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
     if (b->n != 4) return fail(STE_EINVAL, "state dimension n must be 4 (heading index 3 is hard-wired, unscented.py:250)");
@@ -2191,12 +1334,10 @@ int make_params(const ste_ukf_batch_f64* b, bool need_sm_out, ste::KParams* kp, 
     if (!(fabs(b->w0 + 8.0 * b->wi - 1.0) <= 1e-14))
         return fail(STE_EINVAL, "sigma weights must sum to one: w0 + 2 n wi = 1 (unscented.py:125-132)");
     {
-        bool sel = true;
+        bool sel = selects_lon_lat(b->H);
         for (int r = 0; r < 4; ++r)
-            for (int c = 0; c < 4; ++c) {
-                sel = sel && b->H[r * 4 + c] == ((r == c && r < 2) ? 1.0 : 0.0);
+            for (int c = 0; c < 4; ++c)
                 if (r >= 2 || c >= 2) sel = sel && b->R[r * 4 + c] == 0.0;
-            }
         kp->fast_upd = sel && b->R[1] == b->R[4];
     }
     kp->nsteps = b->nsteps;
@@ -2269,18 +1410,12 @@ int slice_params(const ste_ukf_batch_f64* b, ste::KParams* kp) {
     return STE_OK;
 }
 
-// A run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{})
-template <class F>
-auto with_bool(bool v, F&& f) {
-    return v ? f(std::true_type{}) : f(std::false_type{});
-}
-
 // The instantiations of the lane-per-track forward kernels, in one place: kGains (the smoother's work rows) is free, and
 // (kFastUpd, kRobust) is (0, 0), (1, 0) or (1, 1) -- robust rescaling without the closed-form update runs the
 // <..., false, false> kernel, whose general update reads robust_iters itself.  `f` gets the three as std::bool_constants.
 template <class F>
 auto with_forward_variant(const ste::KParams& kp, F&& f) {
-    return with_bool(kp.rts_work != nullptr, [&](auto gains) {
+    return ste::with_bool(kp.rts_work != nullptr, [&](auto gains) {
         if (kp.fast_upd && kp.m.robust_iters > 0) return f(gains, std::true_type{}, std::true_type{});
         if (kp.fast_upd) return f(gains, std::true_type{}, std::false_type{});
         return f(gains, std::false_type{}, std::false_type{});
@@ -2322,48 +1457,14 @@ int launch_forward(const char* fn, const ste::KParams& kp, const ste::LikParams*
     return check_hip(hipGetLastError(), np ? "ukf_forward_tn launch" : lp ? "ukf_forward_lik launch" : "ukf_forward launch");
 }
 
-// Batches of at most this many tracks smooth with the two-kernel form (urtss_gains_all + urtss_recur_lean): up to there the
-// one-kernel smoother is a few waves running a latency chain of ~1.5-4.7 us per step, and the extra 440 B per track-step of
-// the gains pass cost less than the chain they remove; a batch that fills the chip is bound by bytes and issue instead.
-// STE_TUNING_TWO_KERNEL_SMOOTHER forces the two-kernel form, STE_TUNING_ONE_KERNEL_SMOOTHER the one-kernel form (tests,
-// measurements); the choice must not change between the backward calls made on one forward result (the first two-kernel call
-// turns the work rows into gains).
-constexpr int kLeanSmootherMaxTracks = 4096;
-bool lean_smoother(const ste::KParams& kp) {
-    return kp.rts_work && kp.Nmax > 0 && ((kp.tuning & STE_TUNING_TWO_KERNEL_SMOOTHER) || (!(kp.tuning & STE_TUNING_ONE_KERNEL_SMOOTHER) && kp.B <= kLeanSmootherMaxTracks));
-}
-
-// `np`: per-track noise, or NULL.  The smoother reads Q alone: without a per-track Q it takes the shared instantiations,
-// and the lean recurrences read no Q at all.
+// `np`: per-track noise, or NULL.  With the forward pass's work rows: the smoothers of ste_smooth.hip; without them the
+// stand-alone smoother, which reads Q alone and takes the shared instantiation without a per-track Q.
 int launch_backward(const ste::KParams& kp, const ste::NoiseParams* np, hipStream_t s) {
+    if (kp.rts_work) return ste::launch_backward_work(kp, np, s);
     const dim3 grid((unsigned)((kp.B + 63) / 64)), block(64);
-    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts, tn = np && np->Q;
+    const bool tn = np && np->Q;
     const ste::NoiseParams nz = tn ? *np : ste::NoiseParams{nullptr, nullptr};
-    auto with_shift_tn = [&](auto&& f) { with_bool(shift, [&](auto sh) { with_bool(tn, [&](auto t) { f(sh, t); }); }); };
-    if (lean_smoother(kp)) {
-        const dim3 ggrid((unsigned)(((size_t)kp.B * (size_t)kp.Nmax + 63) / 64));
-        with_shift_tn([&](auto sh, auto t) {
-            hipLaunchKernelGGL((ste::urtss_gains_all<decltype(sh)::value, decltype(t)::value>), ggrid, block, 0, s, kp, nz);
-        });
-        int rc = check_hip(hipGetLastError(), "urtss_gains_all launch");
-        if (rc) return rc;
-        // the recurrence: a quad per track (16 tracks per wave); STE_TUNING_LANE_RECURRENCE keeps the lane-per-track form
-        if (kp.tuning & STE_TUNING_LANE_RECURRENCE)
-            hipLaunchKernelGGL(ste::urtss_recur_lean, grid, block, 0, s, kp);
-        else
-            hipLaunchKernelGGL(ste::urtss_recur_lean_q4, dim3((unsigned)((kp.B + 15) / 16)), block, 0, s, kp);
-        return check_hip(hipGetLastError(), "urtss_recur_lean launch");
-    }
-    if (kp.rts_work) {
-        with_shift_tn([&](auto sh, auto t) {
-            if constexpr (decltype(t)::value)
-                hipLaunchKernelGGL(ste::urtss_recur_tn<decltype(sh)::value>, grid, block, 0, s, kp, nz);
-            else
-                hipLaunchKernelGGL(ste::urtss_recur_l1<decltype(sh)::value>, grid, block, 0, s, kp);
-        });
-        return check_hip(hipGetLastError(), "urtss_recur launch");
-    }
-    with_bool(tn, [&](auto t) { hipLaunchKernelGGL(ste::urtss_backward_l1<decltype(t)::value>, grid, block, 0, s, kp, nz); });
+    ste::with_bool(tn, [&](auto t) { hipLaunchKernelGGL(ste::urtss_backward_l1<decltype(t)::value>, grid, block, 0, s, kp, nz); });
     return check_hip(hipGetLastError(), "urtss_backward launch");
 }
 
@@ -2385,10 +1486,7 @@ int noise_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_noise
 void noise_route(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, ste::KParams* kp) {
     kp->flags |= STE_FLAG_LANES_1;
     if (!nz->R) return;  // shared R: make_params has looked at it
-    bool sel = true;
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) sel = sel && b->H[r * 4 + c] == ((r == c && r < 2) ? 1.0 : 0.0);
-    kp->fast_upd = sel && (nz->flags & STE_NOISE_R_BLOCK2) != 0;
+    kp->fast_upd = selects_lon_lat(b->H) && (nz->flags & STE_NOISE_R_BLOCK2) != 0;
 }
 
 // "whole passes only", for the entry point `fn`; `why`: what stands in the way of time slices, or where they go instead
@@ -2728,7 +1826,7 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
         const ste::KParams& kp = kps[w];
         // one kernel runs every window: the one-kernel smoother from the forward pass's work rows (what launch_backward picks
         // for a batch of more than kLeanSmootherMaxTracks tracks), with or without rates of its own
-        if (!kp.rts_work || lean_smoother(kp))
+        if (!kp.rts_work || ste::lean_smoother(kp))
             return fail(STE_EINVAL, "scheduled smoother: every window must take the one-kernel smoother (rts_work, more than 4096 tracks or tuning bit 10)");
         const int sh = (kp.sog_rate_rts || kp.cog_rate_rts) ? 1 : 0;
         if (shift >= 0 && sh != shift) return fail(STE_EINVAL, "scheduled smoother: the windows must agree on smoother rates (one kernel runs them all)");
@@ -2763,11 +1861,7 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
     sp.progress = sc->progress;
     sp.error = sc->error;
     sp.timeout_ticks = (unsigned long long)((sc->timeout_s > 0 ? sc->timeout_s : 2.0) * 1e8);
-    if (shift)
-        hipLaunchKernelGGL(ste::urtss_recur_sched<true>, dim3((unsigned)sc->nitems), dim3(64), 0, s, sp);
-    else
-        hipLaunchKernelGGL(ste::urtss_recur_sched<false>, dim3((unsigned)sc->nitems), dim3(64), 0, s, sp);
-    return check_hip(hipGetLastError(), "urtss_recur_sched launch");
+    return ste::launch_recur_sched(shift != 0, sc->nitems, sp, s);
 }
 
 int ste_urtss_backward_f64(const ste_ukf_batch_f64* b, void* stream) {
@@ -2839,24 +1933,7 @@ int ste_ukf_urtss_noise_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64*
 
 // ---- posterior track sampling (ste_ukf_sample_f64) ---------------------------------------------------------------------
 namespace {
-// Samples per lane of urtss_sample_recur.  Measured at 10 000 tracks x 500 steps ("Posterior tracks"; ms for 1 / 2 / 4
-// per lane): 16 samples 4.13 / 2.23 / 1.60 -- the 34 shared loads of a row are what a lane saves --, 8 samples 1.85 / 1.17 / 1.26,
-// 4 samples 0.98 / 0.88 / 1.17: sharing pays only while the launch still has the waves to hide its latency, and a lane that
-// carries more samples (248 registers at 4, 200 at 2) needs more of them: 628 waves are enough for 4 per lane, 314 are not but
-// are for 2.  So: 4 per lane from 512 waves on, else 2 from 256 on, else 1.  Same bits whichever is taken
-// (tests/test_track_sampling.py).  ste_dbg_sample_lanes forces one for a measurement (0 = this rule).
-constexpr size_t kSampleWavesPerSample = 128;
-int g_samples_per_lane = 0;
-int pick_samples_per_lane(int B, int nsamples) {
-    if (g_samples_per_lane) return g_samples_per_lane;
-    const size_t tiles = ((size_t)B + 63) / 64;
-    for (int spl = ste::kMaxSamplesPerLane; spl > 1; spl /= 2)
-        if (tiles * (((size_t)nsamples + spl - 1) / spl) >= kSampleWavesPerSample * spl) return spl;
-    return 1;
-}
-
-int sample_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_sample_f64* sm, ste::KParams* kp,
-                  ste::SampleParams* sp) {
+int sample_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_sample_f64* sm, ste::KParams* kp) {
     if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
     if (!sm) return fail(STE_EINVAL, "%s: the sampler arguments (sm) are NULL", fn);
     if (!sm->samples || !sm->coef) return fail(STE_EINVAL, "%s: sm->samples and sm->coef are required", fn);
@@ -2870,70 +1947,32 @@ int sample_params(const char* fn, const ste_ukf_batch_f64* b, const ste_ukf_samp
     rc = make_params(b, true, kp);
     if (rc) return rc;
     if (sm->nsamples > 65535) return fail(STE_EINVAL, "%s: sm->nsamples is limited to 65535 per call (one grid row per sample group)", fn);
-    *sp = {sm->samples, sm->coef, sm->status, sm->nsamples};
     return STE_OK;
 }
-
-int launch_sample_coef(const ste::KParams& kp, const ste_ukf_noise_f64* nz, const ste::SampleParams& sp, hipStream_t s) {
-    if (sp.status) {
-        int rc = check_hip(hipMemsetAsync(sp.status, 0, sizeof(int32_t) * (size_t)kp.B, s), "urtss_sample_coef status reset");
-        if (rc) return rc;
-    }
-    const bool shift = kp.sog_rate_rts || kp.cog_rate_rts, tn = nz && nz->Q;
-    const ste::NoiseParams np = tn ? ste::NoiseParams{nz->Q, nz->R} : ste::NoiseParams{nullptr, nullptr};
-    const dim3 grid((unsigned)(((size_t)kp.B * ((size_t)kp.Nmax + 1) + 63) / 64)), block(64);
-    with_bool(shift, [&](auto sh) {
-        with_bool(tn, [&](auto t) {
-            hipLaunchKernelGGL((ste::urtss_sample_coef<decltype(sh)::value, decltype(t)::value>), grid, block, 0, s, kp, np, sp);
-        });
-    });
-    return check_hip(hipGetLastError(), "urtss_sample_coef launch");
-}
-
-int launch_sample_recur(const ste::KParams& kp, const ste::SampleParams& sp, hipStream_t s) {
-    const int spl = pick_samples_per_lane(kp.B, sp.nsamples);
-    const dim3 grid((unsigned)((kp.B + 63) / 64), (unsigned)((sp.nsamples + spl - 1) / spl)), block(64);
-    switch (spl) {
-        case 1: hipLaunchKernelGGL(ste::urtss_sample_recur<1>, grid, block, 0, s, kp, sp); break;
-        case 2: hipLaunchKernelGGL(ste::urtss_sample_recur<2>, grid, block, 0, s, kp, sp); break;
-        default: hipLaunchKernelGGL(ste::urtss_sample_recur<4>, grid, block, 0, s, kp, sp); break;
-    }
-    return check_hip(hipGetLastError(), "urtss_sample_recur launch");
-}
 }  // namespace
-
-int ste_dbg_sample_lanes(int samples_per_lane) {  // developer instrumentation, not part of the ABI: 1, 2, 4 or 0 (by launch size); returns the old value
-    const int old = g_samples_per_lane;
-    if (samples_per_lane == 0 || samples_per_lane == 1 || samples_per_lane == 2 || samples_per_lane == 4)
-        g_samples_per_lane = samples_per_lane;
-    return old;
-}
 
 int ste_urtss_sample_prepare_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64* sm,
                                  void* stream) {
     ste::KParams kp;
-    ste::SampleParams sp;
-    int rc = sample_params("ste_urtss_sample_prepare_f64", b, sm, &kp, &sp);
+    int rc = sample_params("ste_urtss_sample_prepare_f64", b, sm, &kp);
     if (rc) return rc;
-    return launch_sample_coef(kp, nz, sp, (hipStream_t)stream);
+    return ste::launch_sample_coef(kp, nz, *sm, (hipStream_t)stream);
 }
 
 int ste_urtss_sample_draw_f64(const ste_ukf_batch_f64* b, const ste_ukf_sample_f64* sm, void* stream) {
     ste::KParams kp;
-    ste::SampleParams sp;
-    int rc = sample_params("ste_urtss_sample_draw_f64", b, sm, &kp, &sp);
+    int rc = sample_params("ste_urtss_sample_draw_f64", b, sm, &kp);
     if (rc) return rc;
-    return launch_sample_recur(kp, sp, (hipStream_t)stream);
+    return ste::launch_sample_recur(kp, *sm, (hipStream_t)stream);
 }
 
 int ste_urtss_sample_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64* sm, void* stream) {
     ste::KParams kp;
-    ste::SampleParams sp;
-    int rc = sample_params("ste_urtss_sample_f64", b, sm, &kp, &sp);
+    int rc = sample_params("ste_urtss_sample_f64", b, sm, &kp);
     if (rc) return rc;
-    rc = launch_sample_coef(kp, nz, sp, (hipStream_t)stream);
+    rc = ste::launch_sample_coef(kp, nz, *sm, (hipStream_t)stream);
     if (rc) return rc;
-    return launch_sample_recur(kp, sp, (hipStream_t)stream);
+    return ste::launch_sample_recur(kp, *sm, (hipStream_t)stream);
 }
 
 int ste_geodetic_dynamics_f64(int64_t count, const double* x, const double* dt, const double* sog_rate,

@@ -1,7 +1,8 @@
-// ste_ukf.h — what the translation units of the UKF / URTSS kernels (ste_kernels.hip, ste_forward_quad.hip) share: the kernel
-// arguments, the work-row layout, and the loads and stores of the SoA histories (track index fastest, so a wave's accesses
-// are contiguous runs).  Everything here is inlined into its callers: the library is built without relocatable device code,
-// each .hip is a code object of its own, and a kernel is instantiated in the one file that launches it.
+// ste_ukf.h — what the translation units of the UKF / URTSS kernels (ste_kernels.hip, ste_forward_quad.hip, ste_smooth.hip,
+// ste_sample.hip) share: the kernel arguments, the work-row layout, the bounded wait of the scheduled launches, and the loads
+// and stores of the SoA histories (track index fastest, so a wave's accesses are contiguous runs).  Everything here is
+// inlined into its callers: the library is built without relocatable device code, each .hip is a code object of its own,
+// and a kernel is instantiated in the one file that launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,31 @@ struct KParams {
     double* sm_pos;    // [Nmax+1][2][ld] smoothed lon / lat beside sm_mean, or nullptr
 };
 
+// kTrackNoise: per-track Q and R (ste_ukf_noise_f64), a further kernel argument of the *_tn entry kernels: upper triangles
+// [10][ld] in the order of STE_FLAG_PACKED_COV, track index fastest; nullptr = the shared matrix of KParams.  Q goes into
+// the ten Qv registers once per track (forward) or is read once per track before the backward loop (smoothers); R is
+// read at each update (lane_update / ukf_update).
+struct NoiseParams {
+    const double* Q;
+    const double* R;
+};
+
+// The scheduled smoother (ste_urtss_backward_sched_f64 builds the table in ste_kernels.hip, urtss_recur_sched of ste_smooth.hip
+// reads it): one item per (window, 64-track tile), and the kernel's arguments.
+struct SmoothItem {
+    int kp;    // index of the window's parameter block
+    int tile;  // 64-track tile of that window
+    int prog;  // index of the tile's progress counter (the forward launch's)
+    int need;  // slices of a forward pass of that window: the count the tile's counter reaches
+};
+struct SmoothSchedParams {
+    const KParams* kps;
+    const SmoothItem* items;
+    const int* progress;
+    int* error;  // 2 = a smoother wave waited longer than its bound
+    unsigned long long timeout_ticks;
+};
+
 // ste.h flags are 8 bits wide; this one is set by slice_params only: the launch continues a forward pass at step k0 > 0
 constexpr unsigned kFlagContinue = 0x10000u;
 
@@ -57,6 +83,19 @@ __device__ __forceinline__ int late_k0() {
     typedef const char __attribute__((address_space(4))) * kptr;
     kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
     return *(const volatile int __attribute__((address_space(4)))*)(ka + offsetof(KParams, k0));
+}
+
+// wave-uniform: spin (sleeping) until *flag >= need or the bound is reached
+__device__ __forceinline__ bool sched_wait(const int* flag, int need, unsigned long long timeout_ticks) {
+    if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+            if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) return false;
+            __builtin_amdgcn_s_sleep(64);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    return true;
 }
 
 constexpr int kColdEvery = 64;  // power of two
@@ -104,6 +143,13 @@ __device__ __forceinline__ void load_vec(const double* base, size_t row, size_t 
 __device__ __forceinline__ void store_vec(double* base, size_t row, size_t B, size_t t, const double (&v)[4]) {
     STE_UNROLL
     for (int c = 0; c < 4; ++c) st_stream(&base[(row * 4 + c) * B + t], v[c]);
+}
+
+__device__ __forceinline__ void store_pos(const KParams& p, size_t row, size_t B, size_t t, const double (&xs)[4]) {
+    if (p.sm_pos) {  // the tensor configs[2] exchanges between GPUs: smoothed lon / lat on their own (ste.h: sm_pos)
+        st_stream(&p.sm_pos[(row * 2 + 0) * B + t], xs[0]);
+        st_stream(&p.sm_pos[(row * 2 + 1) * B + t], xs[1]);
+    }
 }
 
 // Covariance histories (fwd_cov, sm_cov) come in two layouts: [row][16][B] full 4 x 4 matrices, the reference's return

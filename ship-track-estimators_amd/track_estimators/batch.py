@@ -1008,7 +1008,7 @@ def smoother_tile_order(items: np.ndarray, ntiles: Sequence[int]) -> np.ndarray:
     return np.ascontiguousarray(np.stack([win, idx - tile0[win]], axis=1).astype(np.int32))
 
 
-# What decides between the smoother's two forms (csrc/ste_kernels.hip: kLeanSmootherMaxTracks and the tuning bits that
+# What decides between the smoother's two forms (csrc/ste_smooth.hip: kLeanSmootherMaxTracks and the tuning bits that
 # lean_smoother() looks at; include/ste.h: STE_TUNING_*)
 LEAN_SMOOTHER_MAX_TRACKS = 4096  # up to this many tracks: two kernels (all gains, then a lean recurrence); one kernel above
 TUNING_TWO_KERNEL_SMOOTHER = binding.STE_TUNING_TWO_KERNEL_SMOOTHER  # ... two kernels whatever the batch size
@@ -1017,7 +1017,7 @@ TUNING_ONE_KERNEL_SMOOTHER = binding.STE_TUNING_ONE_KERNEL_SMOOTHER  # ... one k
 
 def _one_kernel_smoother(st) -> bool:
     """Does the batch struct ``st`` smooth from its work rows in one kernel?  Mirrors ``lean_smoother()`` in
-    csrc/ste_kernels.hip: true where that is false for a batch with work rows and steps."""
+    csrc/ste_smooth.hip: true where that is false for a batch with work rows and steps."""
     return bool(st.rts_work and st.Nmax > 0 and not (st.tuning & TUNING_TWO_KERNEL_SMOOTHER)
                 and ((st.tuning & TUNING_ONE_KERNEL_SMOOTHER) or st.B > LEAN_SMOOTHER_MAX_TRACKS))
 

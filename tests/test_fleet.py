@@ -240,7 +240,7 @@ def test_pipeline_orders_itself_behind_work_issued_outside_it():
 def test_two_kernel_smoother_is_the_one_kernel_smoother_bit_for_bit(kind):
     """Small batches smooth in two kernels -- x_b, P_b and the gain K = D pinv(P_b) of EVERY step at once (they depend on the
     forward pass alone, unscented.py:297-333), then a recurrence that only loads them -- because a few waves of the one-kernel
-    smoother are a latency chain (include/ste.h ``tuning`` bits 9 / 10, csrc/ste_kernels.hip launch_backward).  Same device
+    smoother are a latency chain (include/ste.h ``tuning`` bits 9 / 10, csrc/ste_smooth.hip launch_backward_work).  Same device
     functions, same bits: histories, sm_pos, status; and the call stays repeatable although the work rows hold gains
     afterwards."""
     import torch

@@ -350,6 +350,34 @@ def test_slices_that_change_waves_every_round_hand_over_bit_for_bit():
 
 
 @pytest.mark.gpu
+def test_tile_smoothers_with_smoother_rates_of_their_own_are_the_per_batch_smoother_bit_for_bit():
+    """The one-launch smoother of a sequence (ste_urtss_backward_sched_f64) for a window that smooths with rates of its own
+    (sog_rate_rts / cog_rate_rts: the kShift instantiation of urtss_recur_sched, which no other test launches).  130 ragged
+    tracks -- two full tiles and a partial one -- of up to 68 steps, so that every tile crosses a slice boundary; the
+    one-kernel smoother forced by its tuning bit.  Histories, smoothed histories, work rows and status are those of
+    DeviceBatch.run(), whose smoother is urtss_recur_l1<kShift> (tests/test_round3.py, tests/test_fleet.py)."""
+    import dataclasses
+
+    import torch
+
+    _, hb = _uniform(130, 620_000, nobs=18, substeps=4)
+    assert hb.Nmax == 68
+    nsteps = (hb.Nmax - (np.arange(hb.B) * 7) % 40).astype(np.int32)
+    hb = dataclasses.replace(hb, nsteps=nsteps, lanes=1, sog_rate_rts=hb.sog_rate * 1.25 + 0.01,
+                             cog_rate_rts=hb.cog_rate * 0.75 - 0.02)
+    ref = _clear(batch.DeviceBatch(hb, tuning=binding.STE_TUNING_ONE_KERNEL_SMOOTHER))
+    ref.run()
+    db = _clear(batch.DeviceBatch(hb, tuning=binding.STE_TUNING_ONE_KERNEL_SMOOTHER))
+    assert db.struct.sog_rate_rts and db.struct.cog_rate_rts
+    torch.cuda.synchronize()
+    with batch.SmootherPipeline(ntracks=130) as pipe:
+        pipe.submit_sequence([db], tile_smoothers=True)
+        assert pipe._sched_live[-1].smoother is not None  # one smoother launch, a wave per tile
+        pipe.synchronize()
+    assert bool(ref.sm_mean.abs().sum() > 0) and _same(ref, db)
+
+
+@pytest.mark.gpu
 def test_scheduled_launches_of_two_pipelines_become_resident_one_at_a_time():
     """Every wave of a scheduled launch may wait for any other, so two launches dispatched together could each hold part of
     the chip.  The launch counts its waves as they begin (``started``, include/ste.h) and the next scheduled launch of the

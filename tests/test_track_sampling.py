@@ -235,6 +235,43 @@ def test_zero_draws_reproduce_the_smoother():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("track_q", [False, True], ids=["shared-Q", "per-track-Q"])
+def test_zero_draws_reproduce_a_smoother_with_rates_of_its_own(track_q):
+    """The same with smoother rates that differ from the forward pass's (sog_rate_rts / cog_rate_rts: the kShift instantiations
+    of urtss_sample_coef, which the eight tracks' packing -- two sub-steps, shared rates -- never takes), with the shared Q and
+    with a Q per track: S = 2, B = 70, ragged, all draws zero.  Every sample is sm_mean on rows 0 .. ns, as values, from work
+    rows that hold D (after forward() alone, against the one-kernel smoother) and from rows that hold gains (after the
+    two-kernel smoother)."""
+    from track_estimators import batch, synthetic
+
+    Qs = None
+    if track_q:
+        _, Q, _, _ = synthetic.example_matrices()
+        Q2 = Q * 2.0
+        Q2[0, 2] = Q2[2, 0] = 1e-6
+        Q2[1, 3] = Q2[3, 1] = -2e-6
+        Qs = np.stack([Q, Q2, Q * 0.5, Q2] * 2)[tsc.B70_TRACKS]
+    hb = tsc.host_batch(tsc.B70_TRACKS, tsc.B70_NSTEPS, Qs=Qs, lanes=1)
+    hb = dataclasses.replace(hb, sog_rate_rts=hb.sog_rate * 1.25 + 0.01, cog_rate_rts=hb.cog_rate * 0.75 - 0.02)
+    draws = np.zeros((2, tsc.NMAX + 1, 4, 70))
+    for state, tuning in (("forward", 0x400), ("two-kernel", 0x200)):
+        db = batch.DeviceBatch(hb, tuning=tuning)
+        assert db.struct.sog_rate_rts and db.struct.cog_rate_rts and (db.noise is not None) == track_q
+        db.forward()
+        if state != "forward":
+            db.backward()
+        got, status = _sample(db, draws)
+        if state == "forward":
+            db.backward()
+        db.torch.cuda.synchronize()
+        sm = db.sm_mean.cpu().numpy()
+        assert not status.any() and not db.status.cpu().numpy().any(), state
+        for b, ns in enumerate(hb.nsteps):
+            for s in range(2):
+                assert np.array_equal(got[s, : ns + 1, :, b], sm[: ns + 1, :, b]), (state, b, s)
+
+
+@pytest.mark.gpu
 def test_recorded_draws_against_the_restatement():
     """S = 3 with host draws, the eight tracks plus a ragged copy of them: every component within MEAN_TOL of the restatement,
     relative to max(|ref|, smoothed standard deviation), heading through wrap180; sampler status 0; the batch's status,
