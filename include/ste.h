@@ -18,6 +18,8 @@
  *                            src/track_estimators/ship_track.py:197-338 (distance / heading: utils.py:9-147)
  *   ste_path_metrics_f64     distance sailed and line-crossing times of tracks that stay on the device (smoothed, filtered or
  *                            sampled): per-leg utils.haversine_formula / geographiclib_distance (utils.py:9-113), summed
+ *   ste_region_metrics_f64   time inside a polygon, first entry, entries, distance inside and per-row flags of such tracks (no
+ *                            counterpart in the reference: its callers would loop over a geometry library on a download)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -50,7 +52,8 @@ extern "C" {
                            ste_ukf_forward_loglik_f64).  Unnumbered addition: the posterior of the time derivative on the
                            GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).  Unnumbered addition: posterior tracks
                            sampled from the smoother (ste_urtss_sample_f64).  Unnumbered addition: path quantities of tracks on the
-                           device (ste_path_metrics_f64).
+                           device (ste_path_metrics_f64).  Unnumbered addition: tracks on the device against a polygon
+                           (ste_region_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -373,6 +376,65 @@ typedef struct ste_path_f64 {
 } ste_path_f64;               /* 64 bytes */
 
 int ste_path_metrics_f64(const ste_ukf_batch_f64* b, const ste_path_f64* pm, void* stream);
+
+/*
+ * REGIONS: tracks that stay on the device against a polygon (an unnumbered addition, like ste_path_f64): the time a track
+ * spends inside, when it first enters, how often it enters, the distance it sails inside and the inside flag of every row.
+ * `states` is that of ste_path_f64.  The geometry is PLANAR in (lon, lat) degrees -- what a GeoJSON or shapefile polygon means --
+ * and a position is linear in time inside a step, the convention of cross_time above.
+ *   - Polygon.  V vertices, px[0..V) then py[0..V); edge i joins vertex i and vertex (i + 1) mod V.  Preconditions the library
+ *     cannot check (the vertices are device memory; the Python front end checks them): the polygon is simple and
+ *     counter-clockwise (signed area > 0), every coordinate is finite, every px lies within lon_ref +- 90.  bbox is the min / max
+ *     of px and of py.
+ *   - Unwrapping.  Row k sits at x_k = lon_ref + wrap180(lon_k - lon_ref), y_k = lat_k, wrap180 that of ste_path_f64.  Step k
+ *     (k < nsteps[t]) runs from A = (x_k, y_k) to B = (x_k + delta, y_{k+1}), delta = wrap180(lon_{k+1} - lon_k).  Step k is
+ *     BROKEN when |delta| < 90 is false or either latitude is not finite; every other step is sound.  With |delta| < 90 and a
+ *     polygon within lon_ref +- 90 no periodic copy of the polygon can be met, so one copy is exact and stored longitudes may be
+ *     wrapped or unwrapped.
+ *   - Row inside.  A row whose (x, y) is not within bbox (closed comparisons, so NaN is outside) is outside.  Otherwise the
+ *     even-odd ray test: edge i, from P = vertex i to Q = vertex i + 1, toggles when (P.y > y) != (Q.y > y) and
+ *     x < P.x + (y - P.y) * (Q.x - P.x) / (Q.y - P.y).
+ *   - Step fraction f of a sound step, i0 the inside flag of row k.  If the step's bounding box and bbox are disjoint (strict
+ *     comparisons) f = i0 and there are no crossings.  Otherwise, for every edge in index order, with d = B - A, e = Q - P,
+ *     w = P - A:  den = d.x e.y - d.y e.x,  u = (w.x e.y - w.y e.x) / den,  v = (w.x d.y - w.y d.x) / den.  A CROSSING exists
+ *     when den != 0, 0 <= u < 1 and 0 <= v < 1; it is ENTERING when den < 0 and leaving otherwise.  Starting from i0, every
+ *     entering crossing adds 1 - u and every leaving one subtracts it, in edge order; f is the result clamped to [0, 1].  No
+ *     crossing is sorted.
+ *   - Outputs, with T_k = dt_0 + ... + dt_{k-1} summed in order.  time_inside = sum of dt_k f_k over the sound steps, in step
+ *     order.  dist_inside = sum of leg_k f_k over the sound steps with f_k > 0, in step order, leg_k the leg of
+ *     ste_path_metrics_f64 for `model`.  ENTERING EVENTS are: row 0 inside, at time 0; every entering crossing of a sound step,
+ *     at T_k + dt_k u; for a broken step, row k + 1 inside while row k is not, at T_{k+1}.  nenter counts them; first_entry is
+ *     the earliest (within a step: T_k + dt_k times the smallest u), NaN when there is none.  nbroken counts the broken steps;
+ *     a broken step adds nothing to time_inside or dist_inside.  inside holds the flags of rows 0 .. nsteps[t].  A track with
+ *     nsteps == 0 gives 0, (0 or NaN), (1 or 0), 0, 0.
+ *   - Every value's bits depend on that track's rows and the polygon alone: not on S, the window, track_stride, or which
+ *     outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64 (inside: inside[(s * (Nmax + 1) + row) * track_stride
+ *     + t], one byte each).  Rows past nsteps[t] of states are not read.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or rg NULL; states or vert NULL; nstates < 1
+ *     or > 65535; nvert < 3 or > STE_REGION_MAX_VERT; reserved != 0; a non-finite lon_ref; dist_inside with an unknown model;
+ *     b->dt NULL when time_inside or first_entry is asked for; every output NULL; B <= 0, Nmax < 0, or track_stride non-zero
+ *     and below B.
+ */
+#define STE_REGION_MAX_VERT 1024
+typedef struct ste_region_f64 {
+    int32_t nstates;        /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;          /* STE_PREP_SPHERE / STE_PREP_WGS84: leg function for dist_inside; read only when dist_inside != NULL */
+    const double* states;   /* DEVICE [S][Nmax+1][4][track_stride]; components 0 (lon) and 1 (lat) are read */
+    int32_t nvert;          /* V, 3 <= V <= STE_REGION_MAX_VERT (1024) */
+    int32_t reserved;       /* must be 0 */
+    const double* vert;     /* DEVICE [2][V]: px[0..V), py[0..V) in degrees, shared by all tracks of the call */
+    double lon_ref;         /* HOST value: the meridian the longitudes are unwrapped about (above) */
+    double* time_inside;    /* DEVICE [S][track_stride] out or NULL: hours */
+    double* first_entry;    /* DEVICE [S][track_stride] out or NULL: hours from row 0, NaN = never inside */
+    int32_t* nenter;        /* DEVICE [S][track_stride] out or NULL */
+    int32_t* nbroken;       /* DEVICE [S][track_stride] out or NULL */
+    double* dist_inside;    /* DEVICE [S][track_stride] out or NULL: km sailed inside */
+    uint8_t* inside;        /* DEVICE [S][Nmax+1][track_stride] out or NULL: 1 = row inside; rows past nsteps[t] untouched */
+} ste_region_f64;           /* 88 bytes */
+
+int ste_region_metrics_f64(const ste_ukf_batch_f64* b, const ste_region_f64* rg, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -141,6 +141,29 @@ class StePathF64(C.Structure):
     ]
 
 
+STE_REGION_MAX_VERT = 1024
+
+
+class SteRegionF64(C.Structure):
+    """Mirror of ``struct ste_region_f64`` (include/ste.h): tracks on the device against a polygon."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("nvert", C.c_int32),
+        ("reserved", C.c_int32),
+        ("vert", _dp),
+        ("lon_ref", C.c_double),
+        ("time_inside", _dp),
+        ("first_entry", _dp),
+        ("nenter", _dp),
+        ("nbroken", _dp),
+        ("dist_inside", _dp),
+        ("inside", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -249,6 +272,7 @@ SYMBOLS = {
     "ste_urtss_sample_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteUkfSampleF64),
                                        C.c_void_p]),
     "ste_path_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePathF64), C.c_void_p]),
+    "ste_region_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRegionF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -854,6 +854,85 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- regions --------------------------------------------------------------------------------------------------
+    def region_metrics(self, states, polygon, model: str = "sphere", distance: bool = False, mask: bool = False, stream=None):
+        """Tracks that are on the device against a polygon (include/ste.h: ste_region_metrics_f64; DESIGN.md, "Regions"):
+        time inside, first entry, entries.  ``states`` as in ``path_metrics``.  ``polygon``: a (V, 2) array of lon / lat in
+        degrees, planar as in GeoJSON, or what ``region_polygon`` made of one; a repeated closing vertex is dropped, a
+        clockwise ring reversed and the longitudes unwrapped (``region_polygon`` has the rules and the refusals).  Returns a
+        dict of device tensors: ``time_inside`` (S, B) in hours; ``first_entry`` (S, B), hours from row 0 to the first entry,
+        0 for a track that starts inside, NaN for one that never is inside; ``nenter`` (S, B) int32, the number of entries;
+        ``nbroken`` (S, B) int32, the steps left out because they have a NaN latitude or span 90 degrees of longitude or more;
+        with ``distance`` also ``dist_inside`` (S, B), km sailed inside under ``model`` ("sphere" or "wgs84", the legs of
+        ``path_metrics``); with ``mask`` also ``inside`` (S, Nmax+1, B) uint8, 1 where the row is inside, 0 past ``nsteps[b]``.
+        Windows, in-place views and ``stream`` as in ``path_metrics``; every value depends on its own track's rows and the
+        polygon alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        poly = polygon if isinstance(polygon, RegionPolygon) else region_polygon(polygon)
+        S, V = int(states.shape[0]), int(poly.vert.shape[1])
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            vert = torch.from_numpy(poly.vert).to(self.device)
+            keep = [states, vert]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            tin, first = torch.empty((S, width), **f64), torch.empty((S, width), **f64)
+            nent, nbrk = torch.empty((S, width), **i32), torch.empty((S, width), **i32)
+            din = torch.empty((S, width), **f64) if distance else None
+            flags = torch.zeros((S, N + 1, width), dtype=torch.uint8, device=self.device) if mask else None
+            rg = binding.SteRegionF64()
+            rg.nstates, rg.model, rg.states = S, self._PATH_MODELS[model], states.data_ptr()
+            rg.nvert, rg.reserved, rg.vert, rg.lon_ref = V, 0, vert.data_ptr(), float(poly.lon_ref)
+            rg.time_inside, rg.first_entry = tin.data_ptr() + 8 * col, first.data_ptr() + 8 * col
+            rg.nenter, rg.nbroken = nent.data_ptr() + 4 * col, nbrk.data_ptr() + 4 * col
+            rg.dist_inside = None if din is None else din.data_ptr() + 8 * col
+            rg.inside = None if flags is None else flags.data_ptr() + col
+            binding.check(self.lib.ste_region_metrics_f64(C.byref(s), C.byref(rg), self._stream(st)), "ste_region_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            out = {"time_inside": tin[:, col:col + B], "first_entry": first[:, col:col + B], "nenter": nent[:, col:col + B],
+                   "nbroken": nbrk[:, col:col + B]}
+            if din is not None:
+                out["dist_inside"] = din[:, col:col + B]
+            if flags is not None:
+                out["inside"] = flags[..., col:col + B]
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -1916,6 +1995,117 @@ def path_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, mod
         with warnings.catch_warnings():  # a track that no sample takes across the line: all-NaN column, NaN quantiles
             warnings.simplefilter("ignore", RuntimeWarning)
             out["cross_time_quantiles"] = np.nanquantile(ct, q, axis=0)
+    out["status"] = status.cpu().numpy()
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class RegionPolygon:
+    """A polygon as ``ste_region_metrics_f64`` wants it (``region_polygon`` makes one): ``vert`` (2, V) float64, px then py,
+    counter-clockwise, longitudes unwrapped and within ``lon_ref`` +- 90."""
+
+    vert: np.ndarray
+    lon_ref: float
+
+
+def region_polygon(polygon) -> RegionPolygon:
+    """Normalise a (V, 2) array of lon / lat degrees (a GeoJSON ring; planar in lon / lat) for ``region_metrics``.  The
+    longitudes are unwrapped about the first vertex (lon_0 + wrap180(lon_i - lon_0)), so a ring may straddle the antimeridian
+    stored either way; a repeated closing vertex is dropped; a clockwise ring is reversed; ``lon_ref`` is the midpoint of the
+    unwrapped longitude range.  ``ValueError``: not (V, 2); a non-finite coordinate; V outside [3, 1024] after the closing
+    vertex is dropped; a longitude extent above 180 degrees; zero area.  That the ring is simple is not checked."""
+    p = np.asarray(polygon, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"polygon must be a (V, 2) array of lon / lat degrees, got shape {p.shape}")
+    if not np.isfinite(p).all():
+        raise ValueError("polygon has a non-finite coordinate")
+    V = p.shape[0]
+    lon, lat = p[:, 0], p[:, 1]
+    if V:
+        lon = lon[0] + ((lon - lon[0] + 180.0) % 360.0 - 180.0)
+    if V > 1 and lon[0] == lon[-1] and lat[0] == lat[-1]:
+        lon, lat, V = lon[:-1], lat[:-1], V - 1
+    if V < 3 or V > binding.STE_REGION_MAX_VERT:
+        raise ValueError(f"polygon must have between 3 and {binding.STE_REGION_MAX_VERT} vertices (a repeated closing vertex "
+                         f"not counted), got {V}")
+    lo, hi = float(lon.min()), float(lon.max())
+    if hi - lo > 180.0:
+        raise ValueError(f"polygon spans {hi - lo:.6g} degrees of longitude; at most 180 are supported")
+    area2 = float(np.sum(lon * np.roll(lat, -1) - np.roll(lon, -1) * lat))
+    if area2 == 0.0:
+        raise ValueError("polygon has zero area")
+    if area2 < 0.0:
+        lon, lat = lon[::-1], lat[::-1]
+    return RegionPolygon(vert=np.ascontiguousarray(np.stack([lon, lat])), lon_ref=0.5 * (lo + hi))
+
+
+def region_statistics(hb_or_db, polygon, nsamples: int, seed: int = 0, chunk: int = 16, model: str = "sphere",
+                      distance: bool = False, quantiles=(0.05, 0.5, 0.95), device="cuda:0"):
+    """Time in a polygon, entry and occupancy with the uncertainty of the smoothing posterior, per track: ``nsamples`` posterior
+    tracks are drawn (``DeviceBatch.sample_smoothed``), reduced (``DeviceBatch.region_metrics``) and discarded, ``chunk``
+    samples at a time, with the generator discipline of ``path_statistics``: one draw buffer refilled from one generator, so
+    the draws depend on ``(seed, chunk)`` and with ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.
+    Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother first; a ``DeviceBatch`` (or a window of one)
+    is taken to hold a completed ``run()``.  ``polygon``, ``model`` and ``distance`` as in ``region_metrics``.
+
+    Returns a dict of NumPy arrays in the batch's slot order: ``time_inside_smoothed`` (B,) and ``inside_smoothed``
+    (Nmax+1, B) bool, of the smoothed track ``sm_mean``; ``time_inside`` (nsamples, B) with ``time_inside_mean``,
+    ``time_inside_std`` (ddof = 1, 0 for a single sample) and ``time_inside_quantiles`` (len(quantiles), B); ``nenter``
+    (nsamples, B); ``entry_prob`` (B,), the fraction of samples that are inside at some time; ``first_entry`` (nsamples, B), NaN
+    where a sample never is, and ``first_entry_quantiles`` over the samples that enter, NaN where none does; ``occupancy``
+    (Nmax+1, B), the fraction of samples inside at each row, summed on the device chunk by chunk from the masks, NaN past
+    ``nsteps``; with ``distance`` also ``dist_inside_smoothed`` (B,) and ``dist_inside`` (nsamples, B); and ``status`` (B,),
+    the sampler's STE_STATUS_* bits."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    poly = polygon if isinstance(polygon, RegionPolygon) else region_polygon(polygon)
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("region_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    kw = dict(model=model, distance=distance, mask=True)
+    smoothed = db.region_metrics(db.sm_mean, poly, **kw)
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    f64 = dict(dtype=torch.float64, device=db.device)
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    tin, first = torch.empty((nsamples, B), **f64), torch.empty((nsamples, B), **f64)
+    nent = torch.empty((nsamples, B), dtype=torch.int32, device=db.device)
+    din = torch.empty((nsamples, B), **f64) if distance else None
+    count = torch.zeros((N + 1, B), dtype=torch.int32, device=db.device)
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        draws = buf[:n]
+        draws.normal_(generator=gen)
+        m = db.region_metrics(db.sample_smoothed(n, draws=draws), poly, **kw)
+        tin[i:i + n], first[i:i + n], nent[i:i + n] = m["time_inside"], m["first_entry"], m["nenter"]
+        if din is not None:
+            din[i:i + n] = m["dist_inside"]
+        count += m["inside"].sum(dim=0, dtype=torch.int32)
+        status |= db.sample_status
+    q = np.asarray(quantiles, dtype=np.float64)
+    t, fe, ne = tin.cpu().numpy(), first.cpu().numpy(), nent.cpu().numpy()
+    nsteps = db.t["nsteps"][db.lo:db.lo + B].cpu().numpy()
+    live = np.arange(N + 1)[:, None] <= nsteps[None, :]
+    out = {"time_inside_smoothed": smoothed["time_inside"][0].cpu().numpy(),
+           "inside_smoothed": smoothed["inside"][0].cpu().numpy().astype(bool),
+           "time_inside": t, "time_inside_mean": t.mean(axis=0), "time_inside_std": t.std(axis=0, ddof=1 if nsamples > 1 else 0),
+           "time_inside_quantiles": np.quantile(t, q, axis=0), "nenter": ne, "entry_prob": (ne > 0).mean(axis=0),
+           "first_entry": fe, "occupancy": np.where(live, count.cpu().numpy() / float(nsamples), np.nan)}
+    with warnings.catch_warnings():  # a track that no sample takes into the region: all-NaN column, NaN quantiles
+        warnings.simplefilter("ignore", RuntimeWarning)
+        out["first_entry_quantiles"] = np.nanquantile(fe, q, axis=0)
+    if din is not None:
+        out["dist_inside_smoothed"], out["dist_inside"] = smoothed["dist_inside"][0].cpu().numpy(), din.cpu().numpy()
     out["status"] = status.cpu().numpy()
     return out
 

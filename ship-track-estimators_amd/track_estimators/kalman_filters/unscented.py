@@ -315,6 +315,34 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return out["distance"][:, 0]
 
+    def time_in_region(self, polygon, n_samples: int = 0, random_state: int = 0):
+        """Hours the track ``run`` filtered spends inside ``polygon``, a (V, 2) array of lon / lat degrees, planar as in
+        GeoJSON (``track_estimators.batch.region_statistics``; no counterpart in the reference).  ``n_samples == 0``: the time
+        of the smoothed track, a float.  Otherwise an ``(n_samples,)`` array: the times of that many tracks drawn from the
+        joint smoothing posterior, those of ``sample_smoothed(n_samples, random_state)``.  The track is packed as ``run``
+        packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("time_in_region() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("time_in_region() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        poly = _batch.region_polygon(polygon)
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            return float(db.region_metrics(db.sm_mean, poly)["time_inside"][0, 0].item())
+        out = _batch.region_statistics(hb, poly, n_samples, seed=int(random_state), chunk=n_samples)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return out["time_inside"][:, 0]
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
