@@ -20,6 +20,8 @@
  *                            sampled): per-leg utils.haversine_formula / geographiclib_distance (utils.py:9-113), summed
  *   ste_region_metrics_f64   time inside a polygon, first entry, entries, distance inside and per-row flags of such tracks (no
  *                            counterpart in the reference: its callers would loop over a geometry library on a download)
+ *   ste_grid_metrics_f64     ship-hours per cell of a regular lon / lat grid, summed over such tracks in exact integer ticks,
+ *                            and entries per cell (no counterpart in the reference: a download and a host loop)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -53,7 +55,8 @@ extern "C" {
                            GP path (ste_gp_predict_deriv_f64, ste_gp_predict_deriv_cov_f64).  Unnumbered addition: posterior tracks
                            sampled from the smoother (ste_urtss_sample_f64).  Unnumbered addition: path quantities of tracks on the
                            device (ste_path_metrics_f64).  Unnumbered addition: tracks on the device against a polygon
-                           (ste_region_metrics_f64).
+                           (ste_region_metrics_f64).  Unnumbered addition: tracks on the device on a lon / lat grid
+                           (ste_grid_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -435,6 +438,64 @@ typedef struct ste_region_f64 {
 } ste_region_f64;           /* 88 bytes */
 
 int ste_region_metrics_f64(const ste_ukf_batch_f64* b, const ste_region_f64* rg, void* stream);
+
+/*
+ * GRIDS: tracks that stay on the device on a regular lon / lat grid (an unnumbered addition, like ste_region_f64): the time
+ * spent in every cell, SUMMED OVER THE TRACKS of the call, and how often a cell is entered.  `states` is that of ste_path_f64.
+ * The geometry is PLANAR in (lon, lat) degrees and a position is linear in time inside a step, as for ste_region_f64.
+ *   - Ticks.  Time is counted in integer ticks of 1 / STE_GRID_TICKS_PER_HOUR hours (2^-20 h = 3.4 ms).  Integer sums are exact
+ *     and do not depend on the order of the additions, so the grid's bits do not depend on S, windows, sample chunks or launch
+ *     order, which no floating-point sum over tracks could offer.  `ticks` and `entries` are ACCUMULATED (+=) with atomic
+ *     adds: the caller zeroes them, and the grid after two calls is the sum of the grids of each.
+ *   - Grid.  Cell (ix, iy), 0 <= ix < nx, 0 <= iy < ny, is [lon0 + ix dlon, lon0 + (ix + 1) dlon) x [lat0 + iy dlat,
+ *     lat0 + (iy + 1) dlat), stored at [iy * nx + ix].  A position's grid coordinates are gx = (x - lon0) / dlon and
+ *     gy = (lat - lat0) / dlat, and it lies in cell (floor gx, floor gy).  Without STE_GRID_PERIODIC_LON the grid must lie
+ *     within lon_ref +- 90 (so it is at most 180 degrees wide and one copy of it is exact, by the argument of ste_region_f64);
+ *     everything off the grid is one OUTSIDE cell.  With STE_GRID_PERIODIC_LON the grid is exactly 360 degrees wide
+ *     ((double)nx * dlon == 360), the column is floor gx modulo nx (floored), and lon0 must lie within lon_ref +- 360.
+ *   - Unwrapping.  Row k sits at x_k = lon_ref + wrap180(lon_k - lon_ref), wrap180 that of ste_path_f64.  Step k (k <
+ *     nsteps[t]) runs from A = (x_k, lat_k) to B = (x_k + delta, lat_{k+1}), delta = wrap180(lon_{k+1} - lon_k).  Step k is
+ *     SOUND when |delta| < 90, both latitudes are finite, dt_k >= 0 and dt_k * 2^20 < 2^52; every other step is BROKEN: it is
+ *     counted in nbroken and adds no time anywhere.
+ *   - Pieces.  A sound step has dtq = rint(dt_k * 2^20) ticks (rint: to nearest, ties to even).  It is split at the grid lines
+ *     strictly between its ends: the x-lines i with parameter u = (i - gxA) / (gxB - gxA) and the y-lines j with
+ *     u = (j - gyA) / (gyB - gyA), each u clamped to [0, 1], each set in the order met and the two merged by u, ties to x.  Without the
+ *     periodic flag only the grid's own lines 0 .. nx (and always 0 .. ny) are taken: that is the clipping.  The line at u has
+ *     the tick tq = max(rint(u * dtq), the previous line's tick); a piece is the difference of the ticks of its two ends (0 at
+ *     the start, dtq at the end), so the pieces of a step sum to dtq exactly.  The first piece lies in the cell of A (indices
+ *     clamped to -1 .. n, the outside, where not periodic); crossing x-line i eastwards leads to column i, westwards to i - 1,
+ *     and likewise for rows.  A piece of 0 ticks is dropped.
+ *   - Runs.  A track's RUN is a maximal stretch of consecutive pieces in one cell (or outside), across steps and across
+ *     broken steps.  Each run adds its ticks to ticks[cell] once and 1 to entries[cell]; outside runs add to outside[s][t].
+ *     total[s][t] is the sum of dtq over the sound steps.  EXACTLY: the track's ticks on the grid + outside = total.
+ *     A track with nsteps == 0 adds nothing and gives 0, 0, 0.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_region_metrics_f64.  Rows past nsteps[t] of states are not read.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or g NULL; states NULL; nstates < 1 or
+ *     > 65535; unknown flag bits; nx or ny < 1 or nx * ny > STE_GRID_MAX_CELLS; a non-finite lon0, lat0 or lon_ref; dlon or
+ *     dlat not finite or < 1e-6; STE_GRID_PERIODIC_LON with (double)nx * dlon != 360 or with lon0 outside lon_ref +- 360;
+ *     without the flag a grid that is not within lon_ref +- 90 (lon0 - lon_ref >= -90 and (lon0 + nx * dlon) - lon_ref <= 90);
+ *     b->dt NULL; every output NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B.
+ */
+#define STE_GRID_TICKS_PER_HOUR 1048576   /* 2^20: one tick = 3.4 ms */
+#define STE_GRID_MAX_CELLS (1 << 26)
+#define STE_GRID_PERIODIC_LON 0x1u        /* nx * dlon == 360 exactly: columns wrap */
+typedef struct ste_grid_f64 {
+    int32_t nstates;       /* S >= 1 tracks per ship in `states` (<= 65535) */
+    uint32_t flags;        /* STE_GRID_* ; unknown bits refused */
+    const double* states;  /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 / ste_region_f64 */
+    int32_t nx, ny;        /* columns (lon) and rows (lat), >= 1, nx * ny <= STE_GRID_MAX_CELLS */
+    double lon0, lat0;     /* HOST: west and south edge of cell (0, 0), degrees */
+    double dlon, dlat;     /* HOST: cell size, finite, >= 1e-6 */
+    double lon_ref;        /* HOST: meridian the longitudes are unwrapped about */
+    int64_t* ticks;        /* DEVICE [ny][nx], ACCUMULATED (+=): the caller zeroes it; or NULL */
+    int64_t* entries;      /* DEVICE [ny][nx], accumulated: runs of a track in the cell; or NULL */
+    int64_t* outside;      /* DEVICE [S][track_stride] out or NULL: ticks of sound steps spent off the grid */
+    int64_t* total;        /* DEVICE [S][track_stride] out or NULL: ticks of all sound steps */
+    int32_t* nbroken;      /* DEVICE [S][track_stride] out or NULL */
+} ste_grid_f64;            /* 104 bytes */
+
+int ste_grid_metrics_f64(const ste_ukf_batch_f64* b, const ste_grid_f64* g, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -164,6 +164,33 @@ class SteRegionF64(C.Structure):
     ]
 
 
+STE_GRID_TICKS_PER_HOUR = 1048576
+STE_GRID_MAX_CELLS = 1 << 26
+STE_GRID_PERIODIC_LON = 0x1
+
+
+class SteGridF64(C.Structure):
+    """Mirror of ``struct ste_grid_f64`` (include/ste.h): tracks on the device on a regular lon / lat grid."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("flags", C.c_uint32),
+        ("states", _dp),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("lon0", C.c_double),
+        ("lat0", C.c_double),
+        ("dlon", C.c_double),
+        ("dlat", C.c_double),
+        ("lon_ref", C.c_double),
+        ("ticks", _dp),
+        ("entries", _dp),
+        ("outside", _dp),
+        ("total", _dp),
+        ("nbroken", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -273,6 +300,7 @@ SYMBOLS = {
                                        C.c_void_p]),
     "ste_path_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePathF64), C.c_void_p]),
     "ste_region_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRegionF64), C.c_void_p]),
+    "ste_grid_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteGridF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -933,6 +933,86 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- grids ----------------------------------------------------------------------------------------------------
+    def grid_metrics(self, states, grid, entries: bool = False, out=None, stream=None):
+        """Tracks that are on the device on a regular lon / lat grid (include/ste.h: ste_grid_metrics_f64; DESIGN.md, "Grids"):
+        the time spent in every cell, summed over all tracks of the call, in exact integer ticks of 2^-20 h.  ``states`` as in
+        ``path_metrics``; ``grid`` a ``TrackGrid`` (``track_grid`` makes one).  Returns a dict of device tensors: ``ticks``
+        (ny, nx) int64; ``hours`` = ticks / 2^20 as float64; with ``entries`` also ``entries`` (ny, nx) int64, the number of
+        runs of a track in the cell; ``outside`` and ``total`` (S, B) int64, the ticks of a track's sound steps spent off the
+        grid and altogether; ``nbroken`` (S, B) int32, the steps left out (a non-finite latitude, 90 degrees of longitude or
+        more in one step, a negative or non-finite dt).  ``out``: a previous result whose ``ticks`` (and ``entries``) this call
+        adds to, so that windows and sample chunks sum into one grid; otherwise fresh zeroed tensors.  The sums are integers:
+        the grid's bits do not depend on how the tracks were split into calls.  Windows, in-place views and ``stream`` as in
+        ``path_metrics``."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if not isinstance(grid, TrackGrid):
+            raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
+        S, nx, ny = int(states.shape[0]), grid.nx, grid.ny
+        i64 = dict(dtype=torch.int64, device=self.device)
+        if out is not None:
+            ticks, ent = out.get("ticks"), out.get("entries")
+            for name, ten in (("ticks", ticks),) + ((("entries", ent),) if entries else ()):
+                if (not isinstance(ten, torch.Tensor) or ten.dtype != torch.int64 or ten.device != self.device
+                        or tuple(ten.shape) != (ny, nx) or not ten.is_contiguous()):
+                    raise ValueError(f"out[{name!r}] must be a contiguous int64 tensor of shape ({ny}, {nx}) on {self.device}")
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        with torch.cuda.stream(st):
+            if out is None:
+                ticks = torch.zeros((ny, nx), **i64)
+                ent = torch.zeros((ny, nx), **i64) if entries else None
+            elif not entries:
+                ent = None
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, ticks] + ([ent] if ent is not None else [])
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            outside, total = torch.zeros((S, width), **i64), torch.zeros((S, width), **i64)
+            nbrk = torch.zeros((S, width), dtype=torch.int32, device=self.device)
+            g = binding.SteGridF64()
+            g.nstates, g.flags, g.states = S, binding.STE_GRID_PERIODIC_LON if grid.periodic else 0, states.data_ptr()
+            g.nx, g.ny, g.lon0, g.lat0, g.dlon, g.dlat, g.lon_ref = nx, ny, grid.lon0, grid.lat0, grid.dlon, grid.dlat, grid.lon_ref
+            g.ticks, g.entries = ticks.data_ptr(), None if ent is None else ent.data_ptr()
+            g.outside, g.total, g.nbroken = outside.data_ptr() + 8 * col, total.data_ptr() + 8 * col, nbrk.data_ptr() + 4 * col
+            binding.check(self.lib.ste_grid_metrics_f64(C.byref(s), C.byref(g), self._stream(st)), "ste_grid_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            res = {"ticks": ticks, "hours": ticks.to(torch.float64) / float(binding.STE_GRID_TICKS_PER_HOUR),
+                   "outside": outside[:, col:col + B], "total": total[:, col:col + B], "nbroken": nbrk[:, col:col + B]}
+            if ent is not None:
+                res["entries"] = ent
+            for ten in res.values():
+                ten.record_stream(st)
+        return res
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2107,6 +2187,122 @@ def region_statistics(hb_or_db, polygon, nsamples: int, seed: int = 0, chunk: in
     if din is not None:
         out["dist_inside_smoothed"], out["dist_inside"] = smoothed["dist_inside"][0].cpu().numpy(), din.cpu().numpy()
     out["status"] = status.cpu().numpy()
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackGrid:
+    """A regular lon / lat grid as ``ste_grid_metrics_f64`` wants it (``track_grid`` makes one): cell (ix, iy) is
+    [lon0 + ix dlon, lon0 + (ix + 1) dlon) x [lat0 + iy dlat, lat0 + (iy + 1) dlat); ``periodic``: the columns wrap (the grid
+    is exactly 360 degrees wide); ``lon_ref``: the meridian longitudes are unwrapped about, the grid's mid-longitude."""
+
+    lon0: float
+    lat0: float
+    dlon: float
+    dlat: float
+    nx: int
+    ny: int
+    periodic: bool
+    lon_ref: float
+
+    @property
+    def lon_edges(self) -> np.ndarray:
+        """(nx + 1,) cell edges in longitude, unwrapped (they run on past 180), for plotting."""
+        return self.lon0 + self.dlon * np.arange(self.nx + 1)
+
+    @property
+    def lat_edges(self) -> np.ndarray:
+        """(ny + 1,) cell edges in latitude."""
+        return self.lat0 + self.dlat * np.arange(self.ny + 1)
+
+
+def track_grid(lon0, lat0, dlon, dlat, nx, ny) -> TrackGrid:
+    """A regular grid of ``nx`` x ``ny`` cells of ``dlon`` x ``dlat`` degrees whose cell (0, 0) has its west and south edge at
+    (``lon0``, ``lat0``), for ``DeviceBatch.grid_metrics``.  It is periodic in longitude when ``nx * dlon == 360.0`` exactly;
+    any other grid may be at most 180 degrees wide (one copy of it is then exact for steps of less than 90 degrees).
+    ``lon_ref`` is the grid's mid-longitude.  ``ValueError``: nx or ny not an integer >= 1, or nx * ny above 2^26 cells; a
+    non-finite lon0 or lat0; dlon or dlat not finite or below 1e-6 degrees; a grid wider than 180 degrees that is not
+    periodic."""
+    if int(nx) != nx or int(ny) != ny or int(nx) < 1 or int(ny) < 1:
+        raise ValueError(f"nx and ny must be integers >= 1, got {nx!r} and {ny!r}")
+    nx, ny = int(nx), int(ny)
+    if nx * ny > binding.STE_GRID_MAX_CELLS:
+        raise ValueError(f"a grid may have at most {binding.STE_GRID_MAX_CELLS} cells (2^26), got {nx} x {ny}")
+    lon0, lat0, dlon, dlat = float(lon0), float(lat0), float(dlon), float(dlat)
+    if not (np.isfinite(lon0) and np.isfinite(lat0)):
+        raise ValueError(f"lon0 and lat0 must be finite, got {lon0!r} and {lat0!r}")
+    if not (np.isfinite(dlon) and np.isfinite(dlat) and dlon >= 1e-6 and dlat >= 1e-6):
+        raise ValueError(f"dlon and dlat must be finite and >= 1e-6 degrees, got {dlon!r} and {dlat!r}")
+    width = float(nx) * dlon
+    periodic = width == 360.0
+    lon_ref = lon0 + 0.5 * width
+    if not periodic and not (lon0 - lon_ref >= -90.0 and (lon0 + width) - lon_ref <= 90.0):
+        raise ValueError(f"a grid that is not periodic (nx * dlon == 360) may be at most 180 degrees wide, got {width!r}")
+    return TrackGrid(lon0=lon0, lat0=lat0, dlon=dlon, dlat=dlat, nx=nx, ny=ny, periodic=periodic, lon_ref=lon_ref)
+
+
+def grid_statistics(hb_or_db, grid: TrackGrid, nsamples: int, seed: int = 0, chunk: int = 16, entries: bool = False,
+                    device="cuda:0"):
+    """Ship-hours per cell of ``grid`` with the uncertainty of the smoothing posterior, summed over the tracks: ``nsamples``
+    posterior tracks per ship are drawn (``DeviceBatch.sample_smoothed``), laid on the grid (``DeviceBatch.grid_metrics``) and
+    discarded, ``chunk`` samples at a time, every chunk accumulating into one grid, with the generator discipline of
+    ``region_statistics``: one draw buffer refilled from one generator, so the draws depend on ``(seed, chunk)`` and with
+    ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  Given a ``HostBatch`` it uploads it and runs
+    the forward pass and the smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``; a
+    list or tuple of ``DeviceBatch`` windows of a fleet is summed into one grid, every window drawing from a generator seeded
+    alike, and the per-track outputs follow the order of the list.
+
+    Returns a dict of NumPy arrays: ``hours_smoothed`` (ny, nx), the map of the smoothed tracks ``sm_mean``; ``hours_mean``
+    (ny, nx) = ticks / (2^20 nsamples), the posterior mean of the map; ``ticks`` (ny, nx) int64, the samples' exact sum; with
+    ``entries`` also ``entries_mean`` (ny, nx), entries per cell and sample; ``outside_hours`` (nsamples, B), the time of
+    each sampled track off the grid; ``total_ticks`` (nsamples, B) int64, the ticks of each sampled track's sound steps;
+    ``nbroken`` (nsamples, B) int32; and ``status`` (B,), the sampler's STE_STATUS_* bits."""
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if not isinstance(grid, TrackGrid):
+        raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
+    if isinstance(hb_or_db, (list, tuple)):
+        dbs = list(hb_or_db)
+        if not dbs or not all(isinstance(d, DeviceBatch) for d in dbs):
+            raise ValueError("a list given to grid_statistics() must hold DeviceBatch windows, and at least one")
+    elif isinstance(hb_or_db, DeviceBatch):
+        dbs = [hb_or_db]
+    else:
+        dbs = [DeviceBatch(hb_or_db, device=device)]
+        dbs[0].run()
+    smoothed = acc = None
+    per_track = []
+    for db in dbs:
+        if db.sm_mean is None:
+            raise ValueError("grid_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+        torch = db.torch
+        N, B = int(db.struct.Nmax), db.ntracks
+        smoothed = db.grid_metrics(db.sm_mean, grid, out=smoothed)
+        gen = torch.Generator(device=db.device)
+        gen.manual_seed(int(seed))
+        buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), dtype=torch.float64, device=db.device)
+        outside = torch.empty((nsamples, B), dtype=torch.int64, device=db.device)
+        total = torch.empty((nsamples, B), dtype=torch.int64, device=db.device)
+        nbrk = torch.empty((nsamples, B), dtype=torch.int32, device=db.device)
+        status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+        for i in range(0, nsamples, chunk):
+            n = min(chunk, nsamples - i)
+            draws = buf[:n]
+            draws.normal_(generator=gen)
+            acc = db.grid_metrics(db.sample_smoothed(n, draws=draws), grid, entries=entries, out=acc)
+            outside[i:i + n], total[i:i + n], nbrk[i:i + n] = acc["outside"], acc["total"], acc["nbroken"]
+            status |= db.sample_status
+        per_track.append((outside.cpu().numpy(), total.cpu().numpy(), nbrk.cpu().numpy(), status.cpu().numpy()))
+    tph = float(binding.STE_GRID_TICKS_PER_HOUR)
+    ticks = acc["ticks"].cpu().numpy()
+    out = {"hours_smoothed": smoothed["ticks"].cpu().numpy() / tph, "hours_mean": ticks / (tph * nsamples), "ticks": ticks}
+    if entries:
+        out["entries_mean"] = acc["entries"].cpu().numpy() / float(nsamples)
+    out["outside_hours"] = np.concatenate([p[0] for p in per_track], axis=1) / tph
+    out["total_ticks"] = np.concatenate([p[1] for p in per_track], axis=1)
+    out["nbroken"] = np.concatenate([p[2] for p in per_track], axis=1)
+    out["status"] = np.concatenate([p[3] for p in per_track])
     return out
 
 

@@ -343,6 +343,35 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return out["time_inside"][:, 0]
 
+    def time_on_grid(self, grid, n_samples: int = 0, random_state: int = 0):
+        """Hours the track ``run`` filtered spends in every cell of ``grid``, a ``track_estimators.batch.TrackGrid``
+        (``track_estimators.batch.track_grid`` makes one; no counterpart in the reference): an (ny, nx) array.
+        ``n_samples == 0``: the map of the smoothed track.  Otherwise the mean of the maps of that many tracks drawn from the
+        joint smoothing posterior, those of ``sample_smoothed(n_samples, random_state)``.  The track is packed as ``run``
+        packed it, as for ``time_in_region``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("time_on_grid() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("time_on_grid() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        if not isinstance(grid, _batch.TrackGrid):
+            raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            return db.grid_metrics(db.sm_mean, grid)["hours"].cpu().numpy()
+        out = _batch.grid_statistics(hb, grid, n_samples, seed=int(random_state), chunk=n_samples)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return out["hours_mean"]
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
