@@ -56,7 +56,8 @@ extern "C" {
                            sampled from the smoother (ste_urtss_sample_f64).  Unnumbered addition: path quantities of tracks on the
                            device (ste_path_metrics_f64).  Unnumbered addition: tracks on the device against a polygon
                            (ste_region_metrics_f64).  Unnumbered addition: tracks on the device on a lon / lat grid
-                           (ste_grid_metrics_f64).
+                           (ste_grid_metrics_f64).  Unnumbered addition: pairs of tracks on the device against each other
+                           (ste_encounter_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -496,6 +497,89 @@ typedef struct ste_grid_f64 {
 } ste_grid_f64;            /* 104 bytes */
 
 int ste_grid_metrics_f64(const ste_ukf_batch_f64* b, const ste_grid_f64* g, void* stream);
+
+/*
+ * ENCOUNTERS: PAIRS of tracks that stay on the device against each other (an unnumbered addition, like ste_grid_f64): how close
+ * two ships came and when, and for how long, from when and how often they were within R km of each other.  `states` is that of
+ * ste_path_f64; sample s of ship i is held against sample s of ship j.  Every ship has its own dt, so the two are walked on a
+ * common clock.  A position is linear in time inside a step, in planar (lon, lat), and a step is broken by the rule of
+ * ste_region_f64.  Below clamp01(x) = x < 0 ? 0 : (x > 1 ? 1 : x), max(x, y) = x > y ? x : y, min(x, y) = x < y ? x : y, and
+ * every expression is evaluated as written, left to right, without contraction.
+ *   - Clock.  Track t has knots tau_t[k] = t0[t] + T_k, T_0 = 0, T_{k+1} = T_k + dt_k summed in order; the single addition of
+ *     t0 is made at use.  t0 NULL is 0 for every track.
+ *   - Walk.  For pair (i, j), ns_i = nsteps[i], ns_j = nsteps[j]: start with a = b = 0 and repeat while a < ns_i and b < ns_j:
+ *     lo = max(tau_i[a], tau_j[b]), ea = tau_i[a+1], eb = tau_j[b+1], hi = min(ea, eb).  If hi > lo the PIECE (a, b, lo, hi) is
+ *     examined.  Then a advances if ea <= eb and b advances if eb <= ea (both on a tie).  Pieces are examined in this order,
+ *     which defines "first" below.
+ *   - Bad clock.  A pair has a bad clock when t0 of either ship is not finite (checked before the walk: no comparison of the
+ *     walk would be true and it would not end) or when a dt the walk reads -- dt_a of ship i and dt_b of ship j at the top of
+ *     a repetition -- is not finite and >= 0.  A bad clock sets STE_ENC_BAD_TIME in status, ends the walk and gives min_dist,
+ *     min_time and first_within = NaN and zero for every other output.
+ *   - Bad index.  An index outside [0, B) sets STE_ENC_BAD_INDEX and gives the outputs of a bad clock; nothing of that pair is
+ *     read.  A pair with i == j is valid and gives distance 0.
+ *   - Soundness.  A step of a ship is BROKEN when |delta| < 90 is false, delta = wrap180(lon_{k+1} - lon_k), or either of its
+ *     latitudes is not finite.  A piece on a broken step of either ship adds 1 to nbroken and nothing else, and closes an open
+ *     run.  Every other piece is SOUND.
+ *   - Positions in a piece.  Ship i on step a, dt = dt_a: u0 = clamp01((lo - tau_i[a]) / dt), u1 = clamp01((hi - tau_i[a]) / dt),
+ *     x(u) = lon_a + u * delta, y(u) = lat_a + u * (lat_{a+1} - lat_a); (xi0, yi0) at u0 and (xi1, yi1) at u1.  Ship j on
+ *     step b likewise.
+ *   - Relative motion.  gx0 = wrap180(xj0 - xi0), gy0 = yj0 - yi0, gx1 = gx0 + ((xj1 - xj0) - (xi1 - xi0)) (continuous, never
+ *     re-wrapped), gy1 = yj1 - yi1.  c = cos(0.25 * ((yi0 + yi1) + (yj0 + yj1)) * kDeg2Rad), Kd = 6378.137 * kDeg2Rad (one
+ *     double), kc = Kd * c.  r0 = (kc * gx0, Kd * gy0), r1 = (kc * gx1, Kd * gy1), d = r1 - r0, dd = d.x * d.x + d.y * d.y,
+ *     bq = r0.x * d.x + r0.y * d.y, r00 = r0.x * r0.x + r0.y * r0.y.  cos is the only operation here whose bits may differ
+ *     between implementations.
+ *   - Closest approach.  u* = dd > 0 ? clamp01(-bq / dd) : 0, m = (r0.x + u* * d.x, r0.y + u* * d.y), q = m.x * m.x + m.y * m.y.
+ *     The piece becomes the best one when q < best_q (best_q starts at +inf; strict, so the first piece wins a tie).  It then
+ *     records min_time = lo + u* * (hi - lo) and the two positions (xi0 + u* * (xi1 - xi0), yi0 + u* * (yi1 - yi0)) and likewise
+ *     for j.  After the walk min_dist is the leg of ste_path_metrics_f64 for `model` between those two positions (NaN when a
+ *     coordinate is not finite): the leg function runs once per (sample, pair).  Without a best piece min_dist and min_time
+ *     are NaN.
+ *   - Within R, R = radius_km.  If dd > 0: disc = bq * bq - dd * (r00 - R * R), and if disc >= 0: sq = sqrt(disc),
+ *     ua = max((-bq - sq) / dd, 0), ub = min((-bq + sq) / dd, 1).  If dd == 0: ua = 0, ub = 1 iff r00 <= R * R.  Otherwise
+ *     there is no interval.  If ub > ua: time_within += (ub - ua) * (hi - lo); a new RUN starts unless the run is open and
+ *     ua == 0; a new run adds 1 to nwithin and the first one sets first_within = lo + ua * (hi - lo); after that the run is open
+ *     iff ub == 1.  A piece without an interval, a broken piece and the end of the walk close the run.  No tolerance anywhere.
+ *   - Overlap.  overlap is the sum of hi - lo over the sound pieces, in piece order.
+ *   - Accuracy.  The planar metric is for ships close together: its relative error is about tan(lat) times half the latitude
+ *     change over a piece (radians) plus (separation / 6378 km)^2.  On the test fleet (steps of about 0.1 degrees at 50 N,
+ *     separations up to 90 km) sqrt(q) and min_dist differ by up to 1.6e-3 relative.  min_dist is a true distance (of `model`)
+ *     at the time the planar distance is least; time_within, first_within and nwithin are planar, hence the limit on
+ *     radius_km.
+ *   - Every value's bits depend on the two tracks' rows, their dt, t0 and R alone: not on S, P, the place of the pair in the
+ *     list, the window, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64, t0 like nsteps, pair indices count from the
+ *     window's first track.  Rows past nsteps[t] of states are not read.  Outputs per pair are out[s * P + p]; status[p].
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or en NULL; states or pairs NULL; nstates < 1
+ *     or > 65535; npairs < 1 or > STE_ENCOUNTER_MAX_PAIRS; an unknown model when min_dist is asked for; radius_km not finite,
+ *     < 0 or > STE_ENCOUNTER_MAX_RADIUS_KM; flags or reserved non-zero; b->dt NULL; every output NULL; B <= 0, Nmax < 0, or
+ *     track_stride non-zero and below B.
+ */
+#define STE_ENCOUNTER_MAX_PAIRS (1 << 26)
+#define STE_ENCOUNTER_MAX_RADIUS_KM 1000.0
+#define STE_ENC_BAD_INDEX 0x1  /* a pair index outside [0, B): nothing of that pair is read */
+#define STE_ENC_BAD_TIME  0x2  /* a non-finite t0, or a dt met by the walk that is not finite and >= 0 */
+typedef struct ste_encounter_f64 {
+    int32_t nstates;       /* S >= 1 (<= 65535); sample s of ship i is held against sample s of ship j */
+    int32_t model;         /* STE_PREP_SPHERE / STE_PREP_WGS84: leg function for min_dist only */
+    const double* states;  /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 */
+    int64_t npairs;        /* P, 1 .. STE_ENCOUNTER_MAX_PAIRS */
+    const int32_t* pairs;  /* DEVICE [P][2]: (i, j), tracks of the window, 0 <= i, j < B */
+    const double* t0;      /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track, hours */
+    double radius_km;      /* HOST: R, finite, 0 <= R <= STE_ENCOUNTER_MAX_RADIUS_KM */
+    uint32_t flags;        /* must be 0 */
+    uint32_t reserved;     /* must be 0 */
+    double* min_dist;      /* DEVICE [S][P] or NULL: km at the closest approach, NaN = no sound piece */
+    double* min_time;      /* DEVICE [S][P] or NULL: its clock time, hours; NaN likewise */
+    double* time_within;   /* DEVICE [S][P] or NULL: hours with planar distance <= R */
+    double* first_within;  /* DEVICE [S][P] or NULL: clock time of the first run within R, NaN = none */
+    int32_t* nwithin;      /* DEVICE [S][P] or NULL: runs within R */
+    double* overlap;       /* DEVICE [S][P] or NULL: hours of sound pieces (common clock time examined) */
+    int32_t* nbroken;      /* DEVICE [S][P] or NULL: pieces skipped because a step of either ship is broken */
+    int32_t* status;       /* DEVICE [P] or NULL: STE_ENC_* bits (they do not depend on the sample) */
+} ste_encounter_f64;       /* 120 bytes */
+
+int ste_encounter_metrics_f64(const ste_ukf_batch_f64* b, const ste_encounter_f64* en, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -191,6 +191,36 @@ class SteGridF64(C.Structure):
     ]
 
 
+STE_ENCOUNTER_MAX_PAIRS = 1 << 26
+STE_ENCOUNTER_MAX_RADIUS_KM = 1000.0
+STE_ENC_BAD_INDEX = 0x1
+STE_ENC_BAD_TIME = 0x2
+
+
+class SteEncounterF64(C.Structure):
+    """Mirror of ``struct ste_encounter_f64`` (include/ste.h): pairs of tracks on the device against each other."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("npairs", C.c_int64),
+        ("pairs", _dp),
+        ("t0", _dp),
+        ("radius_km", C.c_double),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("min_dist", _dp),
+        ("min_time", _dp),
+        ("time_within", _dp),
+        ("first_within", _dp),
+        ("nwithin", _dp),
+        ("overlap", _dp),
+        ("nbroken", _dp),
+        ("status", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -301,6 +331,7 @@ SYMBOLS = {
     "ste_path_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePathF64), C.c_void_p]),
     "ste_region_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRegionF64), C.c_void_p]),
     "ste_grid_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteGridF64), C.c_void_p]),
+    "ste_encounter_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteEncounterF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

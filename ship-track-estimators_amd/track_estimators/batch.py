@@ -1013,6 +1013,103 @@ class DeviceBatch:
                 ten.record_stream(st)
         return res
 
+    # -- encounters -----------------------------------------------------------------------------------------------
+    def encounter_metrics(self, states, pairs, radius_km, t0=None, model: str = "sphere", stream=None):
+        """Pairs of tracks that are on the device against each other (include/ste.h: ste_encounter_metrics_f64; DESIGN.md,
+        "Encounters"): closest approach and time within ``radius_km``.  ``states`` as in ``path_metrics``; sample s of one
+        ship is held against sample s of the other.  ``pairs``: a (P, 2) integer array or device tensor of track indices
+        (i, j) of this batch (of this window, counted from its first track); only its shape and dtype are checked here, an
+        index outside [0, B) comes back as STE_ENC_BAD_INDEX in ``status``.  ``t0``: the clock time of row 0 in hours, None
+        (0 for every track), a scalar or one value per track ((B,) array or tensor); every track's clock then runs on its own
+        ``dt``.  ``model``: the leg function of ``min_dist``, "sphere" or "wgs84".  Returns a dict of device tensors, (S, P)
+        each: ``min_dist`` in km, NaN where the two clocks share no sound time; ``min_time``, its clock time; ``time_within``,
+        hours with the planar distance <= ``radius_km``; ``first_within``, the clock time the first such run starts, NaN =
+        never; ``nwithin`` int32, the number of runs; ``overlap``, the hours of common clock time examined; ``nbroken`` int32,
+        the pieces left out (a NaN latitude, or 90 degrees of longitude or more in one step); and ``status`` (P,) int32,
+        STE_ENC_BAD_INDEX / STE_ENC_BAD_TIME (a non-finite ``t0``, a ``dt`` that is not finite and >= 0).  The geometry of the
+        search is planar in (lon, lat): it is meant for ships close together (``radius_km`` <= 1000).  Windows, in-place
+        views and ``stream`` as in ``path_metrics``; every value depends on the two tracks' rows, ``dt``, ``t0`` and the
+        radius alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        radius_km = float(radius_km)
+        if not (np.isfinite(radius_km) and 0.0 <= radius_km <= binding.STE_ENCOUNTER_MAX_RADIUS_KM):
+            raise ValueError(f"radius_km must be finite and between 0 and {binding.STE_ENCOUNTER_MAX_RADIUS_KM:g}, got {radius_km!r}")
+        if not isinstance(pairs, torch.Tensor):
+            pairs = np.asarray(pairs)
+            if pairs.dtype.kind not in "iu":
+                raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
+            pairs = torch.from_numpy(np.ascontiguousarray(pairs.astype(np.int64)))
+        elif pairs.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= binding.STE_ENCOUNTER_MAX_PAIRS:
+            raise ValueError(f"pairs must have shape (P, 2) with 1 <= P <= {binding.STE_ENCOUNTER_MAX_PAIRS}, got {tuple(pairs.shape)}")
+        S, P = int(states.shape[0]), int(pairs.shape[0])
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            # an index that does not fit 32 bits stays outside [0, B)
+            pr = pairs.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, pr]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            en = binding.SteEncounterF64()
+            en.nstates, en.model, en.states = S, self._PATH_MODELS[model], states.data_ptr()
+            en.npairs, en.pairs, en.radius_km, en.flags, en.reserved = P, pr.data_ptr(), radius_km, 0, 0
+            if t0 is not None:
+                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
+                if tv.dim() == 0:
+                    tv = tv.expand(B)
+                if tuple(tv.shape) != (B,):
+                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+                clock = torch.zeros((width,), **f64)
+                clock[col:col + B] = tv
+                en.t0 = clock.data_ptr() + 8 * col
+                keep.append(clock)
+            out = {k: torch.empty((S, P), **f64) for k in ("min_dist", "min_time", "time_within", "first_within", "overlap")}
+            out.update({k: torch.empty((S, P), **i32) for k in ("nwithin", "nbroken")})
+            out["status"] = torch.empty((P,), **i32)
+            for k, ten in out.items():
+                setattr(en, k, ten.data_ptr())
+            binding.check(self.lib.ste_encounter_metrics_f64(C.byref(s), C.byref(en), self._stream(st)),
+                          "ste_encounter_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2303,6 +2400,151 @@ def grid_statistics(hb_or_db, grid: TrackGrid, nsamples: int, seed: int = 0, chu
     out["total_ticks"] = np.concatenate([p[1] for p in per_track], axis=1)
     out["nbroken"] = np.concatenate([p[2] for p in per_track], axis=1)
     out["status"] = np.concatenate([p[3] for p in per_track])
+    return out
+
+
+EARTH_RADIUS_KM = 6378.137  # the sphere of the haversine leg and of the encounter kernel's planar metric
+
+
+def candidate_pairs(mean, nsteps, dt, radius_km, margin_km: float = 0.0, t0=None, chunk: int = 2048):
+    """The pair test of ``encounter_candidates`` on plain tensors of any one device: ``mean`` (Nmax+1, 4, B) float64,
+    ``nsteps`` (B,) integer, ``dt`` (Nmax, B) float64, ``t0`` None, a scalar or (B,).  Returns an int32 (P, 2) tensor of
+    (i, j), i < j, sorted by (i, j)."""
+    import torch
+
+    rows, _, B = mean.shape
+    dev = mean.device
+    ns = nsteps.to(dev).to(torch.int64).clamp(0, rows - 1)
+    live = torch.arange(rows, device=dev)[:, None] <= ns[None, :]                     # (rows, B)
+    lon, lat = torch.deg2rad(mean[:, 0]), torch.deg2rad(mean[:, 1])
+    unit = torch.stack([torch.cos(lat) * torch.cos(lon), torch.cos(lat) * torch.sin(lon), torch.sin(lat)])  # (3, rows, B)
+    finite = torch.isfinite(unit).all(dim=0)
+    ok = (ns > 0) & (finite | ~live).all(dim=0)
+    unit = torch.where(live[None], unit, torch.zeros_like(unit))
+    centre = unit.sum(dim=1)
+    norm = centre.norm(dim=0)
+    ok = ok & (norm > 0.0)
+    centre = centre / torch.where(norm > 0.0, norm, torch.ones_like(norm))           # (3, B)
+    # angles from chords: 2 asin(|u - v| / 2), which keeps its precision for small angles
+    chord = (unit - centre[:, None, :]).norm(dim=0)
+    chord = torch.where(live, chord, torch.zeros_like(chord))
+    cap = 2.0 * torch.asin((0.5 * chord).clamp(max=1.0)).max(dim=0).values            # (B,)
+    if t0 is None:
+        start = torch.zeros((B,), dtype=torch.float64, device=dev)
+    else:
+        start = torch.as_tensor(t0, dtype=torch.float64).to(dev).expand(B)
+    steps_live = torch.arange(rows - 1, device=dev)[:, None] < ns[None, :]
+    end = start + torch.where(steps_live, dt.to(dev), torch.zeros_like(dt)).sum(dim=0)
+    ok = ok & torch.isfinite(start) & torch.isfinite(end)
+    # 1e-7 rad (0.6 m): the rounding of an angle taken from a dot product of unit vectors is below sqrt(2^-52) = 1.5e-8
+    reach = (float(radius_km) + float(margin_km)) / EARTH_RADIUS_KM + 1e-7
+    idx = torch.arange(B, device=dev)
+    found = []
+    for lo in range(0, B, int(chunk)):
+        hi = min(lo + int(chunk), B)
+        dot = centre[:, lo:hi].T @ centre                                             # (hi - lo, B)
+        angle = 2.0 * torch.asin(torch.sqrt((0.5 * (1.0 - dot)).clamp(0.0, 1.0)))
+        near = angle <= cap[lo:hi, None] + cap[None, :] + reach
+        clocks = torch.maximum(start[lo:hi, None], start[None, :]) <= torch.minimum(end[lo:hi, None], end[None, :])
+        keep = near & clocks & ok[lo:hi, None] & ok[None, :] & (idx[None, :] > idx[lo:hi, None])
+        ij = keep.nonzero()                                                           # row-major: sorted by (i, j)
+        ij[:, 0] += lo
+        found.append(ij)
+    return torch.cat(found).to(torch.int32)
+
+
+def encounter_candidates(db: "DeviceBatch", radius_km, margin_km: float = 0.0, t0=None, chunk: int = 2048):
+    """The pairs of a resident batch worth giving to ``DeviceBatch.encounter_metrics``: an int32 (P, 2) device tensor of
+    (i, j), i < j, sorted by (i, j), on the batch's device.  Torch plumbing without a kernel, on ``sm_mean`` (``fwd_mean`` when
+    the batch has no smoother).  Every track gets a bounding cap on the unit sphere (centre: the normalised sum of its rows'
+    unit vectors; angular radius: the largest angle to one of its rows 0 .. nsteps) and a clock span [t0, t0 + sum of its dt];
+    a pair is kept when the clock spans overlap and the angle between the centres is at most the sum of the two radii plus
+    (``radius_km`` + ``margin_km``) / 6378.137.  The B x B test runs in blocks of ``chunk`` rows, so memory stays at a few
+    times chunk x B doubles.  Tracks with ``nsteps == 0`` or a non-finite row pair with nothing; the test is on unit vectors,
+    so the antimeridian is no special case.  ``margin_km`` must cover what the tested track does not show: the posterior spread
+    when the pairs are then used on samples of the posterior (a few standard deviations of position), and the 0.2 % by which
+    the kernel's planar distance may differ from the true one."""
+    mean = db.sm_mean if db.sm_mean is not None else db.fwd_mean
+    if mean is None:
+        raise ValueError("encounter_candidates() needs sm_mean or fwd_mean, and this batch was built without histories")
+    B = db.ntracks
+    nsteps = db.t["nsteps"][db.lo:db.lo + B]
+    dt = db.t["dt"][:, db.lo:db.lo + B]
+    with db.torch.cuda.device(db.device):
+        return candidate_pairs(mean, nsteps, dt, radius_km, margin_km, t0, chunk)
+
+
+def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 0, chunk: int = 16, t0=None,
+                         model: str = "sphere", quantiles=(0.05, 0.5, 0.95), device="cuda:0"):
+    """Closest approach and time within ``radius_km`` of pairs of ships with the uncertainty of the smoothing posterior:
+    ``nsamples`` posterior tracks per ship are drawn (``DeviceBatch.sample_smoothed``), sample s of one ship held against
+    sample s of the other (``DeviceBatch.encounter_metrics``) and discarded, ``chunk`` samples at a time, with the generator
+    discipline of ``region_statistics``: one draw buffer refilled from one generator, so the draws depend on ``(seed, chunk)``
+    and with ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  The ships' posteriors are taken as
+    independent (each is smoothed on its own).  Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother
+    first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``pairs``, ``radius_km``, ``t0``
+    and ``model`` as in ``encounter_metrics``.
+
+    Returns a dict of NumPy arrays per pair: ``min_dist_smoothed``, ``min_time_smoothed``, ``time_within_smoothed``,
+    ``overlap_smoothed`` (P,) and ``status`` (P,; STE_ENC_* bits), of the smoothed tracks ``sm_mean``; ``min_dist``
+    (nsamples, P) with ``min_dist_mean``, ``min_dist_std`` (ddof = 1, 0 for a single sample) and ``min_dist_quantiles``
+    (len(quantiles), P), over the samples that have a distance; ``min_time`` and ``min_time_quantiles``; ``time_within``
+    with ``time_within_mean`` and ``time_within_quantiles``; ``nwithin`` (nsamples, P); ``encounter_prob`` (P,), the fraction
+    of samples that come within ``radius_km``; ``first_within``, NaN where a sample never does, and
+    ``first_within_quantiles`` over the samples that do, NaN where none does; and ``sample_status`` (B,), the sampler's
+    STE_STATUS_* bits per track."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("encounter_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    kw = dict(t0=t0, model=model)
+    smoothed = db.encounter_metrics(db.sm_mean, pairs, radius_km, **kw)
+    P = int(smoothed["status"].shape[0])
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    f64 = dict(dtype=torch.float64, device=db.device)
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    names = ("min_dist", "min_time", "time_within", "first_within")
+    acc = {k: torch.empty((nsamples, P), **f64) for k in names}
+    nwit = torch.empty((nsamples, P), dtype=torch.int32, device=db.device)
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        draws = buf[:n]
+        draws.normal_(generator=gen)
+        m = db.encounter_metrics(db.sample_smoothed(n, draws=draws), pairs, radius_km, **kw)
+        for k in names:
+            acc[k][i:i + n] = m[k]
+        nwit[i:i + n] = m["nwithin"]
+        status |= db.sample_status
+    q = np.asarray(quantiles, dtype=np.float64)
+    host = {k: v.cpu().numpy() for k, v in acc.items()}
+    nw = nwit.cpu().numpy()
+    out = {k + "_smoothed": smoothed[k][0].cpu().numpy() for k in ("min_dist", "min_time", "time_within", "overlap")}
+    out["status"] = smoothed["status"].cpu().numpy()
+    with warnings.catch_warnings():  # a pair no sample gives a distance (or brings within the radius): all-NaN column, NaN out
+        warnings.simplefilter("ignore", RuntimeWarning)
+        d = host["min_dist"]
+        out.update({"min_dist": d, "min_dist_mean": np.nanmean(d, axis=0),
+                    "min_dist_std": np.nanstd(d, axis=0, ddof=1) if nsamples > 1 else np.where(np.isnan(d[0]), np.nan, 0.0),
+                    "min_dist_quantiles": np.nanquantile(d, q, axis=0),
+                    "min_time": host["min_time"], "min_time_quantiles": np.nanquantile(host["min_time"], q, axis=0),
+                    "time_within": host["time_within"], "time_within_mean": host["time_within"].mean(axis=0),
+                    "time_within_quantiles": np.quantile(host["time_within"], q, axis=0),
+                    "nwithin": nw, "encounter_prob": (nw > 0).mean(axis=0),
+                    "first_within": host["first_within"],
+                    "first_within_quantiles": np.nanquantile(host["first_within"], q, axis=0)})
+    out["sample_status"] = status.cpu().numpy()
     return out
 
 
