@@ -22,6 +22,9 @@
  *                            counterpart in the reference: its callers would loop over a geometry library on a download)
  *   ste_grid_metrics_f64     ship-hours per cell of a regular lon / lat grid, summed over such tracks in exact integer ticks,
  *                            and entries per cell (no counterpart in the reference: a download and a host loop)
+ *   ste_encounter_metrics_f64  closest approach and time within a radius of pairs of such tracks (no counterpart in the reference)
+ *   ste_track_positions_f64  position, speed and heading of such tracks at given clock times, and the moments of the positions over
+ *                            the samples for an error ellipse (no counterpart in the reference: a download, a search and a host loop)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -57,7 +60,8 @@ extern "C" {
                            device (ste_path_metrics_f64).  Unnumbered addition: tracks on the device against a polygon
                            (ste_region_metrics_f64).  Unnumbered addition: tracks on the device on a lon / lat grid
                            (ste_grid_metrics_f64).  Unnumbered addition: pairs of tracks on the device against each other
-                           (ste_encounter_metrics_f64).
+                           (ste_encounter_metrics_f64).  Unnumbered addition: tracks on the device at given clock times
+                           (ste_track_positions_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -580,6 +584,80 @@ typedef struct ste_encounter_f64 {
 } ste_encounter_f64;       /* 120 bytes */
 
 int ste_encounter_metrics_f64(const ste_ukf_batch_f64* b, const ste_encounter_f64* en, void* stream);
+
+/*
+ * POSITIONS: where tracks that stay on the device were AT GIVEN CLOCK TIMES (an unnumbered addition, like ste_encounter_f64):
+ * longitude, latitude, speed and heading of every sample at a list of (track, time) queries, and the moments of the positions
+ * OVER THE SAMPLES about an anchor, from which a caller makes a mean position and an error ellipse per query.  `states` is that
+ * of ste_path_f64 and the clock that of ste_encounter_f64.  A position is linear in time inside a step, in planar (lon, lat), and
+ * a step is broken by the rule of ste_region_f64.  Below clamp01(x) = x < 0 ? 0 : (x > 1 ? 1 : x), wrap180 is that of
+ * ste_path_f64, a % 360 is the floored modulus (NumPy's), and every expression is evaluated as written, left to right, without
+ * contraction.  No operation here has bits that may differ between implementations: the library and a NumPy restatement agree
+ * bit for bit.
+ *   - Knots.  Track t, ns = nsteps[t]: T_0 = 0, T_{k+1} = T_k + dt_k for k < ns, summed in order.  The clock of a track is BAD when
+ *     some dt_k, k < ns, is not finite and >= 0, or when t0[t] is not finite.  The call writes T_k into knots[k][t] for k <= ns
+ *     (knots[k * track_stride + t]), with knots[0][t] = NaN marking a bad dt and 0 otherwise; rows past ns are left alone.  With
+ *     STE_POS_REUSE_KNOTS it reads `knots` as a previous call on the same batch left them and does not read dt.
+ *     tau_k = t0[t] + T_k: the single addition of t0 is made at use.  t0 NULL is 0 for every track.
+ *   - Bad index.  qtrack[q] outside [0, B) sets STE_POS_BAD_INDEX; nothing of that query's track is read.
+ *   - Bad time.  A bad clock or a non-finite qtime[q] sets STE_POS_BAD_TIME.
+ *   - Locate, with tq = qtime[q].  (1) If tq == tau_0 the answer is ROW 0, for ns == 0 too.  (2) Otherwise, if ns == 0, or
+ *     tq >= tau_0 is false, or tq <= tau_ns is false, the status is STE_POS_OUTSIDE: the call never extrapolates.  (3) Otherwise
+ *     k is the smallest index in [0, ns) with tq <= tau_{k+1}; if tq == tau_{k+1} the answer is ROW k + 1.  tau is
+ *     non-decreasing, so a bisection finds the k of a scan.  (4) Otherwise the query is INTERIOR to step k with
+ *     u = clamp01((tq - tau_k) / (T_{k+1} - T_k)).  The divisor is the length of the step on the clock that was searched: it is
+ *     dt_k rounded once (by the sum that made T_{k+1}), it is > 0 here because tau_k < tq < tau_{k+1}, and the call can form it
+ *     from `knots` alone, which is what lets STE_POS_REUSE_KNOTS leave dt unread.  step[q] is the row of a knot hit or k, -1 when
+ *     the query is not located; frac[q] is 0 on a knot hit or u, NaN when not located.
+ *   - Knot hit on row j.  Per sample the outputs are the row itself: wrap180(lon_j), lat_j, speed_j, heading_j % 360.  A NaN
+ *     stays a NaN; no step's soundness is consulted and no other row is read.
+ *   - Interior.  delta = wrap180(lon_{k+1} - lon_k).  Step k is BROKEN when |delta| < 90 is false or either latitude is not
+ *     finite, and then all four outputs are NaN.  Otherwise lon = wrap180(lon_k + u * delta), lat = lat_k + u * (lat_{k+1} -
+ *     lat_k), speed = s_k + u * (s_{k+1} - s_k), heading = (h_k + u * wrap180(h_{k+1} - h_k)) % 360.
+ *   - Not located.  A bad index, a bad time or an outside query gives NaN in every per-sample output and adds nothing to count
+ *     or moments.
+ *   - Moments.  For query q, for s = 0 .. S - 1 in order: dx = wrap180(lon - anchor[0][q]), dy = lat - anchor[1][q]; if both are
+ *     finite, count[q] += 1 and the sums of dx, dy, dx * dx, dx * dy, dy * dy (moments[0..5)[q]) take one addition each.  The sums
+ *     START FROM THE STORED VALUES and are stored once at the end, so a call with S samples equals a call with the first S1 and
+ *     a call with the other S - S1 on the same accumulators, bit for bit.  The caller zeroes them before the first call.  The
+ *     moments are in degrees.
+ *   - Every value's bits depend on the track's rows, its dt, t0, the query and (the moments) the stored accumulators alone: not
+ *     on Q, the place of the query in the list, S, the window, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64, t0 and the columns of knots like nsteps, qtrack counts
+ *     from the window's first track.  Rows past nsteps[t] of states are not read.  Outputs per sample are out[s * Q + q].
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or po NULL; states, qtrack, qtime or knots
+ *     NULL; nstates < 1 or > 65535; nqueries < 1 or > STE_POSITIONS_MAX_QUERIES; unknown flag bits; b->dt NULL without
+ *     STE_POS_REUSE_KNOTS; count without moments or moments without count, or either without anchor; every output NULL; B <= 0,
+ *     Nmax < 0, or track_stride non-zero and below B.
+ */
+#define STE_POSITIONS_MAX_QUERIES (1 << 26)
+#define STE_POS_REUSE_KNOTS 0x1u /* `knots` holds what a previous call on this batch wrote: it is read, dt is not */
+#define STE_POS_BAD_INDEX 0x1    /* qtrack outside [0, B): nothing of that query's track is read */
+#define STE_POS_BAD_TIME  0x2    /* a non-finite t0 or qtime, or a dt of the track that is not finite and >= 0 */
+#define STE_POS_OUTSIDE   0x4    /* the time lies before row 0 or after row nsteps of the track (or the track has no step) */
+typedef struct ste_positions_f64 {
+    int32_t nstates;        /* S >= 1 tracks per ship in `states` (<= 65535) */
+    uint32_t flags;         /* STE_POS_REUSE_KNOTS; unknown bits refused */
+    const double* states;   /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 */
+    int64_t nqueries;       /* Q, 1 .. STE_POSITIONS_MAX_QUERIES */
+    const int32_t* qtrack;  /* DEVICE [Q]: track of the window, 0 <= t < B */
+    const double* qtime;    /* DEVICE [Q]: clock time, hours */
+    const double* t0;       /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track, as ste_encounter_f64 */
+    double* knots;          /* DEVICE [Nmax+1][track_stride] workspace, required, caller-owned: written, or read with the flag */
+    const double* anchor;   /* DEVICE [2][Q]: lon then lat in degrees; required when count and moments are given */
+    double* lon;            /* DEVICE [S][Q] or NULL: degrees in [-180, 180) */
+    double* lat;            /* DEVICE [S][Q] or NULL */
+    double* speed;          /* DEVICE [S][Q] or NULL: km/h */
+    double* heading;        /* DEVICE [S][Q] or NULL: degrees in [0, 360] */
+    int32_t* step;          /* DEVICE [Q] or NULL: row of a knot hit, or k; -1 = not located */
+    double* frac;           /* DEVICE [Q] or NULL: 0 on a knot hit, or u; NaN = not located */
+    int32_t* status;        /* DEVICE [Q] or NULL: STE_POS_* bits (step, frac and status do not depend on the sample) */
+    int32_t* count;         /* DEVICE [Q], ACCUMULATED (+=), or NULL: samples with a finite dx and dy; with moments or not at all */
+    double* moments;        /* DEVICE [5][Q], ACCUMULATED: sums of dx, dy, dx dx, dx dy, dy dy in degrees; or NULL */
+} ste_positions_f64;        /* 136 bytes */
+
+int ste_track_positions_f64(const ste_ukf_batch_f64* b, const ste_positions_f64* po, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

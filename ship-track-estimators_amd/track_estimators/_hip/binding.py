@@ -221,6 +221,38 @@ class SteEncounterF64(C.Structure):
     ]
 
 
+STE_POSITIONS_MAX_QUERIES = 1 << 26
+STE_POS_REUSE_KNOTS = 0x1
+STE_POS_BAD_INDEX = 0x1
+STE_POS_BAD_TIME = 0x2
+STE_POS_OUTSIDE = 0x4
+
+
+class StePositionsF64(C.Structure):
+    """Mirror of ``struct ste_positions_f64`` (include/ste.h): tracks on the device at given clock times."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("flags", C.c_uint32),
+        ("states", _dp),
+        ("nqueries", C.c_int64),
+        ("qtrack", _dp),
+        ("qtime", _dp),
+        ("t0", _dp),
+        ("knots", _dp),
+        ("anchor", _dp),
+        ("lon", _dp),
+        ("lat", _dp),
+        ("speed", _dp),
+        ("heading", _dp),
+        ("step", _dp),
+        ("frac", _dp),
+        ("status", _dp),
+        ("count", _dp),
+        ("moments", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -332,6 +364,7 @@ SYMBOLS = {
     "ste_region_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRegionF64), C.c_void_p]),
     "ste_grid_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteGridF64), C.c_void_p]),
     "ste_encounter_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteEncounterF64), C.c_void_p]),
+    "ste_track_positions_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePositionsF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1110,6 +1110,165 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- positions at query times ---------------------------------------------------------------------------------
+    def positions_at(self, states, qtrack, qtime, t0=None, velocity: bool = False, anchor=None, accumulate=None, knots=None,
+                     stream=None, sort: bool = True):
+        """Where tracks that are on the device were at given clock times (include/ste.h: ste_track_positions_f64; DESIGN.md,
+        "Positions").  ``states`` as in ``path_metrics``.  ``qtrack``: (Q,) integer array or device tensor of track indices of
+        this batch (of this window, counted from its first track); ``qtime``: (Q,) clock times in hours.  ``t0`` as in
+        ``encounter_metrics``: the clock time of row 0, None (0), a scalar or one value per track.  A position is linear in time
+        inside a step and a query at a knot returns that row; nothing is extrapolated.  Returns a dict of device tensors:
+        ``lon``, ``lat`` (S, Q) and with ``velocity`` also ``speed``, ``heading`` (S, Q), NaN where the query is not located or
+        its step is broken; ``step`` (Q,) int32, the row of a knot hit or the step, -1 = not located; ``frac`` (Q,), the
+        fraction of the step, 0 on a knot hit; ``status`` (Q,) int32, STE_POS_BAD_INDEX / STE_POS_BAD_TIME / STE_POS_OUTSIDE;
+        and ``knots`` (Nmax+1, B), the knot times the call summed from ``dt``: passed back in as ``knots=`` they are reused
+        (STE_POS_REUSE_KNOTS) instead of summed again.  With ``anchor``, a (2, Q) array or tensor of lon / lat degrees, also
+        ``count`` (Q,) int32 and ``moments`` (5, Q): the number of samples with a finite position and the sums over the samples
+        of dx, dy, dx dx, dx dy, dy dy, dx = wrap180(lon - anchor lon), dy = lat - anchor lat, in degrees.  They start from zero,
+        or with ``accumulate=(count, moments)`` from those two tensors, which are updated in place and returned: S samples in
+        one call and the same samples in several calls give the same bits.  The queries are sorted by (track, time) for the
+        kernel (lanes that share a track share cache lines) and the outputs come back in the caller's order; ``sort=False``
+        takes the list as it is.  No value depends on the order.  Windows, in-place views and ``stream`` as in ``path_metrics``."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if not isinstance(qtrack, torch.Tensor):
+            qtrack = np.asarray(qtrack)
+            if qtrack.dtype.kind not in "iu":
+                raise ValueError(f"qtrack must be a (Q,) integer array or tensor, got dtype {qtrack.dtype}")
+            qtrack = torch.from_numpy(np.ascontiguousarray(qtrack.astype(np.int64)))
+        elif qtrack.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"qtrack must be a (Q,) integer array or tensor, got dtype {qtrack.dtype}")
+        if qtrack.dim() != 1 or not 1 <= qtrack.shape[0] <= binding.STE_POSITIONS_MAX_QUERIES:
+            raise ValueError(f"qtrack must have shape (Q,) with 1 <= Q <= {binding.STE_POSITIONS_MAX_QUERIES}, got {tuple(qtrack.shape)}")
+        S, Q = int(states.shape[0]), int(qtrack.shape[0])
+        qtime = torch.as_tensor(qtime, dtype=torch.float64)
+        if tuple(qtime.shape) != (Q,):
+            raise ValueError(f"qtime must have shape ({Q},) like qtrack, got {tuple(qtime.shape)}")
+        if anchor is not None:
+            anchor = torch.as_tensor(anchor, dtype=torch.float64)
+            if tuple(anchor.shape) != (2, Q):
+                raise ValueError(f"anchor must have shape (2, {Q}): lon and lat per query, got {tuple(anchor.shape)}")
+        if accumulate is not None:
+            if anchor is None:
+                raise ValueError("accumulate continues the moments about an anchor: give the anchor they were started with")
+            count, moments = accumulate
+            ok = (isinstance(count, torch.Tensor) and isinstance(moments, torch.Tensor) and count.device == self.device
+                  and moments.device == self.device and count.dtype == torch.int32 and moments.dtype == torch.float64
+                  and tuple(count.shape) == (Q,) and tuple(moments.shape) == (5, Q))
+            if not ok:
+                raise ValueError(f"accumulate must be (count, moments): an int32 ({Q},) and a float64 (5, {Q}) tensor on {self.device}")
+        if knots is not None and not (isinstance(knots, torch.Tensor) and knots.dtype == torch.float64 and knots.device == self.device
+                                      and tuple(knots.shape) == (N + 1, B)):
+            raise ValueError(f"knots must be the float64 ({N + 1}, {B}) tensor a previous call on this batch returned")
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            # an index that does not fit 32 bits stays outside [0, B)
+            qt = qtrack.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+            tq = qtime.to(self.device).contiguous()
+            perm = None
+            if sort and Q > 1:
+                by_time = torch.sort(tq, stable=True).indices
+                perm = by_time[torch.sort(qt[by_time], stable=True).indices]
+                qt, tq = qt[perm].contiguous(), tq[perm].contiguous()
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, qt, tq]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B and knots is None:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            po = binding.StePositionsF64()
+            po.nstates, po.flags, po.states = S, 0, states.data_ptr()
+            po.nqueries, po.qtrack, po.qtime = Q, qt.data_ptr(), tq.data_ptr()
+            if t0 is not None:
+                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
+                if tv.dim() == 0:
+                    tv = tv.expand(B)
+                if tuple(tv.shape) != (B,):
+                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+                clock = torch.zeros((width,), **f64)
+                clock[col:col + B] = tv
+                po.t0 = clock.data_ptr() + 8 * col
+                keep.append(clock)
+            if knots is not None and knots.stride() == (width, 1):
+                kn = knots  # the view a call of the same kind returned: read where it lies
+                po.knots = kn.data_ptr()
+            else:
+                ws = torch.empty((N + 1, width), **f64)
+                kn = ws[:, col:col + B]
+                if knots is not None:
+                    kn.copy_(knots)
+                po.knots = ws.data_ptr() + 8 * col
+                keep.append(ws)
+            if knots is not None:
+                po.flags = binding.STE_POS_REUSE_KNOTS
+            keep.append(kn)
+            names = ("lon", "lat", "speed", "heading") if velocity else ("lon", "lat")
+            out = {k: torch.empty((S, Q), **f64) for k in names}
+            out.update(step=torch.empty((Q,), **i32), frac=torch.empty((Q,), **f64), status=torch.empty((Q,), **i32))
+            for k, ten in out.items():
+                setattr(po, k, ten.data_ptr())
+            cnt = mom = None
+            if anchor is not None:
+                an = anchor.to(self.device)
+                an = (an if perm is None else an[:, perm]).contiguous()
+                if accumulate is None:
+                    cnt, mom = torch.zeros((Q,), **i32), torch.zeros((5, Q), **f64)
+                elif perm is None:
+                    cnt, mom = accumulate[0].contiguous(), accumulate[1].contiguous()
+                else:
+                    cnt, mom = accumulate[0][perm].contiguous(), accumulate[1][:, perm].contiguous()
+                po.anchor, po.count, po.moments = an.data_ptr(), cnt.data_ptr(), mom.data_ptr()
+                keep += [an, cnt, mom]
+            binding.check(self.lib.ste_track_positions_f64(C.byref(s), C.byref(po), self._stream(st)), "ste_track_positions_f64")
+            if perm is not None:  # back to the caller's order
+                inv = torch.empty_like(perm)
+                inv[perm] = torch.arange(Q, device=self.device)
+                out = {k: v[..., inv].contiguous() for k, v in out.items()}
+                if cnt is not None:
+                    cnt, mom = cnt[inv].contiguous(), mom[:, inv].contiguous()
+                keep += [perm, inv]
+            if cnt is not None:
+                if accumulate is not None:
+                    if cnt.data_ptr() != accumulate[0].data_ptr():
+                        accumulate[0].copy_(cnt)
+                    if mom.data_ptr() != accumulate[1].data_ptr():
+                        accumulate[1].copy_(mom)
+                    cnt, mom = accumulate
+                out["count"], out["moments"] = cnt, mom
+            out["knots"] = kn
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2544,6 +2703,105 @@ def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 
                     "nwithin": nw, "encounter_prob": (nw > 0).mean(axis=0),
                     "first_within": host["first_within"],
                     "first_within_quantiles": np.nanquantile(host["first_within"], q, axis=0)})
+    out["sample_status"] = status.cpu().numpy()
+    return out
+
+
+KM_PER_DEG = 6378.137 * np.pi / 180.0  # Kd: km per degree of a great circle on the sphere of the leg functions
+
+
+def position_ellipse(count, moments, anchor_lat, prob: float = 0.95):
+    """Mean offset, covariance and error ellipse in km from the moments of ``DeviceBatch.positions_at``: NumPy on (Q,) arrays.
+    ``count`` (Q,), ``moments`` (5, Q) = sums of dx, dy, dx dx, dx dy, dy dy in degrees about the anchor, ``anchor_lat`` (Q,)
+    degrees.  East is dx times Kd cos(anchor lat) and north dy times Kd, Kd = 6378.137 pi / 180.  Returns a dict:
+    ``mean_east_km``, ``mean_north_km`` (NaN where count is 0); ``cov_km`` (Q, 2, 2), ddof = 1, NaN where count < 2;
+    ``semi_major_km``, ``semi_minor_km``, the square roots of the eigenvalues of ``cov_km`` times sqrt(-2 ln(1 - prob)) -- the
+    ellipse that holds ``prob`` of a bivariate normal -- and ``orientation_deg`` in [0, 180), the major axis clockwise from
+    north."""
+    prob = float(prob)
+    if not 0.0 < prob < 1.0:
+        raise ValueError(f"prob must lie strictly between 0 and 1, got {prob!r}")
+    n = np.asarray(count, dtype=np.float64)
+    m = np.asarray(moments, dtype=np.float64)
+    lat = np.asarray(anchor_lat, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != 5 or n.shape != m.shape[1:] or lat.shape != n.shape:
+        raise ValueError(f"count (Q,), moments (5, Q) and anchor_lat (Q,) are wanted, got {n.shape}, {m.shape} and {lat.shape}")
+    ke, kn = KM_PER_DEG * np.cos(np.radians(lat)), KM_PER_DEG
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mx, my = m[0] / n, m[1] / n
+        dof = np.where(n >= 2, n - 1.0, np.nan)
+        cxx, cxy, cyy = (m[2] - m[0] * mx) / dof, (m[3] - m[0] * my) / dof, (m[4] - m[1] * my) / dof
+        a, b, c = cxx * ke * ke, cxy * ke * kn, cyy * kn * kn
+        half, mid = np.hypot(0.5 * (a - c), b), 0.5 * (a + c)
+        scale = np.sqrt(-2.0 * np.log1p(-prob))
+        major, minor = scale * np.sqrt(np.maximum(mid + half, 0.0)), scale * np.sqrt(np.maximum(mid - half, 0.0))
+        # the major axis makes 0.5 atan2(2 b, a - c) with east, counter-clockwise: 90 degrees minus that from north, clockwise
+        orient = np.where(np.isnan(half), np.nan, (90.0 - 0.5 * np.degrees(np.arctan2(2.0 * b, a - c))) % 180.0)
+    cov = np.stack([np.stack([a, b], axis=-1), np.stack([b, c], axis=-1)], axis=-2)
+    return {"mean_east_km": mx * ke, "mean_north_km": my * kn, "cov_km": cov, "semi_major_km": major, "semi_minor_km": minor,
+            "orientation_deg": orient}
+
+
+def position_statistics(hb_or_db, qtrack, qtime, nsamples: int, seed: int = 0, chunk: int = 16, t0=None, prob: float = 0.95,
+                        device="cuda:0"):
+    """Position at given clock times with the uncertainty of the smoothing posterior, per query: ``nsamples`` posterior tracks
+    are drawn (``DeviceBatch.sample_smoothed``), interpolated (``DeviceBatch.positions_at``) and discarded, ``chunk`` samples at
+    a time, with the generator discipline of ``region_statistics``: one draw buffer refilled from one generator, so the draws
+    depend on ``(seed, chunk)`` and with ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  Only the
+    count and the five moments per query survive a chunk, continued on the device with the bits of one pass, so memory does not
+    grow with ``nsamples``.  The anchor of the moments is the smoothed position, ``positions_at(db.sm_mean, ...)``; the knot
+    times are summed once and reused; the queries are sorted once.  Given a ``HostBatch`` it uploads it and runs the forward pass
+    and the smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``qtrack``,
+    ``qtime`` and ``t0`` as in ``positions_at``.
+
+    Returns a dict of NumPy arrays per query: ``lon``, ``lat``, ``speed``, ``heading``, ``step``, ``frac``, ``status`` of the
+    smoothed track; ``count``, the samples with a finite position; and what ``position_ellipse`` makes of the moments:
+    ``mean_east_km``, ``mean_north_km`` (the samples' mean about the smoothed position), ``cov_km`` (Q, 2, 2),
+    ``semi_major_km``, ``semi_minor_km``, ``orientation_deg`` for ``prob``; and ``sample_status`` (B,), the sampler's
+    STE_STATUS_* bits per track."""
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if not 0.0 < float(prob) < 1.0:
+        raise ValueError(f"prob must lie strictly between 0 and 1, got {prob!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("position_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    smoothed = db.positions_at(db.sm_mean, qtrack, qtime, t0=t0, velocity=True)
+    Q = int(smoothed["status"].shape[0])
+    # the kernel's order once, for every chunk: by (track, time)
+    qt = torch.as_tensor(np.asarray(qtrack) if not isinstance(qtrack, torch.Tensor) else qtrack).to(db.device)
+    tq = torch.as_tensor(qtime, dtype=torch.float64).to(db.device)
+    by_time = torch.sort(tq, stable=True).indices
+    perm = by_time[torch.sort(qt[by_time], stable=True).indices]
+    qt, tq = qt[perm], tq[perm]
+    anchor = torch.stack([smoothed["lon"][0], smoothed["lat"][0]])[:, perm].contiguous()
+    knots = smoothed["knots"]
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    f64 = dict(dtype=torch.float64, device=db.device)
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    acc = (torch.zeros((Q,), dtype=torch.int32, device=db.device), torch.zeros((5, Q), **f64))
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        draws = buf[:n]
+        draws.normal_(generator=gen)
+        db.positions_at(db.sample_smoothed(n, draws=draws), qt, tq, t0=t0, anchor=anchor, accumulate=acc, knots=knots, sort=False)
+        status |= db.sample_status
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(Q, device=db.device)
+    count, moments = acc[0][inv].cpu().numpy(), acc[1][:, inv].cpu().numpy()
+    out = {k: smoothed[k][0].cpu().numpy() for k in ("lon", "lat", "speed", "heading")}
+    out.update({k: smoothed[k].cpu().numpy() for k in ("step", "frac", "status")})
+    out["count"] = count
+    out.update(position_ellipse(count, moments, out["lat"], prob))
     out["sample_status"] = status.cpu().numpy()
     return out
 

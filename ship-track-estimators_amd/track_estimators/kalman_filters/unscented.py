@@ -372,6 +372,44 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return out["hours_mean"]
 
+    def position_at(self, times, n_samples: int = 0, random_state: int = 0):
+        """Where the track ``run`` filtered was at ``times``, hours from its first row
+        (``track_estimators.batch.position_statistics``; no counterpart in the reference, whose callers search and interpolate
+        the history themselves).  A position is linear in time inside a step, a time that is a step time returns that row, and
+        a time before the first or after the last row gives NaN.  ``n_samples == 0``: the smoothed track there, a
+        ``(len(times), 4)`` array of lon, lat, speed, heading.  Otherwise a dict: ``position``, that array, and per time
+        ``count``, ``mean_east_km``, ``mean_north_km``, ``cov_km``, ``semi_major_km``, ``semi_minor_km``, ``orientation_deg``
+        (the 95 % ellipse) from that many tracks drawn from the joint smoothing posterior, those of
+        ``sample_smoothed(n_samples, random_state)``.  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("position_at() reads the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("position_at() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        times = np.atleast_1d(np.asarray(times, dtype=np.float64))
+        if times.ndim != 1 or times.size < 1:
+            raise ValueError(f"times must be a scalar or a one-dimensional array of hours, got shape {times.shape}")
+        track = np.zeros(times.size, dtype=np.int32)
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            got = db.positions_at(db.sm_mean, track, times, velocity=True)
+            return np.stack([got[k][0].cpu().numpy() for k in ("lon", "lat", "speed", "heading")], axis=1)
+        out = _batch.position_statistics(hb, track, times, n_samples, seed=int(random_state), chunk=n_samples)
+        self._status_sampler = int(out["sample_status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        res = {"position": np.stack([out[k] for k in ("lon", "lat", "speed", "heading")], axis=1)}
+        res.update({k: out[k] for k in ("count", "mean_east_km", "mean_north_km", "cov_km", "semi_major_km", "semi_minor_km",
+                                        "orientation_deg")})
+        return res
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
