@@ -25,6 +25,8 @@
  *   ste_encounter_metrics_f64  closest approach and time within a radius of pairs of such tracks (no counterpart in the reference)
  *   ste_track_positions_f64  position, speed and heading of such tracks at given clock times, and the moments of the positions over
  *                            the samples for an error ellipse (no counterpart in the reference: a download, a search and a host loop)
+ *   ste_site_metrics_f64     closest approach and time within a radius of such tracks at fixed sites (ports), a dense (sample, site,
+ *                            track) block (no counterpart in the reference)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -61,7 +63,8 @@ extern "C" {
                            (ste_region_metrics_f64).  Unnumbered addition: tracks on the device on a lon / lat grid
                            (ste_grid_metrics_f64).  Unnumbered addition: pairs of tracks on the device against each other
                            (ste_encounter_metrics_f64).  Unnumbered addition: tracks on the device at given clock times
-                           (ste_track_positions_f64).
+                           (ste_track_positions_f64).  Unnumbered addition: tracks on the device against fixed sites
+                           (ste_site_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -658,6 +661,88 @@ typedef struct ste_positions_f64 {
 } ste_positions_f64;        /* 136 bytes */
 
 int ste_track_positions_f64(const ste_ukf_batch_f64* b, const ste_positions_f64* po, void* stream);
+
+/*
+ * SITES: tracks that stay on the device against FIXED POINTS (an unnumbered addition, like ste_positions_f64): how close every
+ * ship came to every one of M sites (ports, anchorages, buoys, stations, wrecks) and when, and for how long, from when, how
+ * often and for how long at a stretch it was within the site's own radius.  `states` is that of ste_path_f64.  A site is a ship
+ * that does not move and has no clock: every rule below is the rule of ste_encounter_f64 specialised to that, so an encounter
+ * call with one stationary one-step ship per site whose step spans every clock gives the same bits wherever no step has zero
+ * length (tests/test_site_metrics.py holds the two against each other).  A position is linear in time inside a step, in planar
+ * (lon, lat), and a step is broken by the rule of ste_region_f64.  Below clamp01(x) = x < 0 ? 0 : (x > 1 ? 1 : x),
+ * max(x, y) = x > y ? x : y, min(x, y) = x < y ? x : y, wrap180 is that of ste_path_f64, and every expression is evaluated as
+ * written, left to right, without contraction.
+ *   - Clock.  Track t has knots tau_k = t0[t] + T_k, T_0 = 0, T_{k+1} = T_k + dt_k summed in order; the single addition of t0 is
+ *     made at use.  t0 NULL is 0 for every track.
+ *   - Bad clock.  A track's clock is bad when t0[t] is not finite or when some dt_k, k < nsteps[t], is not finite or is negative.
+ *     A bad clock sets STE_SITE_BAD_TIME in track_status[t] and gives min_dist, min_time and first_within = NaN and zero for
+ *     every other output, for every site and sample of that track (sound_time and nbroken too).
+ *   - Pieces.  Step k of track t, k < nsteps[t], is the PIECE (lo, hi) = (tau_k, tau_{k+1}).  It is examined when hi > lo: a
+ *     step of zero length is skipped.  Pieces are examined in the order of k, which defines "first" below.
+ *   - Soundness.  delta = wrap180(lon_{k+1} - lon_k).  The step is BROKEN when |delta| < 90 is false or either of its latitudes
+ *     is not finite.  A broken examined step adds 1 to nbroken and nothing else, and closes every open run.  Every other
+ *     examined step is SOUND.  sound_time is the sum of hi - lo over the sound examined steps, in order.
+ *   - Bad site.  A site is bad when its lon or lat is not finite, or when its radius is not finite, is < 0 or is
+ *     > STE_ENCOUNTER_MAX_RADIUS_KM.  A bad site sets STE_SITE_BAD_SITE in site_status[m] and gives min_dist, min_time and
+ *     first_within = NaN and zero for time_within, longest and nwithin, for every track and sample.
+ *   - Relative motion on a sound step, for the site (X, Y) with radius R.  x0 = lon_k, y0 = lat_k, x1 = x0 + delta,
+ *     y1 = lat_{k+1}.  gx0 = wrap180(X - x0), gy0 = Y - y0, gx1 = gx0 - (x1 - x0) (continuous, never re-wrapped), gy1 = Y - y1.
+ *     c = cos(0.25 * ((y0 + y1) + (Y + Y)) * kDeg2Rad), Kd = 6378.137 * kDeg2Rad (one double), kc = Kd * c.  r0 = (kc * gx0,
+ *     Kd * gy0), r1 = (kc * gx1, Kd * gy1), d = r1 - r0, dd = d.x * d.x + d.y * d.y, bq = r0.x * d.x + r0.y * d.y,
+ *     r00 = r0.x * r0.x + r0.y * r0.y.  cos is the only operation here whose bits may differ between implementations.
+ *   - Closest approach.  u* = dd > 0 ? clamp01(-bq / dd) : 0, m = (r0.x + u* * d.x, r0.y + u* * d.y), q = m.x * m.x + m.y * m.y.
+ *     The piece becomes the best one when q < best_q (best_q starts at +inf; strict, so the first piece wins a tie).  It then
+ *     records min_time = lo + u* * (hi - lo) and the ship's position (x0 + u* * (x1 - x0), y0 + u* * (y1 - y0)).  After the last
+ *     step min_dist is the leg of ste_path_metrics_f64 for `model` from that position to (X, Y): the leg function runs once per
+ *     (sample, site, track).  Without a best piece min_dist and min_time are NaN.
+ *   - Within R.  If dd > 0: disc = bq * bq - dd * (r00 - R * R), and if disc >= 0: sq = sqrt(disc), ua = max((-bq - sq) / dd, 0),
+ *     ub = min((-bq + sq) / dd, 1).  If dd == 0: ua = 0, ub = 1 iff r00 <= R * R.  Otherwise there is no interval.  If ub > ua:
+ *     time_within += (ub - ua) * (hi - lo); a new RUN starts unless the run is open and ua == 0; a new run adds 1 to nwithin and
+ *     the first one sets first_within = lo + ua * (hi - lo); after that the run is open iff ub == 1.  The length of a run is the
+ *     sum of (ub - ua) * (hi - lo) over its pieces, in order; longest is the largest length of a run, 0 without one.  A piece
+ *     without an interval, a broken piece, a skipped piece (hi > lo false) and the end of the track close the run.  No
+ *     tolerance anywhere.  (Only the skipped piece departs from ste_encounter_f64, whose walk passes over it with the run open.)
+ *   - Accuracy.  That of ste_encounter_f64: the planar metric is for a ship near the site, min_dist is a true distance (of
+ *     `model`) at the time the planar distance is least, the within-R outputs are planar, hence the limit on the radius.
+ *   - Every value's bits depend on the track's rows, its dt and t0, and the site's three numbers alone: not on S, M, the site's
+ *     place in the list, the window, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64, t0 and track_status like nsteps.  Rows past nsteps[t]
+ *     of states are not read.  Outputs per (sample, site, track) are out[(s * M + m) * track_stride + t]; sound_time and nbroken
+ *     out[s * track_stride + t] (track_stride = B where it is 0).
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or si NULL; states, sites or radius_km NULL;
+ *     nstates < 1 or > 65535; nsites < 1 or > STE_SITES_MAX; an unknown model when min_dist is asked for; flags or reserved
+ *     non-zero; b->dt NULL; every output NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B; and a call whose
+ *     ceil(B / 64) * ceil(nsites / ste_site_tile()) exceeds 2^31 - 1.
+ */
+#define STE_SITES_MAX 65536
+#define STE_SITE_BAD_TIME 0x1  /* track_status: a non-finite t0, or a dt below nsteps that is not finite and >= 0 */
+#define STE_SITE_BAD_SITE 0x1  /* site_status: a non-finite lon or lat, or a radius that is not finite, < 0 or above the limit */
+typedef struct ste_site_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;           /* STE_PREP_SPHERE / STE_PREP_WGS84: leg function for min_dist only */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 */
+    int32_t nsites;          /* M, 1 .. STE_SITES_MAX (four bytes of padding follow) */
+    const double* sites;     /* DEVICE [2][M]: lon[0..M) then lat[0..M), degrees */
+    const double* radius_km; /* DEVICE [M]: R per site, finite, 0 <= R <= STE_ENCOUNTER_MAX_RADIUS_KM, else the site is bad */
+    const double* t0;        /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track, as ste_encounter_f64 */
+    uint32_t flags;          /* must be 0 */
+    uint32_t reserved;       /* must be 0 */
+    double* min_dist;        /* DEVICE [S][M][track_stride] or NULL: km at the closest approach, NaN = no sound piece */
+    double* min_time;        /* DEVICE [S][M][track_stride] or NULL: its clock time, hours; NaN likewise */
+    double* time_within;     /* DEVICE [S][M][track_stride] or NULL: hours with planar distance <= R */
+    double* first_within;    /* DEVICE [S][M][track_stride] or NULL: clock time at which the first run within R starts, NaN = none */
+    double* longest;         /* DEVICE [S][M][track_stride] or NULL: hours of the longest run within R, 0 = none */
+    int32_t* nwithin;        /* DEVICE [S][M][track_stride] or NULL: runs within R */
+    double* sound_time;      /* DEVICE [S][track_stride] or NULL: hours of sound steps */
+    int32_t* nbroken;        /* DEVICE [S][track_stride] or NULL: broken examined steps */
+    int32_t* track_status;   /* DEVICE [track_stride] or NULL: STE_SITE_BAD_TIME (does not depend on the sample or the site) */
+    int32_t* site_status;    /* DEVICE [M] or NULL: STE_SITE_BAD_SITE */
+} ste_site_f64;              /* 136 bytes */
+
+int ste_site_metrics_f64(const ste_ukf_batch_f64* b, const ste_site_f64* si, void* stream);
+/* sites a wave holds in registers; M at and around its multiples is where the tiling of the sites shows */
+int ste_site_tile(void);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -253,6 +253,37 @@ class StePositionsF64(C.Structure):
     ]
 
 
+STE_SITES_MAX = 65536
+STE_SITE_BAD_TIME = 0x1
+STE_SITE_BAD_SITE = 0x1
+
+
+class SteSiteF64(C.Structure):
+    """Mirror of ``struct ste_site_f64`` (include/ste.h): tracks on the device against fixed sites."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("nsites", C.c_int32),
+        ("sites", _dp),
+        ("radius_km", _dp),
+        ("t0", _dp),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("min_dist", _dp),
+        ("min_time", _dp),
+        ("time_within", _dp),
+        ("first_within", _dp),
+        ("longest", _dp),
+        ("nwithin", _dp),
+        ("sound_time", _dp),
+        ("nbroken", _dp),
+        ("track_status", _dp),
+        ("site_status", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -365,6 +396,8 @@ SYMBOLS = {
     "ste_grid_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteGridF64), C.c_void_p]),
     "ste_encounter_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteEncounterF64), C.c_void_p]),
     "ste_track_positions_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePositionsF64), C.c_void_p]),
+    "ste_site_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSiteF64), C.c_void_p]),
+    "ste_site_tile": (C.c_int, []),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1269,6 +1269,104 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- fixed sites ----------------------------------------------------------------------------------------------
+    _SITE_OUT3 = ("min_dist", "min_time", "time_within", "first_within", "longest")
+
+    def site_metrics(self, states, sites, radius_km, t0=None, model: str = "sphere", stream=None):
+        """Tracks that are on the device against fixed sites -- ports, anchorages, buoys -- (include/ste.h:
+        ste_site_metrics_f64; DESIGN.md, "Sites"): every ship against every site, a dense block.  ``states`` as in
+        ``path_metrics``.  ``sites``: an (M, 2) array or tensor of (lon, lat) in degrees, 1 <= M <= 65536.  ``radius_km``: a
+        scalar or one radius per site, (M,).  ``t0`` and ``model`` as in ``encounter_metrics``.  Returns a dict of device
+        tensors: ``min_dist`` (S, M, B) in km, NaN where the track has no sound step; ``min_time``, its clock time;
+        ``time_within``, hours with the planar distance <= the site's radius; ``first_within``, the clock time the first such
+        run starts, NaN = never; ``longest``, the hours of the longest run; ``nwithin`` int32, the number of runs;
+        ``sound_time`` (S, B), the hours of sound steps, and ``nbroken`` (S, B) int32, the steps left out (a NaN latitude, or 90
+        degrees of longitude or more in one step); ``track_status`` (B,) int32, STE_SITE_BAD_TIME (a non-finite ``t0``, a ``dt``
+        that is not finite and >= 0), and ``site_status`` (M,) int32, STE_SITE_BAD_SITE (a non-finite coordinate, or a radius
+        that is not finite and between 0 and 1000): neither is refused, a bad track or site gives NaN / 0.  Windows, in-place
+        views and ``stream`` as in ``path_metrics``; for a window read in place the per-track outputs are views of rows as
+        wide as the fleet's.  Every value depends on the track's rows, ``dt``, ``t0`` and the site's three numbers alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        sv = torch.as_tensor(sites, dtype=torch.float64)
+        if sv.dim() != 2 or sv.shape[1] != 2 or not 1 <= sv.shape[0] <= binding.STE_SITES_MAX:
+            raise ValueError(f"sites must have shape (M, 2) (lon, lat) with 1 <= M <= {binding.STE_SITES_MAX}, got {tuple(sv.shape)}")
+        S, M = int(states.shape[0]), int(sv.shape[0])
+        rv = torch.as_tensor(radius_km, dtype=torch.float64)
+        if rv.dim() == 0:
+            rv = rv.expand(M)
+        if tuple(rv.shape) != (M,):
+            raise ValueError(f"radius_km must be a scalar or have shape ({M},), got {tuple(rv.shape)}")
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            xy = sv.to(self.device).t().contiguous()  # [2][M]: lon then lat
+            rad = rv.to(self.device).contiguous()
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, xy, rad]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            si = binding.SteSiteF64()
+            si.nstates, si.model, si.states = S, self._PATH_MODELS[model], states.data_ptr()
+            si.nsites, si.sites, si.radius_km, si.flags, si.reserved = M, xy.data_ptr(), rad.data_ptr(), 0, 0
+            if t0 is not None:
+                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
+                if tv.dim() == 0:
+                    tv = tv.expand(B)
+                if tuple(tv.shape) != (B,):
+                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+                clock = torch.zeros((width,), **f64)
+                clock[col:col + B] = tv
+                si.t0 = clock.data_ptr() + 8 * col
+                keep.append(clock)
+            # rows as wide as the states': the window's columns are what the call writes and what is returned
+            full = {k: torch.empty((S, M, width), **f64) for k in self._SITE_OUT3}
+            full["nwithin"] = torch.empty((S, M, width), **i32)
+            full["sound_time"] = torch.empty((S, width), **f64)
+            full["nbroken"] = torch.empty((S, width), **i32)
+            full["track_status"] = torch.empty((width,), **i32)
+            for k, ten in full.items():
+                setattr(si, k, ten.data_ptr() + ten.element_size() * col)
+            out = {k: ten[..., col:col + B] for k, ten in full.items()}
+            out["site_status"] = torch.empty((M,), **i32)
+            si.site_status = out["site_status"].data_ptr()
+            binding.check(self.lib.ste_site_metrics_f64(C.byref(s), C.byref(si), self._stream(st)), "ste_site_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2703,6 +2801,118 @@ def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 
                     "nwithin": nw, "encounter_prob": (nw > 0).mean(axis=0),
                     "first_within": host["first_within"],
                     "first_within_quantiles": np.nanquantile(host["first_within"], q, axis=0)})
+    out["sample_status"] = status.cpu().numpy()
+    return out
+
+
+def nearest_site(min_dist):
+    """The closest site per (sample, track) from the ``min_dist`` (S, M, B) of ``DeviceBatch.site_metrics``: torch on the
+    tensor's own device, no kernel of this library.  Returns ``(index, distance)``, (S, B) each: the index of the smallest
+    distance that is not NaN (the first of equal ones) as int64 and that distance in km; -1 and NaN where every site's is NaN
+    (a track without a sound step, a bad clock, bad sites only)."""
+    import torch
+
+    if min_dist.dim() != 3:
+        raise ValueError(f"min_dist must have shape (S, M, B), got {tuple(min_dist.shape)}")
+    nan = torch.isnan(min_dist)
+    dist, index = torch.where(nan, torch.full_like(min_dist, float("inf")), min_dist).min(dim=1)
+    none = nan.all(dim=1)
+    return torch.where(none, torch.full_like(index, -1), index), torch.where(none, torch.full_like(dist, float("nan")), dist)
+
+
+def site_statistics(hb_or_db, sites, radius_km, nsamples: int, seed: int = 0, chunk: int = 16, min_stay_h: float = 0.0,
+                    quantiles=None, max_bytes: int = 2 ** 31, t0=None, model: str = "sphere", draws=None, device="cuda:0"):
+    """Which ships called at which sites, with the uncertainty of the smoothing posterior: ``nsamples`` posterior tracks per
+    ship are drawn (``DeviceBatch.sample_smoothed``), held against every site (``DeviceBatch.site_metrics``) and discarded,
+    ``chunk`` samples at a time, with the generator discipline of ``region_statistics``: one draw buffer refilled from one
+    generator, so the draws depend on ``(seed, chunk)`` and with ``chunk >= nsamples`` they are those of
+    ``sample_smoothed(nsamples, seed)``.  What is kept between chunks are counts and sums per (site, track) on the device,
+    added to sample by sample in sample order: memory does not grow with ``nsamples``, and for given draws the result does not
+    depend on ``chunk``, bit for bit.  ``draws``: None, or a callable ``draws(buf, first)`` that fills the (n, Nmax+1, 4, B)
+    float64 device tensor ``buf`` with the standard normal draws of samples ``first .. first + n`` in place of the generator
+    (zeros give the smoothed track n times over).  Given a ``HostBatch`` it uploads it and runs the forward pass and the
+    smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``sites``, ``radius_km``,
+    ``t0`` and ``model`` as in ``site_metrics``.
+
+    Returns a dict of NumPy arrays per (site, track), (M, B): ``min_dist_smoothed``, ``min_time_smoothed``,
+    ``time_within_smoothed``, ``first_within_smoothed``, ``longest_smoothed``, ``nwithin_smoothed``, of the smoothed tracks
+    ``sm_mean``; ``visit_prob``, the fraction of samples that come within the site's radius (``nwithin`` > 0); ``call_prob``,
+    the fraction whose longest stay is at least ``min_stay_h`` hours and that come within at all; ``min_dist_mean`` over the
+    samples that have a distance (NaN where none has) with their number ``min_dist_count``; ``time_within_mean`` and
+    ``longest_mean`` over all samples; ``track_status`` (B,), ``site_status`` (M,) and ``sample_status`` (B,), the
+    sampler's STE_STATUS_* bits.  With ``quantiles`` (a sequence of probabilities) also ``min_dist_quantiles``,
+    ``time_within_quantiles`` and ``longest_quantiles`` (len(quantiles), M, B): these keep every sample's value, nsamples x M x
+    B doubles per quantity, and are refused when that exceeds ``max_bytes``."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("site_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    M = int(np.shape(sites)[0]) if not isinstance(sites, torch.Tensor) else int(sites.shape[0])
+    qnames = ("min_dist", "time_within", "longest")
+    if quantiles is not None:
+        need = 8 * nsamples * M * B
+        if need > int(max_bytes):
+            raise ValueError(f"quantiles keep nsamples x M x B = {nsamples} x {M} x {B} doubles per quantity, {need} bytes, above "
+                             f"max_bytes = {int(max_bytes)}: lower nsamples, split the sites, raise max_bytes or pass quantiles=None")
+    kw = dict(t0=t0, model=model)
+    smoothed = db.site_metrics(db.sm_mean, sites, radius_km, **kw)
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    f64 = dict(dtype=torch.float64, device=db.device)
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    visits, calls, have = (torch.zeros((M, B), dtype=torch.int32, device=db.device) for _ in range(3))
+    sums = {k: torch.zeros((M, B), **f64) for k in qnames}
+    kept = {k: torch.empty((nsamples, M, B), **f64) for k in qnames} if quantiles is not None else None
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    stay = float(min_stay_h)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        z = buf[:n]
+        if draws is None:
+            z.normal_(generator=gen)
+        else:
+            draws(z, i)
+        m = db.site_metrics(db.sample_smoothed(n, draws=z), sites, radius_km, **kw)
+        came = m["nwithin"] > 0
+        found = ~torch.isnan(m["min_dist"])
+        dist = torch.where(found, m["min_dist"], torch.zeros_like(m["min_dist"]))
+        for s in range(n):  # sample by sample: the sums take their terms in sample order whatever the chunk
+            visits += came[s]
+            calls += came[s] & (m["longest"][s] >= stay)
+            have += found[s]
+            sums["min_dist"] += dist[s]
+            sums["time_within"] += m["time_within"][s]
+            sums["longest"] += m["longest"][s]
+        if kept is not None:
+            for k in qnames:
+                kept[k][i:i + n] = m[k]
+        status |= db.sample_status
+    out = {k + "_smoothed": smoothed[k][0].cpu().numpy() for k in DeviceBatch._SITE_OUT3 + ("nwithin",)}
+    count = have.cpu().numpy()
+    out["visit_prob"] = visits.cpu().numpy() / float(nsamples)
+    out["call_prob"] = calls.cpu().numpy() / float(nsamples)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["min_dist_mean"] = np.where(count > 0, sums["min_dist"].cpu().numpy() / count, np.nan)
+    out["min_dist_count"] = count
+    out["time_within_mean"] = sums["time_within"].cpu().numpy() / float(nsamples)
+    out["longest_mean"] = sums["longest"].cpu().numpy() / float(nsamples)
+    if kept is not None:
+        q = np.asarray(quantiles, dtype=np.float64)
+        with warnings.catch_warnings():  # a (site, track) no sample gives a distance: all-NaN column, NaN out
+            warnings.simplefilter("ignore", RuntimeWarning)
+            for k in qnames:
+                out[k + "_quantiles"] = np.nanquantile(kept[k].cpu().numpy(), q, axis=0)
+    out["track_status"], out["site_status"] = smoothed["track_status"].cpu().numpy(), smoothed["site_status"].cpu().numpy()
     out["sample_status"] = status.cpu().numpy()
     return out
 

@@ -410,6 +410,45 @@ class UnscentedKalmanFilter(KalmanFilterBase):
                                         "orientation_deg")})
         return res
 
+    def site_visits(self, sites, radius_km, nsamples: int = 0, min_stay_h: float = 0.0, model: str = "sphere",
+                    random_state: int = 0):
+        """The track ``run`` filtered against fixed sites -- ports, anchorages, buoys -- (``DeviceBatch.site_metrics`` and
+        ``track_estimators.batch.site_statistics``; no counterpart in the reference).  ``sites``: (M, 2) lon / lat in
+        degrees; ``radius_km``: a scalar or one radius per site; times are hours from the first row.  ``nsamples == 0``: a
+        dict of (M,) arrays of the smoothed track, ``min_dist`` (km), ``min_time``, ``time_within``, ``first_within``,
+        ``longest``, ``nwithin``, and ``nearest``, the index of the closest site (-1 without one).  Otherwise those under
+        ``*_smoothed`` names and per site ``visit_prob`` (the fraction of that many tracks drawn from the joint smoothing
+        posterior that come within the radius), ``call_prob`` (that stay ``min_stay_h`` or longer at a stretch) and the means
+        ``min_dist_mean``, ``time_within_mean``, ``longest_mean``.  The track is packed as ``run`` packed it, as for
+        ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("site_visits() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("site_visits() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        nsamples = int(nsamples)
+        if nsamples < 0:
+            raise ValueError(f"nsamples must be >= 0, got {nsamples!r}")
+        names = ("min_dist", "min_time", "time_within", "first_within", "longest", "nwithin")
+        if nsamples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            got = db.site_metrics(db.sm_mean, sites, radius_km, model=model)
+            res = {k: got[k][0, :, 0].cpu().numpy() for k in names}
+            res["nearest"] = int(_batch.nearest_site(got["min_dist"])[0][0, 0].item())
+            return res
+        out = _batch.site_statistics(hb, sites, radius_km, nsamples, seed=int(random_state), chunk=nsamples,
+                                     min_stay_h=min_stay_h, model=model)
+        self._status_sampler = int(out["sample_status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        res = {k + "_smoothed": out[k + "_smoothed"][:, 0] for k in names}
+        res.update({k: out[k][:, 0] for k in ("visit_prob", "call_prob", "min_dist_mean", "time_within_mean", "longest_mean")})
+        return res
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
