@@ -27,6 +27,8 @@
  *                            the samples for an error ellipse (no counterpart in the reference: a download, a search and a host loop)
  *   ste_site_metrics_f64     closest approach and time within a radius of such tracks at fixed sites (ports), a dense (sample, site,
  *                            track) block (no counterpart in the reference)
+ *   ste_line_metrics_f64     closest approach and crossings of such tracks at polylines (coasts, cables, gates), a dense (sample,
+ *                            line, track) block (no counterpart in the reference)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -64,7 +66,8 @@ extern "C" {
                            (ste_grid_metrics_f64).  Unnumbered addition: pairs of tracks on the device against each other
                            (ste_encounter_metrics_f64).  Unnumbered addition: tracks on the device at given clock times
                            (ste_track_positions_f64).  Unnumbered addition: tracks on the device against fixed sites
-                           (ste_site_metrics_f64).
+                           (ste_site_metrics_f64).  Unnumbered addition: tracks on the device against polylines
+                           (ste_line_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -743,6 +746,109 @@ typedef struct ste_site_f64 {
 int ste_site_metrics_f64(const ste_ukf_batch_f64* b, const ste_site_f64* si, void* stream);
 /* sites a wave holds in registers; M at and around its multiples is where the tiling of the sites shows */
 int ste_site_tile(void);
+
+/*
+ * LINES: tracks that stay on the device against FIXED POLYLINES (an unnumbered addition, like ste_site_f64): how close every
+ * ship came to every one of M lines (coasts, cables, planned routes, gates) and when, on which segment and where along it, and
+ * how often, in which direction and when it crossed the line.  `states` is that of ste_path_f64, the clock that of
+ * ste_site_f64, the frame that of ste_region_f64 (one per line) and the metric that of ste_site_f64.  The lines are a CSR list:
+ * line m owns vertices first[m] .. first[m+1] - 1 of vert, L = first[m+1] - first[m] - 1 segments; segment j of the line joins
+ * its vertices j and j + 1, P = vertex j and Q = vertex j + 1 below.  A position is linear in time inside a step, in planar
+ * (lon, lat).  Below clamp01(x) = x < 0 ? 0 : (x > 1 ? 1 : x), wrap180 is that of ste_path_f64, a . b = a.x * b.x + a.y * b.y,
+ * and every expression is evaluated as written, left to right, without contraction.
+ *   - Clock.  Track t has knots tau_k = t0[t] + T_k, T_0 = 0, T_{k+1} = T_k + dt_k summed in order; the single addition of t0 is
+ *     made at use.  t0 NULL is 0 for every track.
+ *   - Bad clock.  A track's clock is bad when t0[t] is not finite or when some dt_k, k < nsteps[t], is not finite or is negative.
+ *     A bad clock sets STE_LINE_BAD_TIME in track_status[t] and gives min_dist, min_time, min_frac, first_cross and last_cross
+ *     = NaN, min_seg = -1 and zero for every other output, for every line and sample of that track (sound_time and nbroken too).
+ *   - Pieces.  Step k of track t, k < nsteps[t], is the PIECE (lo, hi) = (tau_k, tau_{k+1}).  It is examined when hi > lo: a
+ *     step of zero length is skipped.  Pieces are examined in the order of k, and within a piece the segments in the order of
+ *     j, which defines "first" below.
+ *   - Soundness.  delta = wrap180(lon_{k+1} - lon_k).  The step is BROKEN when |delta| < 90 is false or either of its latitudes
+ *     is not finite.  A broken examined step adds 1 to nbroken and nothing else.  Every other examined step is SOUND.
+ *     sound_time is the sum of hi - lo over the sound examined steps, in order.
+ *   - Frame of line m, ref = lon_ref[m].  Row k sits at x_k = ref + wrap180(lon_k - ref); the step runs from A = (x_k, lat_k) to
+ *     B = (x_k + delta, lat_{k+1}).  Vertices are used as stored, so adjacent segments share a vertex's bits.  PRECONDITION:
+ *     every vertex longitude of line m lies within ref +- 90; then, as for ste_region_f64, no periodic copy of the line can be
+ *     met by a sound step and stored longitudes of the ships may be wrapped or not.  The library cannot refuse a violation (the
+ *     vertices are device memory): the kernel marks the line bad, the Python front end raises before the call.
+ *   - Bad line.  Line m is bad when first[m+1] - first[m] < 2, when its range leaves [0, V] (first[m] < 0 or first[m+1] > V),
+ *     when lon_ref[m] is not finite, or when any of its vertices has a non-finite coordinate or a longitude with
+ *     |lon - ref| <= 90 false.  A bad line sets STE_LINE_BAD_LINE in line_status[m] and gives min_dist, min_time, min_frac,
+ *     first_cross and last_cross = NaN, min_seg = -1 and zero for ncross and net_cross, for every track and sample.  With a bad
+ *     range nothing of the line is read.
+ *   - Crossing, planar in degrees: the rule of ste_region_f64.  On a sound step, for segment j, with d = B - A, e = Q - P,
+ *     w = P - A:  den = d.x * e.y - d.y * e.x,  u = (w.x * e.y - w.y * e.x) / den,  v = (w.x * d.y - w.y * d.x) / den.  A
+ *     CROSSING exists when den != 0, 0 <= u < 1 and 0 <= v < 1 (so a track through a vertex shared by two segments crosses
+ *     once).  It adds 1 to ncross, and +1 to net_cross when den < 0 and -1 otherwise (for a counter-clockwise ring +1 is
+ *     ste_region_f64's ENTERING); its time is lo + u * (hi - lo).  first_cross is the earliest: of the first step that has a
+ *     crossing, lo + umin * (hi - lo) with umin the smallest u of that step's crossings; last_cross likewise is the latest: of
+ *     the last step that has one, with the largest u.  No crossing is sorted.  Without a crossing both are NaN.
+ *   - Closest approach, planar in km, per (sound step, segment).  c = cos(0.25 * ((A.y + B.y) + (P.y + Q.y)) * kDeg2Rad),
+ *     Kd = 6378.137 * kDeg2Rad (one double), kc = Kd * c.  a0 = (kc * w.x, Kd * w.y), a1 = (kc * (Q.x - A.x), Kd * (Q.y - A.y)),
+ *     dk = (kc * d.x, Kd * d.y), ek = a1 - a0, dd = dk . dk, ee = ek . ek, b0 = a0 - dk.  cos is the only operation here whose
+ *     bits may differ between implementations.  The CANDIDATES, each a (u, v, q) with q the squared norm of the difference
+ *     vector g between the point of the segment at v and the ship's position at u, q = g.x * g.x + g.y * g.y, in this order:
+ *       1. the crossing, when there is one: its (u, v), q = 0;
+ *       2. P against the step: u = dd > 0 ? clamp01((a0 . dk) / dd) : 0, v = 0, g = (a0.x - u * dk.x, a0.y - u * dk.y);
+ *       3. Q against the step: u = dd > 0 ? clamp01((a1 . dk) / dd) : 0, v = 1, g = (a1.x - u * dk.x, a1.y - u * dk.y);
+ *       4. A against the segment: v = ee > 0 ? clamp01(-(a0 . ek) / ee) : 0, u = 0, g = (a0.x + v * ek.x, a0.y + v * ek.y);
+ *       5. B against the segment: v = ee > 0 ? clamp01(-(b0 . ek) / ee) : 0, u = 1, g = (b0.x + v * ek.x, b0.y + v * ek.y).
+ *     A candidate replaces the best one only when its q < best_q (best_q starts at +inf; strict, so the first candidate of the
+ *     first segment of the first step wins a tie).  The best candidate records min_time = lo + u * (hi - lo), the ship's
+ *     position (A.x + u * d.x, A.y + u * d.y), min_seg = j and min_frac = v.  After the last step min_dist is the leg of
+ *     ste_path_metrics_f64 for `model` from that position to (P.x + v * (Q.x - P.x), P.y + v * (Q.y - P.y)) of the recorded
+ *     segment: the leg function runs once per (sample, line, track).  Without a sound step min_dist, min_time and min_frac are
+ *     NaN and min_seg is -1.
+ *   - Accuracy.  That of ste_site_f64: the planar metric is for a ship near the line, and min_dist is a true distance (of
+ *     `model`) between a point of the track and a point of the line, at the time the planar distance is least.  A step and a
+ *     line more than 180 degrees apart in the frame (more than 90 degrees of true longitude between them) are compared in the
+ *     wrong image; the planar metric means nothing there anyway, and min_dist, still a true distance between a point of the
+ *     track and a point of the line, is an upper bound.
+ *   - Every value's bits depend on the track's rows, its dt and t0, and the line's vertices and lon_ref alone: not on S, M, the
+ *     line's place in the list or in vert, the window, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64, t0 and track_status like nsteps.  Rows past nsteps[t]
+ *     of states are not read.  Outputs per (sample, line, track) are out[(s * M + m) * track_stride + t]; sound_time and nbroken
+ *     out[s * track_stride + t] (track_stride = B where it is 0).
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or li NULL; states, vert, first or lon_ref
+ *     NULL; nstates < 1 or > 65535; nlines < 1 or > STE_LINES_MAX; nvert < 2 or > STE_LINE_MAX_VERT_TOTAL; an unknown model when
+ *     min_dist is asked for; flags or reserved non-zero; b->dt NULL; every output NULL; B <= 0, Nmax < 0, or track_stride
+ *     non-zero and below B; and a call whose ceil(B / 64) * nlines exceeds 2^31 - 1.
+ */
+#define STE_LINES_MAX 4096
+#define STE_LINE_MAX_VERT_TOTAL (1 << 20)
+#define STE_LINE_BAD_TIME 0x1  /* track_status: a non-finite t0, or a dt below nsteps that is not finite and >= 0 */
+#define STE_LINE_BAD_LINE 0x1  /* line_status: fewer than 2 vertices, a range outside vert, a non-finite lon_ref or vertex, a vertex outside lon_ref +- 90 */
+typedef struct ste_line_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;           /* STE_PREP_SPHERE / STE_PREP_WGS84: leg function for min_dist only */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 */
+    int32_t nlines;          /* M, 1 .. STE_LINES_MAX */
+    int32_t nvert;           /* V, 2 .. STE_LINE_MAX_VERT_TOTAL: vertices of all lines together */
+    const double* vert;      /* DEVICE [2][V]: lon[0..V) then lat[0..V), degrees */
+    const int32_t* first;    /* DEVICE [M+1]: line m owns vertices first[m] .. first[m+1] - 1 */
+    const double* lon_ref;   /* DEVICE [M]: the meridian line m is unwrapped about */
+    const double* t0;        /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track, as ste_site_f64 */
+    uint32_t flags;          /* must be 0 */
+    uint32_t reserved;       /* must be 0 */
+    double* min_dist;        /* DEVICE [S][M][track_stride] or NULL: km at the closest approach, NaN = no sound step */
+    double* min_time;        /* DEVICE [S][M][track_stride] or NULL: its clock time, hours; NaN likewise */
+    int32_t* min_seg;        /* DEVICE [S][M][track_stride] or NULL: segment of the line that is closest, -1 = none */
+    double* min_frac;        /* DEVICE [S][M][track_stride] or NULL: v on that segment, 0 at its first vertex, 1 at its second; NaN = none */
+    int32_t* ncross;         /* DEVICE [S][M][track_stride] or NULL: crossings */
+    int32_t* net_cross;      /* DEVICE [S][M][track_stride] or NULL: crossings with den < 0 minus the others */
+    double* first_cross;     /* DEVICE [S][M][track_stride] or NULL: clock time of the earliest crossing, NaN = none */
+    double* last_cross;      /* DEVICE [S][M][track_stride] or NULL: clock time of the latest crossing, NaN = none */
+    double* sound_time;      /* DEVICE [S][track_stride] or NULL: hours of sound steps */
+    int32_t* nbroken;        /* DEVICE [S][track_stride] or NULL: broken examined steps */
+    int32_t* track_status;   /* DEVICE [track_stride] or NULL: STE_LINE_BAD_TIME (does not depend on the sample or the line) */
+    int32_t* line_status;    /* DEVICE [M] or NULL: STE_LINE_BAD_LINE */
+} ste_line_f64;              /* 160 bytes */
+
+int ste_line_metrics_f64(const ste_ukf_batch_f64* b, const ste_line_f64* li, void* stream);
+/* segments of a line the kernel stages at a time; line lengths at and around its multiples are where the staging shows */
+int ste_line_chunk(void);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -284,6 +284,42 @@ class SteSiteF64(C.Structure):
     ]
 
 
+STE_LINES_MAX = 4096
+STE_LINE_MAX_VERT_TOTAL = 1 << 20
+STE_LINE_BAD_TIME = 0x1
+STE_LINE_BAD_LINE = 0x1
+
+
+class SteLineF64(C.Structure):
+    """Mirror of ``struct ste_line_f64`` (include/ste.h): tracks on the device against polylines."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("nlines", C.c_int32),
+        ("nvert", C.c_int32),
+        ("vert", _dp),
+        ("first", _dp),
+        ("lon_ref", _dp),
+        ("t0", _dp),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("min_dist", _dp),
+        ("min_time", _dp),
+        ("min_seg", _dp),
+        ("min_frac", _dp),
+        ("ncross", _dp),
+        ("net_cross", _dp),
+        ("first_cross", _dp),
+        ("last_cross", _dp),
+        ("sound_time", _dp),
+        ("nbroken", _dp),
+        ("track_status", _dp),
+        ("line_status", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -398,6 +434,8 @@ SYMBOLS = {
     "ste_track_positions_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePositionsF64), C.c_void_p]),
     "ste_site_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSiteF64), C.c_void_p]),
     "ste_site_tile": (C.c_int, []),
+    "ste_line_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteLineF64), C.c_void_p]),
+    "ste_line_chunk": (C.c_int, []),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1367,6 +1367,100 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- polylines ------------------------------------------------------------------------------------------------
+    _LINE_OUT3 = {"min_dist": False, "min_time": False, "min_seg": True, "min_frac": False}  # name -> int32?
+    _LINE_CROSS = {"ncross": True, "net_cross": True, "first_cross": False, "last_cross": False}
+
+    def line_metrics(self, states, lines, t0=None, model: str = "sphere", crossings: bool = True, stream=None):
+        """Tracks that are on the device against polylines -- coasts, cables, planned routes, gates -- (include/ste.h:
+        ste_line_metrics_f64; DESIGN.md, "Lines"): every ship against every line, a dense block.  ``states`` as in
+        ``path_metrics``.  ``lines``: a list of (n_i, 2) arrays of (lon, lat) in degrees, n_i >= 2, or what ``track_lines``
+        made of one (which has the rules and the refusals).  ``t0`` and ``model`` as in ``site_metrics``.  Returns a dict of
+        device tensors: ``min_dist`` (S, M, B) in km, the distance of ``model`` between the ship and the line where the planar
+        distance is least, NaN where the track has no sound step; ``min_time``, its clock time; ``min_seg`` int32, the
+        segment of the line that is closest (-1 = none) and ``min_frac``, where along it (0 at its first vertex, 1 at its
+        second); with ``crossings`` also ``ncross`` int32, the number of crossings, ``net_cross`` int32, those from the right
+        of the line's direction to its left minus the others (for a counter-clockwise ring: entries minus exits), and
+        ``first_cross`` and ``last_cross``, the clock times of the earliest and the latest, NaN = none; ``sound_time`` (S, B)
+        and ``nbroken`` (S, B) int32 as in ``site_metrics``; ``track_status`` (B,) int32, STE_LINE_BAD_TIME, and
+        ``line_status`` (M,) int32, STE_LINE_BAD_LINE.  Windows, in-place views and ``stream`` as in ``site_metrics``.  Every
+        value depends on the track's rows, ``dt``, ``t0`` and the line's vertices alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        tl = lines if isinstance(lines, TrackLines) else track_lines(lines)
+        S, M, V = int(states.shape[0]), tl.nlines, int(tl.vert.shape[1])
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            vert, first, ref = tl.on(self.device)
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, vert, first, ref]
+            if in_place:
+                width, col = ld, self.lo
+            else:
+                states = states.contiguous()
+                width, col = B, 0
+                s.track_stride = 0
+                keep.append(states)
+                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
+                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+                    s.dt = dt.data_ptr()
+                    keep.append(dt)
+            li = binding.SteLineF64()
+            li.nstates, li.model, li.states = S, self._PATH_MODELS[model], states.data_ptr()
+            li.nlines, li.nvert, li.vert, li.first, li.lon_ref = M, V, vert.data_ptr(), first.data_ptr(), ref.data_ptr()
+            li.flags, li.reserved = 0, 0
+            if t0 is not None:
+                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
+                if tv.dim() == 0:
+                    tv = tv.expand(B)
+                if tuple(tv.shape) != (B,):
+                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+                clock = torch.zeros((width,), **f64)
+                clock[col:col + B] = tv
+                li.t0 = clock.data_ptr() + 8 * col
+                keep.append(clock)
+            # rows as wide as the states': the window's columns are what the call writes and what is returned
+            names = dict(self._LINE_OUT3)
+            if crossings:
+                names.update(self._LINE_CROSS)
+            full = {k: torch.empty((S, M, width), **(i32 if isint else f64)) for k, isint in names.items()}
+            full["sound_time"] = torch.empty((S, width), **f64)
+            full["nbroken"] = torch.empty((S, width), **i32)
+            full["track_status"] = torch.empty((width,), **i32)
+            for k, ten in full.items():
+                setattr(li, k, ten.data_ptr() + ten.element_size() * col)
+            out = {k: ten[..., col:col + B] for k, ten in full.items()}
+            out["line_status"] = torch.empty((M,), **i32)
+            li.line_status = out["line_status"].data_ptr()
+            binding.check(self.lib.ste_line_metrics_f64(C.byref(s), C.byref(li), self._stream(st)), "ste_line_metrics_f64")
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2913,6 +3007,217 @@ def site_statistics(hb_or_db, sites, radius_km, nsamples: int, seed: int = 0, ch
             for k in qnames:
                 out[k + "_quantiles"] = np.nanquantile(kept[k].cpu().numpy(), q, axis=0)
     out["track_status"], out["site_status"] = smoothed["track_status"].cpu().numpy(), smoothed["site_status"].cpu().numpy()
+    out["sample_status"] = status.cpu().numpy()
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackLines:
+    """Polylines as ``ste_line_metrics_f64`` wants them (``track_lines`` makes one): ``vert`` (2, V) float64, lon then lat,
+    the longitudes of each line unwrapped from its first vertex; ``first`` (M + 1,) int32, line m owns vertices first[m] ..
+    first[m+1] - 1; ``lon_ref`` (M,), the middle of each line's unwrapped extent.  ``on(device)`` gives the three as device
+    tensors, uploaded once per device."""
+
+    vert: np.ndarray
+    first: np.ndarray
+    lon_ref: np.ndarray
+    _dev: dict = dataclasses.field(default_factory=dict, repr=False, compare=False)
+
+    @property
+    def nlines(self) -> int:
+        return int(self.lon_ref.shape[0])
+
+    def line(self, m: int) -> np.ndarray:
+        """(n_m, 2) lon / lat of line m as stored."""
+        return self.vert[:, self.first[m]:self.first[m + 1]].T
+
+    def on(self, device):
+        import torch
+
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(a).to(device) for a in (self.vert, self.first, self.lon_ref))
+        return self._dev[key]
+
+
+def track_lines(lines) -> TrackLines:
+    """Normalise a list of (n_i, 2) arrays of lon / lat degrees (planar in lon / lat, as a GeoJSON LineString) for
+    ``DeviceBatch.line_metrics``.  The longitudes of each line are unwrapped from its first vertex by wrap180 differences
+    (lon_{i+1} = lon_i + wrap180(lon_{i+1} - lon_i)), so a line may straddle the antimeridian stored either way; ``lon_ref`` is
+    the middle of the unwrapped extent.  ``ValueError``: no line or more than 4096; a line that is not (n, 2) or has fewer than
+    2 vertices; a non-finite coordinate; a segment with |delta lon| >= 90 degrees; a line wider than 180 degrees; more than
+    2^20 vertices in all.  A closed ring is a line whose last vertex repeats its first."""
+    if isinstance(lines, TrackLines):
+        return lines
+    lines = list(lines)
+    if not 1 <= len(lines) <= binding.STE_LINES_MAX:
+        raise ValueError(f"lines must be a list of 1 to {binding.STE_LINES_MAX} (n, 2) arrays, got {len(lines)}")
+    xs, ys, refs, first = [], [], [], [0]
+    for m, ln in enumerate(lines):
+        p = np.asarray(ln.detach().cpu().numpy() if hasattr(ln, "detach") else ln, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"line {m} must be an (n, 2) array of lon / lat degrees, got shape {p.shape}")
+        if p.shape[0] < 2:
+            raise ValueError(f"line {m} has fewer than 2 vertices ({p.shape[0]})")
+        if not np.isfinite(p).all():
+            raise ValueError(f"line {m} has a non-finite coordinate")
+        step = (np.diff(p[:, 0]) + 180.0) % 360.0 - 180.0
+        if (np.abs(step) >= 90.0).any():
+            raise ValueError(f"line {m} has a segment of {float(np.abs(step).max()):.6g} degrees of longitude; a segment must span "
+                             "less than 90")
+        lon = p[0, 0] + np.concatenate([[0.0], np.cumsum(step)])
+        lo, hi = float(lon.min()), float(lon.max())
+        if hi - lo > 180.0:
+            raise ValueError(f"line {m} spans {hi - lo:.6g} degrees of longitude; at most 180 are supported")
+        xs.append(lon)
+        ys.append(p[:, 1])
+        refs.append(0.5 * (lo + hi))
+        first.append(first[-1] + p.shape[0])
+    if first[-1] > binding.STE_LINE_MAX_VERT_TOTAL:
+        raise ValueError(f"the lines have {first[-1]} vertices in all; at most {binding.STE_LINE_MAX_VERT_TOTAL} are supported")
+    vert = np.ascontiguousarray(np.stack([np.concatenate(xs), np.concatenate(ys)]))
+    return TrackLines(vert=vert, first=np.asarray(first, dtype=np.int32), lon_ref=np.asarray(refs, dtype=np.float64))
+
+
+def line_chainage(lines, min_seg, min_frac, model: str = "sphere"):
+    """Where along each line the closest point lies, in km from the line's first vertex: the lengths of the segments before
+    ``min_seg`` plus ``min_frac`` times the length of that segment, NaN where ``min_seg`` < 0.  ``lines`` as in
+    ``DeviceBatch.line_metrics``; ``min_seg`` and ``min_frac`` its (S, M, B) outputs (or any (..., M, B) tensors).  The segment
+    lengths are the legs of ``model`` ("sphere" or "wgs84"), computed once on the host; the rest is torch on the tensors' own
+    device, no kernel of this library."""
+    import torch
+
+    from . import utils
+
+    if model not in DeviceBatch._PATH_MODELS:
+        raise ValueError(f"model must be one of {sorted(DeviceBatch._PATH_MODELS)}, got {model!r}")
+    tl = track_lines(lines)
+    M = tl.nlines
+    if min_seg.dim() < 2 or min_seg.shape[-2] != M or min_seg.shape != min_frac.shape:
+        raise ValueError(f"min_seg and min_frac must have one shape (..., {M}, B), got {tuple(min_seg.shape)} and {tuple(min_frac.shape)}")
+    x, y = tl.vert
+    V = x.shape[0]
+    seglen, before = np.zeros(V), np.zeros(V)  # per vertex: the segment that starts there, and the km before it on its line
+    for m in range(M):
+        a, b = int(tl.first[m]), int(tl.first[m + 1])
+        if model == "sphere":
+            leg = np.asarray(utils.haversine_formula(x[a:b - 1], y[a:b - 1], x[a + 1:b], y[a + 1:b]), dtype=np.float64)
+        else:
+            leg = np.array([utils.geographiclib_distance(x[i], y[i], x[i + 1], y[i + 1]) for i in range(a, b - 1)])
+        seglen[a:b - 1] = leg
+        before[a:b] = np.concatenate([[0.0], np.cumsum(leg)])
+    dev = min_seg.device
+    seglen_d, before_d = torch.from_numpy(seglen).to(dev), torch.from_numpy(before).to(dev)
+    start = torch.from_numpy(tl.first[:-1].astype(np.int64)).to(dev).reshape((M, 1))
+    none = min_seg < 0
+    idx = start + torch.where(none, torch.zeros_like(min_seg), min_seg).to(torch.int64)
+    km = before_d[idx] + min_frac * seglen_d[idx]
+    return torch.where(none, torch.full_like(km, float("nan")), km)
+
+
+def line_statistics(hb_or_db, lines, nsamples: int, seed: int = 0, chunk: int = 16, within_km=None, quantiles=None,
+                    max_bytes: int = 2 ** 31, t0=None, model: str = "sphere", draws=None, device="cuda:0"):
+    """Which ships crossed which lines and how close they came, with the uncertainty of the smoothing posterior: ``nsamples``
+    posterior tracks per ship are drawn (``DeviceBatch.sample_smoothed``), held against every line
+    (``DeviceBatch.line_metrics``) and discarded, ``chunk`` samples at a time, with the generator discipline of
+    ``site_statistics``: one draw buffer refilled from one generator, so the draws depend on ``(seed, chunk)`` and with
+    ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  What is kept between chunks are counts and sums
+    per (line, track) on the device, added to sample by sample in sample order: memory does not grow with ``nsamples``, and for
+    given draws the result does not depend on ``chunk``, bit for bit.  ``draws`` as in ``site_statistics``.  Given a
+    ``HostBatch`` it uploads it and runs the forward pass and the smoother first; a ``DeviceBatch`` (or a window of one) is
+    taken to hold a completed ``run()``.  ``lines``, ``t0`` and ``model`` as in ``line_metrics``.
+
+    Returns a dict of NumPy arrays per (line, track), (M, B): ``min_dist_smoothed``, ``min_time_smoothed``,
+    ``min_seg_smoothed``, ``min_frac_smoothed``, ``ncross_smoothed``, ``net_cross_smoothed``, ``first_cross_smoothed`` and
+    ``last_cross_smoothed`` of the smoothed tracks ``sm_mean``; ``cross_prob``, the fraction of samples that cross the line
+    (``ncross`` > 0); ``net_prob``, the fraction that end on its other side (``net_cross`` != 0); ``first_cross_mean`` over the
+    samples that cross (NaN where none does) with their number ``first_cross_count``; ``min_dist_mean`` over the samples that
+    have a distance (NaN where none has) with their number ``min_dist_count``; with ``within_km`` (a scalar or one per line)
+    ``approach_prob``, the fraction of samples with ``min_dist`` <= ``within_km``; ``track_status`` (B,), ``line_status`` (M,)
+    and ``sample_status`` (B,), the sampler's STE_STATUS_* bits.  With ``quantiles`` (a sequence of probabilities) also
+    ``min_dist_quantiles`` and ``first_cross_quantiles`` (len(quantiles), M, B), over the samples that have a value: these keep
+    every sample's value, nsamples x M x B doubles per quantity, and are refused when that exceeds ``max_bytes``."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    tl = track_lines(lines)
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("line_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B, M = int(db.struct.Nmax), db.ntracks, tl.nlines
+    qnames = ("min_dist", "first_cross")
+    if quantiles is not None:
+        need = 8 * nsamples * M * B
+        if need > int(max_bytes):
+            raise ValueError(f"quantiles keep nsamples x M x B = {nsamples} x {M} x {B} doubles per quantity, {need} bytes, above "
+                             f"max_bytes = {int(max_bytes)}: lower nsamples, split the lines, raise max_bytes or pass quantiles=None")
+    f64 = dict(dtype=torch.float64, device=db.device)
+    near = None
+    if within_km is not None:
+        near = torch.as_tensor(within_km, dtype=torch.float64).to(db.device)
+        if near.dim() == 0:
+            near = near.expand(M)
+        if tuple(near.shape) != (M,):
+            raise ValueError(f"within_km must be None, a scalar or have shape ({M},), got {tuple(near.shape)}")
+        near = near.reshape((M, 1))
+    kw = dict(t0=t0, model=model)
+    smoothed = db.line_metrics(db.sm_mean, tl, **kw)
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    crossed, net, have, close = (torch.zeros((M, B), dtype=torch.int32, device=db.device) for _ in range(4))
+    sums = {k: torch.zeros((M, B), **f64) for k in qnames}
+    kept = {k: torch.empty((nsamples, M, B), **f64) for k in qnames} if quantiles is not None else None
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        z = buf[:n]
+        if draws is None:
+            z.normal_(generator=gen)
+        else:
+            draws(z, i)
+        m = db.line_metrics(db.sample_smoothed(n, draws=z), tl, **kw)
+        found = ~torch.isnan(m["min_dist"])
+        dist = torch.where(found, m["min_dist"], torch.zeros_like(m["min_dist"]))
+        came = m["ncross"] > 0
+        when = torch.where(came, m["first_cross"], torch.zeros_like(m["first_cross"]))
+        for s in range(n):  # sample by sample: the sums take their terms in sample order whatever the chunk
+            crossed += came[s]
+            net += m["net_cross"][s] != 0
+            have += found[s]
+            sums["min_dist"] += dist[s]
+            sums["first_cross"] += when[s]
+            if near is not None:
+                close += m["min_dist"][s] <= near
+        if kept is not None:
+            for k in qnames:
+                kept[k][i:i + n] = m[k]
+        status |= db.sample_status
+    names = tuple(DeviceBatch._LINE_OUT3) + tuple(DeviceBatch._LINE_CROSS)
+    out = {k + "_smoothed": smoothed[k][0].cpu().numpy() for k in names}
+    count, ncount = have.cpu().numpy(), crossed.cpu().numpy()
+    out["cross_prob"] = ncount / float(nsamples)
+    out["net_prob"] = net.cpu().numpy() / float(nsamples)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["first_cross_mean"] = np.where(ncount > 0, sums["first_cross"].cpu().numpy() / ncount, np.nan)
+        out["min_dist_mean"] = np.where(count > 0, sums["min_dist"].cpu().numpy() / count, np.nan)
+    out["first_cross_count"], out["min_dist_count"] = ncount, count
+    if near is not None:
+        out["approach_prob"] = close.cpu().numpy() / float(nsamples)
+    if kept is not None:
+        q = np.asarray(quantiles, dtype=np.float64)
+        with warnings.catch_warnings():  # a (line, track) no sample gives a value: all-NaN column, NaN out
+            warnings.simplefilter("ignore", RuntimeWarning)
+            for k in qnames:
+                out[k + "_quantiles"] = np.nanquantile(kept[k].cpu().numpy(), q, axis=0)
+    out["track_status"], out["line_status"] = smoothed["track_status"].cpu().numpy(), smoothed["line_status"].cpu().numpy()
     out["sample_status"] = status.cpu().numpy()
     return out
 

@@ -449,6 +449,45 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         res.update({k: out[k][:, 0] for k in ("visit_prob", "call_prob", "min_dist_mean", "time_within_mean", "longest_mean")})
         return res
 
+    def line_approach(self, lines, nsamples: int = 0, within_km=None, model: str = "sphere", random_state: int = 0):
+        """The track ``run`` filtered against polylines -- coasts, cables, routes, gates -- (``DeviceBatch.line_metrics``
+        and ``track_estimators.batch.line_statistics``; no counterpart in the reference).  ``lines``: a list of (n, 2) lon /
+        lat arrays in degrees, or what ``track_estimators.batch.track_lines`` made of one; times are hours from the first row.
+        ``nsamples == 0``: a dict of (M,) arrays of the smoothed track, ``min_dist`` (km), ``min_time``, ``min_seg``,
+        ``min_frac``, ``ncross``, ``net_cross``, ``first_cross``, ``last_cross``, and ``chainage``, the km along each line
+        from its first vertex to the closest point.  Otherwise those (but ``chainage``) under ``*_smoothed`` names and per
+        line ``cross_prob`` (the fraction of that many tracks drawn from the joint smoothing posterior that cross the
+        line), ``net_prob`` (that end on its other side), ``first_cross_mean``, ``min_dist_mean`` and, with ``within_km``,
+        ``approach_prob`` (that come that close).  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("line_approach() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("line_approach() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        nsamples = int(nsamples)
+        if nsamples < 0:
+            raise ValueError(f"nsamples must be >= 0, got {nsamples!r}")
+        names = ("min_dist", "min_time", "min_seg", "min_frac", "ncross", "net_cross", "first_cross", "last_cross")
+        tl = _batch.track_lines(lines)
+        if nsamples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            got = db.line_metrics(db.sm_mean, tl, model=model)
+            res = {k: got[k][0, :, 0].cpu().numpy() for k in names}
+            res["chainage"] = _batch.line_chainage(tl, got["min_seg"], got["min_frac"], model=model)[0, :, 0].cpu().numpy()
+            return res
+        out = _batch.line_statistics(hb, tl, nsamples, seed=int(random_state), chunk=nsamples, within_km=within_km, model=model)
+        self._status_sampler = int(out["sample_status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        res = {k + "_smoothed": out[k + "_smoothed"][:, 0] for k in names}
+        keys = ("cross_prob", "net_prob", "first_cross_mean", "min_dist_mean") + (("approach_prob",) if within_km is not None else ())
+        res.update({k: out[k][:, 0] for k in keys})
+        return res
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
