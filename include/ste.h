@@ -29,6 +29,8 @@
  *                            track) block (no counterpart in the reference)
  *   ste_line_metrics_f64     closest approach and crossings of such tracks at polylines (coasts, cables, gates), a dense (sample,
  *                            line, track) block (no counterpart in the reference)
+ *   ste_route_metrics_f64    discrete Frechet distance and time-warping cost of pairs of such tracks as curves without a clock
+ *                            (the reference's performance_metrics.py compares two tracks row by row, which needs equal rows)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -67,7 +69,8 @@ extern "C" {
                            (ste_encounter_metrics_f64).  Unnumbered addition: tracks on the device at given clock times
                            (ste_track_positions_f64).  Unnumbered addition: tracks on the device against fixed sites
                            (ste_site_metrics_f64).  Unnumbered addition: tracks on the device against polylines
-                           (ste_line_metrics_f64).
+                           (ste_line_metrics_f64).  Unnumbered addition: pairs of tracks on the device as curves
+                           (ste_route_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -849,6 +852,80 @@ typedef struct ste_line_f64 {
 int ste_line_metrics_f64(const ste_ukf_batch_f64* b, const ste_line_f64* li, void* stream);
 /* segments of a line the kernel stages at a time; line lengths at and around its multiples are where the staging shows */
 int ste_line_chunk(void);
+
+/*
+ * ROUTES: pairs of tracks that stay on the device as CURVES, without a clock (an unnumbered addition, like ste_line_f64): did
+ * two ships sail the same route, and where do the two curves differ most?  Per (sample, pair) the discrete Frechet distance
+ * (the largest gap under the best monotone matching of rows) with the rows that attain it, and the dynamic-time-warping (DTW)
+ * cost (the summed gap under the best matching) with the number of cells on its path.  `states` is that of ste_path_f64, the
+ * pair list that of ste_encounter_f64.  No dt and no t0 is read: two ships on one lane a month apart have distance 0.  Below
+ * kDeg2Rad is that of ste_path_f64, and every expression is evaluated as written, left to right, without contraction.
+ *   - Curves.  Pair (i, j) holds sample s of ship i against sample s of ship j.  With ns = nsteps[t] (NULL = Nmax), track i
+ *     gives the points a = 0 .. ns_i, its rows 0 .. ns_i; track j gives the points b = 0 .. ns_j: point b is row b, or row
+ *     ns_j - b with STE_ROUTE_REVERSE_J.  A track with ns = 0 is one point and is valid.  i == j is valid (unreversed: 0).
+ *   - Point.  lambda = lon * kDeg2Rad, phi = lat * kDeg2Rad, c = cos(phi), u = (c * cos(lambda), c * sin(lambda), sin(phi)).
+ *   - Cell.  d = u_i(a) - u_j(b) componentwise, q(a, b) = (d.x * d.x + d.y * d.y) + d.z * d.z: the squared chord on the unit
+ *     sphere, monotone in the great-circle distance.  A q that is not finite counts as +inf.  cos and sin are the only
+ *     operations here whose bits may differ between implementations.
+ *   - Cost (DTW only).  h = 0.5 * sqrt(q), h > 1 taken as 1; cost(a, b) = (2 * 6378.137) * asin(h): km on the sphere of
+ *     ste_path_f64.  asin joins cos and sin as an operation whose bits may differ.
+ *   - Band.  Cell (a, b) is ADMISSIBLE when band == 0 or |a - b| <= band (a Sakoe-Chiba band).  Every admissible cell but
+ *     (0, 0) has an admissible predecessor: the diagonal one, or along row 0 / column 0 the one toward (0, 0).
+ *   - Predecessor of (a, b) for a table T: of (a-1, b-1), (a-1, b), (a, b-1), in this order, among those that exist and are
+ *     admissible, the first; a later one replaces it only when its T is strictly smaller.
+ *   - Frechet table.  F(0, 0) = q(0, 0), at(0, 0) = (0, 0).  Otherwise m = F(predecessor by F); if q(a, b) >= m then
+ *     F = q(a, b) and at = (a, b), else F = m and at = at(predecessor).
+ *   - DTW tables.  D(0, 0) = cost(0, 0), L(0, 0) = 1.  Otherwise D = cost(a, b) + D(predecessor by D) and
+ *     L = 1 + L(predecessor by D).
+ *   - Bits.  min and max do not round and each D is one addition, so every value has the bits of the row-major recurrence
+ *     whatever the order in which the device evaluates the cells.
+ *   - Outputs, taken at (ns_i, ns_j).  frechet_at = at(ns_i, ns_j) as ROW indices of the two tracks (with reversal the second
+ *     entry is ns_j - b).  frechet is the leg of ste_path_metrics_f64 for `model` between the positions of those two rows: the
+ *     leg function runs once per (sample, pair).  dtw = D(ns_i, ns_j), dtw_len = L(ns_i, ns_j).
+ *   - Status.  F(ns_i, ns_j) = +inf sets STE_ROUTE_NOT_FINITE: every coupling visits every row, so one row with a non-finite
+ *     coordinate suffices.  STE_ROUTE_BAD_INDEX (a pair index outside [0, B)) and STE_ROUTE_NO_PATH (band > 0 and
+ *     |ns_i - ns_j| > band: the last cell is not admissible) are decided before anything of the pair is read.  Any status bit
+ *     gives frechet = dtw = NaN, frechet_at = (-1, -1) and dtw_len = 0.
+ *   - Every value's bits depend on the two tracks' rows, band and the reverse flag alone: not on S, P, the pair's place in the
+ *     list, the window, which outputs were asked for, or whether `work` was used.
+ *   - The call reads only B, Nmax, track_stride and nsteps (NULL = Nmax for every track) of the batch and writes nothing of the
+ *     batch; windows and addressing are those of ste_path_metrics_f64.  Rows past nsteps[t] of states are not read.  Outputs
+ *     per (sample, pair) are out[s * P + p] (frechet_at: two of them).
+ *   - Work.  A pair whose track j has more than ste_route_lds_cols() points keeps a row of the tables in `work`;
+ *     ste_route_workspace(Nmax, nstates, npairs) is the number of bytes these sizes need, 0 while Nmax + 1 <= ste_route_lds_cols().
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or ro NULL; states or pairs NULL; nstates < 1
+ *     or > 65535; npairs < 1 or > STE_ROUTE_MAX_PAIRS; an unknown model when frechet is asked for; band < 0; flags with any
+ *     other bit than STE_ROUTE_REVERSE_J; every output NULL (each output is independent of the others); work NULL or work_bytes
+ *     below ste_route_workspace(Nmax, nstates, npairs) when that is non-zero; B <= 0, Nmax < 0 or Nmax > 2^31 - 257, or
+ *     track_stride non-zero and below B.
+ */
+#define STE_ROUTE_MAX_PAIRS (1 << 26)
+#define STE_ROUTE_REVERSE_J 0x1u     /* flags: track j is read from its last row to its first */
+#define STE_ROUTE_BAD_INDEX 0x1      /* status: a pair index outside [0, B): nothing of that pair is read */
+#define STE_ROUTE_NO_PATH 0x2        /* status: band > 0 and |ns_i - ns_j| > band: nothing of that pair is read */
+#define STE_ROUTE_NOT_FINITE 0x4     /* status: a coordinate of a row read is not finite */
+typedef struct ste_route_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;           /* STE_PREP_SPHERE / STE_PREP_WGS84: leg function for `frechet` only */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 */
+    int64_t npairs;          /* P, 1 .. STE_ROUTE_MAX_PAIRS */
+    const int32_t* pairs;    /* DEVICE [P][2]: (i, j), tracks of the window */
+    int32_t band;            /* >= 0, 0 = none */
+    uint32_t flags;          /* STE_ROUTE_REVERSE_J or 0 */
+    double* work;            /* DEVICE scratch of work_bytes, see ste_route_workspace; may be NULL when that is 0 */
+    int64_t work_bytes;
+    double* frechet;         /* DEVICE [S][P] or NULL: km */
+    int32_t* frechet_at;     /* DEVICE [S][P][2] or NULL: (row of i, row of j) of the cell that attains it */
+    double* dtw;             /* DEVICE [S][P] or NULL: km */
+    int32_t* dtw_len;        /* DEVICE [S][P] or NULL: cells on the warping path */
+    int32_t* status;         /* DEVICE [S][P] or NULL: STE_ROUTE_* bits */
+} ste_route_f64;             /* 96 bytes */
+
+int ste_route_metrics_f64(const ste_ukf_batch_f64* b, const ste_route_f64* ro, void* stream);
+/* bytes of `work` these sizes need; may be 0 */
+size_t ste_route_workspace(int32_t Nmax, int32_t nstates, int64_t npairs);
+/* columns of track j whose boundary row the kernel keeps in LDS; a pair with more goes through `work` */
+int ste_route_lds_cols(void);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -320,6 +320,34 @@ class SteLineF64(C.Structure):
     ]
 
 
+STE_ROUTE_MAX_PAIRS = 1 << 26
+STE_ROUTE_REVERSE_J = 0x1
+STE_ROUTE_BAD_INDEX = 0x1
+STE_ROUTE_NO_PATH = 0x2
+STE_ROUTE_NOT_FINITE = 0x4
+
+
+class SteRouteF64(C.Structure):
+    """Mirror of ``struct ste_route_f64`` (include/ste.h): pairs of tracks on the device as curves."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("npairs", C.c_int64),
+        ("pairs", _dp),
+        ("band", C.c_int32),
+        ("flags", C.c_uint32),
+        ("work", _dp),
+        ("work_bytes", C.c_int64),
+        ("frechet", _dp),
+        ("frechet_at", _dp),
+        ("dtw", _dp),
+        ("dtw_len", _dp),
+        ("status", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -436,6 +464,9 @@ SYMBOLS = {
     "ste_site_tile": (C.c_int, []),
     "ste_line_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteLineF64), C.c_void_p]),
     "ste_line_chunk": (C.c_int, []),
+    "ste_route_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRouteF64), C.c_void_p]),
+    "ste_route_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
+    "ste_route_lds_cols": (C.c_int, []),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

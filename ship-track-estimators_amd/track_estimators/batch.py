@@ -1461,6 +1461,76 @@ class DeviceBatch:
                 ten.record_stream(st)
         return out
 
+    # -- routes: pairs of tracks as curves ------------------------------------------------------------------------
+    def route_metrics(self, states, pairs, dtw: bool = False, band: int = 0, reverse: bool = False, model: str = "sphere",
+                      stream=None):
+        """Pairs of tracks that are on the device against each other as curves, without a clock (include/ste.h:
+        ste_route_metrics_f64; DESIGN.md, "Routes"): the discrete Frechet distance and, with ``dtw``, the time-warping cost.
+        ``states`` and ``pairs`` as in ``encounter_metrics``; sample s of one ship is held against sample s of the other, rows
+        0 .. nsteps of each, and no ``dt`` is read.  ``band``: 0, or the Sakoe-Chiba band |a - b| <= band on the row indices.
+        ``reverse``: track j is read from its last row to its first (ships on one lane in opposite directions).  ``model``: the
+        leg function of ``frechet``, "sphere" or "wgs84".  Returns a dict of device tensors: ``frechet`` (S, P) in km;
+        ``frechet_at`` (S, P, 2) int32, the rows of i and j whose distance it is; ``status`` (S, P) int32, STE_ROUTE_BAD_INDEX /
+        STE_ROUTE_NO_PATH (the lengths differ by more than the band) / STE_ROUTE_NOT_FINITE, any of which gives NaN and
+        (-1, -1); and with ``dtw`` ``dtw`` (S, P) in km, the summed great-circle gaps on the cheapest warping path, and
+        ``dtw_len`` (S, P) int32, the cells on that path (0 with a status bit).  The scratch the kernel needs for tracks of
+        more than ``ste_route_lds_cols()`` rows is allocated here.  Windows, in-place views and ``stream`` as in
+        ``path_metrics``; every value depends on the two tracks' rows, ``band`` and ``reverse`` alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        if model not in self._PATH_MODELS:
+            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        band = int(band)
+        if not 0 <= band < 2 ** 31:
+            raise ValueError(f"band must be >= 0 (0 = no band) and below 2^31, got {band!r}")
+        if not isinstance(pairs, torch.Tensor):
+            pairs = np.asarray(pairs)
+            if pairs.dtype.kind not in "iu":
+                raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
+            pairs = torch.from_numpy(np.ascontiguousarray(pairs.astype(np.int64)))
+        elif pairs.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= binding.STE_ROUTE_MAX_PAIRS:
+            raise ValueError(f"pairs must have shape (P, 2) with 1 <= P <= {binding.STE_ROUTE_MAX_PAIRS}, got {tuple(pairs.shape)}")
+        S, P = int(states.shape[0]), int(pairs.shape[0])
+        ld = int(self.struct.track_stride or self.struct.B)
+        cur = torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            # an index that does not fit 32 bits stays outside [0, B)
+            pr = pairs.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
+            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
+            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            keep = [states, pr]
+            if not in_place:
+                states = states.contiguous()
+                s.track_stride = 0
+                keep.append(states)
+            out = _route_call(self.lib, torch, s, states, S, pr, dtw, band, reverse, self._PATH_MODELS[model], self.device,
+                              self._stream(st), keep)
+            for ten in keep:
+                ten.record_stream(st)
+            self._mark_use(st)
+            for ten in out.values():
+                ten.record_stream(st)
+        return out
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -3220,6 +3290,215 @@ def line_statistics(hb_or_db, lines, nsamples: int, seed: int = 0, chunk: int = 
     out["track_status"], out["line_status"] = smoothed["track_status"].cpu().numpy(), smoothed["line_status"].cpu().numpy()
     out["sample_status"] = status.cpu().numpy()
     return out
+
+
+def _route_call(lib, torch, s, states, S, pr, dtw, band, reverse, model_id, device, stream_ptr, keep):
+    """One ste_route_metrics_f64 launch on the current stream: ``s`` the batch struct (B, Nmax, track_stride and nsteps are all
+    it needs), ``states`` (S, Nmax+1, 4, ld) and ``pr`` (P, 2) int32 on ``device``.  Allocates the outputs and the scratch;
+    tensors the launch reads are appended to ``keep``."""
+    P = int(pr.shape[0])
+    f64 = dict(dtype=torch.float64, device=device)
+    i32 = dict(dtype=torch.int32, device=device)
+    ro = binding.SteRouteF64()
+    ro.nstates, ro.model, ro.states = S, model_id, states.data_ptr()
+    ro.npairs, ro.pairs = P, pr.data_ptr()
+    ro.band, ro.flags = int(band), binding.STE_ROUTE_REVERSE_J if reverse else 0
+    need = int(lib.ste_route_workspace(int(s.Nmax), S, P))
+    if need:
+        work = torch.empty(((need + 7) // 8,), **f64)
+        ro.work, ro.work_bytes = work.data_ptr(), need
+        keep.append(work)
+    out = {"frechet": torch.empty((S, P), **f64), "frechet_at": torch.empty((S, P, 2), **i32),
+           "status": torch.empty((S, P), **i32)}
+    if dtw:
+        out["dtw"] = torch.empty((S, P), **f64)
+        out["dtw_len"] = torch.empty((S, P), **i32)
+    for k, ten in out.items():
+        setattr(ro, k, ten.data_ptr())
+    binding.check(lib.ste_route_metrics_f64(C.byref(s), C.byref(ro), stream_ptr), "ste_route_metrics_f64")
+    return out
+
+
+def route_endpoint_pairs(mean, nsteps, within_km, margin_km: float = 0.0, reverse: bool = False, chunk: int = 2048):
+    """The pair test of ``route_candidates`` on plain tensors of any one device: ``mean`` (Nmax+1, 4, B) float64 and
+    ``nsteps`` (B,) integer.  Returns an int32 (P, 2) tensor of (i, j), i < j, sorted by (i, j)."""
+    import torch
+
+    rows, _, B = mean.shape
+    dev = mean.device
+    ns = nsteps.to(dev).to(torch.int64).clamp(0, rows - 1)
+    col = torch.arange(B, device=dev)
+
+    def unit(row):  # (3, B): the unit vectors of one row per track
+        lon, lat = torch.deg2rad(mean[row, 0, col]), torch.deg2rad(mean[row, 1, col])
+        return torch.stack([torch.cos(lat) * torch.cos(lon), torch.cos(lat) * torch.sin(lon), torch.sin(lat)])
+
+    first, last = unit(torch.zeros_like(ns)), unit(ns)
+    ok = torch.isfinite(first).all(dim=0) & torch.isfinite(last).all(dim=0)
+    # 1e-7 rad (0.6 m) for the rounding of the chords, as candidate_pairs
+    reach = (float(within_km) + float(margin_km)) / EARTH_RADIUS_KM + 1e-7
+    found = []
+    for lo in range(0, B, int(chunk)):
+        hi = min(lo + int(chunk), B)
+
+        def angle(u, v):  # (hi - lo, B) angles from chords: 2 asin(|u - v| / 2)
+            chord = (u[:, lo:hi, None] - v[:, None, :]).norm(dim=0)
+            return 2.0 * torch.asin((0.5 * chord).clamp(max=1.0))
+
+        if reverse:
+            far = torch.maximum(angle(first, last), angle(last, first))
+        else:
+            far = torch.maximum(angle(first, first), angle(last, last))
+        keep = (far <= reach) & ok[lo:hi, None] & ok[None, :] & (col[None, :] > col[lo:hi, None])
+        ij = keep.nonzero()                                                           # row-major: sorted by (i, j)
+        ij[:, 0] += lo
+        found.append(ij)
+    return torch.cat(found).to(torch.int32)
+
+
+def route_candidates(db: "DeviceBatch", within_km, margin_km: float = 0.0, reverse: bool = False, chunk: int = 2048):
+    """The pairs of a resident batch worth giving to ``DeviceBatch.route_metrics`` when the question is "Frechet distance at
+    most ``within_km``": an int32 (P, 2) device tensor of (i, j), i < j, sorted by (i, j).  Torch plumbing without a kernel, on
+    ``sm_mean`` (``fwd_mean`` when the batch has no smoother).  Every monotone coupling matches first row with first and last
+    with last, so the Frechet distance is at least the larger of the two endpoint distances (with ``reverse``: first against
+    last and last against first); a pair is kept when that is at most ``within_km`` + ``margin_km``.  For the tested tracks the
+    pruning is exact; ``margin_km`` is the allowance for samples of the posterior (a few standard deviations of position).
+    The B x B test runs in blocks of ``chunk`` rows.  Tracks with a non-finite end pair with nothing."""
+    mean = db.sm_mean if db.sm_mean is not None else db.fwd_mean
+    if mean is None:
+        raise ValueError("route_candidates() needs sm_mean or fwd_mean, and this batch was built without histories")
+    B = db.ntracks
+    nsteps = db.t["nsteps"][db.lo:db.lo + B]
+    with db.torch.cuda.device(db.device):
+        return route_endpoint_pairs(mean, nsteps, within_km, margin_km, reverse, chunk)
+
+
+def route_statistics(hb_or_db, pairs, within_km, nsamples: int, seed: int = 0, chunk: int = 16, band: int = 0,
+                     reverse: bool = False, model: str = "sphere", quantiles=None, dtw: bool = False, device="cuda:0"):
+    """How sure one can be that two ships followed one route: ``nsamples`` posterior tracks per ship are drawn
+    (``DeviceBatch.sample_smoothed``), sample s of one ship held against sample s of the other as curves
+    (``DeviceBatch.route_metrics``) and discarded, ``chunk`` samples at a time, with the generator discipline of
+    ``encounter_statistics``: one draw buffer refilled from one generator, so the draws depend on ``(seed, chunk)`` and with
+    ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  What is kept between chunks are counts and
+    sums per pair, added to sample by sample: memory does not grow with ``nsamples`` unless ``quantiles`` are asked for, which
+    keep nsamples x P doubles.  Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother first; a
+    ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``pairs``, ``band``, ``reverse`` and
+    ``model`` as in ``route_metrics``.
+
+    Returns a dict of NumPy arrays per pair, (P,): ``frechet_smoothed``, ``frechet_at_smoothed`` (P, 2) and ``status`` of the
+    smoothed tracks ``sm_mean``; ``prob_within``, the share of samples with frechet <= ``within_km``; ``frechet_mean`` over the
+    samples without a status bit (NaN where there is none); ``nbad``, the number of samples with a status bit; with
+    ``quantiles`` ``frechet_quantiles`` (len(quantiles), P); with ``dtw`` ``dtw_smoothed``, ``dtw_len_smoothed`` and
+    ``dtw_per_cell_mean``, the mean of dtw / dtw_len; and ``sample_status`` (B,), the sampler's STE_STATUS_* bits."""
+    import warnings
+
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    within_km = float(within_km)
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError("route_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    torch = db.torch
+    N, B = int(db.struct.Nmax), db.ntracks
+    kw = dict(dtw=dtw, band=band, reverse=reverse, model=model)
+    smoothed = db.route_metrics(db.sm_mean, pairs, **kw)
+    P = int(smoothed["status"].shape[1])
+    gen = torch.Generator(device=db.device)
+    gen.manual_seed(int(seed))
+    f64 = dict(dtype=torch.float64, device=db.device)
+    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
+    within, nbad = (torch.zeros((P,), dtype=torch.int32, device=db.device) for _ in range(2))
+    fsum, wsum = torch.zeros((P,), **f64), torch.zeros((P,), **f64)
+    kept = torch.empty((nsamples, P), **f64) if quantiles is not None else None
+    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
+    for i in range(0, nsamples, chunk):
+        n = min(chunk, nsamples - i)
+        draws = buf[:n]
+        draws.normal_(generator=gen)
+        m = db.route_metrics(db.sample_smoothed(n, draws=draws), pairs, **kw)
+        good = m["status"] == 0
+        fre = torch.where(good, m["frechet"], torch.zeros_like(m["frechet"]))
+        for s in range(n):  # sample by sample: the sums take their terms in sample order whatever the chunk
+            within += good[s] & (m["frechet"][s] <= within_km)
+            nbad += ~good[s]
+            fsum += fre[s]
+            if dtw:
+                wsum += torch.where(good[s], m["dtw"][s] / m["dtw_len"][s].clamp(min=1), torch.zeros_like(fsum))
+        if kept is not None:
+            kept[i:i + n] = m["frechet"]
+        status |= db.sample_status
+    count = nsamples - nbad.cpu().numpy()
+    out = {"frechet_smoothed": smoothed["frechet"][0].cpu().numpy(), "frechet_at_smoothed": smoothed["frechet_at"][0].cpu().numpy(),
+           "status": smoothed["status"][0].cpu().numpy(), "prob_within": within.cpu().numpy() / float(nsamples),
+           "nbad": nsamples - count}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["frechet_mean"] = np.where(count > 0, fsum.cpu().numpy() / count, np.nan)
+        if dtw:
+            out["dtw_smoothed"], out["dtw_len_smoothed"] = smoothed["dtw"][0].cpu().numpy(), smoothed["dtw_len"][0].cpu().numpy()
+            out["dtw_per_cell_mean"] = np.where(count > 0, wsum.cpu().numpy() / count, np.nan)
+    if kept is not None:
+        with warnings.catch_warnings():  # a pair no sample gives a value: all-NaN column, NaN out
+            warnings.simplefilter("ignore", RuntimeWarning)
+            out["frechet_quantiles"] = np.nanquantile(kept.cpu().numpy(), np.asarray(quantiles, dtype=np.float64), axis=0)
+    out["sample_status"] = status.cpu().numpy()
+    return out
+
+
+def curve_distance(curves_a, curves_b, dtw: bool = False, band: int = 0, reverse: bool = False, model: str = "sphere",
+                   device="cuda:0"):
+    """Frechet distance (and, with ``dtw``, time-warping cost) of pairs of curves that are no tracks of a batch: a filtered
+    track against its observations, a GP track, a Savitzky-Golay track.  ``curves_a`` and ``curves_b``: equally long lists of
+    (n, 2) lon / lat arrays in degrees, of any lengths n >= 1 (a single (n, 2) array is a list of one); pair k is (a_k, b_k).
+    They are packed into a ``states`` tensor whose track 2k is a_k and track 2k + 1 is b_k and given to
+    ste_route_metrics_f64 through a batch struct that carries nothing but B, Nmax and nsteps: the call reads nothing else.
+    ``band``, ``reverse`` and ``model`` as in ``DeviceBatch.route_metrics``.  Returns a dict of NumPy arrays per pair:
+    ``frechet`` (K,) km, ``frechet_at`` (K, 2), the rows of a_k and b_k whose distance it is, ``status`` (K,) and with ``dtw``
+    ``dtw`` and ``dtw_len``."""
+    import torch
+
+    def as_list(c):
+        if isinstance(c, np.ndarray) and c.ndim == 2:
+            return [c]
+        return list(c)
+
+    ca = [np.asarray(c, dtype=np.float64) for c in as_list(curves_a)]
+    cb = [np.asarray(c, dtype=np.float64) for c in as_list(curves_b)]
+    if len(ca) != len(cb) or not ca:
+        raise ValueError(f"curves_a and curves_b must be equally long, non-empty lists, got {len(ca)} and {len(cb)}")
+    for c in ca + cb:
+        if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1:
+            raise ValueError(f"a curve must be an (n, 2) array of lon / lat with n >= 1, got shape {c.shape}")
+    if model not in DeviceBatch._PATH_MODELS:
+        raise ValueError(f"model must be one of {sorted(DeviceBatch._PATH_MODELS)}, got {model!r}")
+    band = int(band)
+    if not 0 <= band < 2 ** 31:
+        raise ValueError(f"band must be >= 0 (0 = no band) and below 2^31, got {band!r}")
+    lib = binding.require_gpu()
+    dev = torch.device(device)
+    K = len(ca)
+    B, rows = 2 * K, max(c.shape[0] for c in ca + cb)
+    host = np.zeros((1, rows, 4, B))
+    nsteps = np.empty((B,), dtype=np.int32)
+    for k in range(K):
+        for t, c in ((2 * k, ca[k]), (2 * k + 1, cb[k])):
+            host[0, :c.shape[0], :2, t] = c
+            nsteps[t] = c.shape[0] - 1
+    with torch.cuda.device(dev):
+        states = torch.from_numpy(host).to(dev)
+        ns = torch.from_numpy(nsteps).to(dev)
+        pr = torch.arange(B, dtype=torch.int32, device=dev).reshape(K, 2)
+        s = binding.SteUkfBatchF64()
+        s.B, s.Nmax, s.nsteps = B, rows - 1, ns.data_ptr()
+        keep = [states, ns, pr]
+        out = _route_call(lib, torch, s, states, 1, pr, dtw, band, reverse, DeviceBatch._PATH_MODELS[model], dev,
+                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), keep)
+        res = {k: v[0].cpu().numpy() for k, v in out.items()}  # the download waits for the launch
+    return res
 
 
 KM_PER_DEG = 6378.137 * np.pi / 180.0  # Kd: km per degree of a great circle on the sphere of the leg functions

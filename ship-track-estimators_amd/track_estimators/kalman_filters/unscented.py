@@ -488,6 +488,44 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         res.update({k: out[k][:, 0] for k in keys})
         return res
 
+    def route_distance(self, curve, nsamples: int = 0, dtw: bool = False, reverse: bool = False, model: str = "sphere",
+                       random_state: int = 0):
+        """The track ``run`` filtered against another curve -- its own observations, a planned route, a GP or Savitzky-Golay
+        track of the same ship -- as curves without a clock (``track_estimators.batch.curve_distance``; the reference's
+        ``performance_metrics.py`` compares two tracks row by row, which needs equal rows).  ``curve``: an (n, 2) array of
+        lon / lat in degrees, of any length.  ``nsamples == 0``: the smoothed track against ``curve``, a dict of ``frechet``
+        (km, a float: the discrete Frechet distance), ``frechet_at`` (the rows of the track and of ``curve`` whose distance
+        it is), ``status`` and, with ``dtw``, ``dtw`` (km, the time-warping cost) and ``dtw_len`` (the cells on its path).
+        Otherwise the same keys as arrays over that many tracks drawn from the joint smoothing posterior, those of
+        ``sample_smoothed(nsamples, random_state)``.  ``reverse``: ``curve`` is read from its last point to its first.
+        ``model``: the leg function of ``frechet``, "sphere" or "wgs84".  The track is packed as ``run`` packed it, as for
+        ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("route_distance() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("route_distance() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        nsamples = int(nsamples)
+        if nsamples < 0:
+            raise ValueError(f"nsamples must be >= 0, got {nsamples!r}")
+        curve = np.asarray(curve, dtype=np.float64)
+        kw = dict(dtw=dtw, reverse=reverse, model=model)
+        if nsamples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            track = db.sm_mean[:, :2, 0].cpu().numpy()
+            got = _batch.curve_distance([track], [curve], **kw)
+            res = {"frechet": float(got["frechet"][0]), "frechet_at": tuple(int(v) for v in got["frechet_at"][0]),
+                   "status": int(got["status"][0])}
+            if dtw:
+                res.update(dtw=float(got["dtw"][0]), dtw_len=int(got["dtw_len"][0]))
+            return res
+        samples = self.sample_smoothed(nsamples, random_state)
+        return _batch.curve_distance([np.ascontiguousarray(t[:, :2]) for t in samples], [curve] * nsamples, **kw)
+
     # -- robustification helpers (unscented.py:353-511) -------------------------------------------------------------
     # The reference's call site is commented out (unscented.py:228), so ``run`` never invokes these; they are kept as
     # callable methods with the reference's signatures.  The batched path offers the same loop as an opt-in flag
