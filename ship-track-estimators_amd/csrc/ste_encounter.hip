@@ -28,7 +28,6 @@
 namespace ste {
 namespace {
 
-constexpr int kNoLeg = -1;                    // min_dist not asked for: no leg function in the kernel
 constexpr double kKd = kEarthKm * kDeg2Rad;   // km per degree of a great circle, one double
 
 struct EncParams {
@@ -51,7 +50,6 @@ struct EncParams {
     int32_t* status;        // [P] or nullptr
 };
 
-__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
 
 // one ship's current step in one sample: rows k and k + 1, and row k + 2 on its way
 struct EncStep {
@@ -138,19 +136,6 @@ __device__ __forceinline__ void piece(const EncStep& A, const EncStep& Bs, EncAc
         } else {
             c.open = false;
         }
-    }
-}
-
-// the leg of path_metrics between two positions given in degrees
-template <int kModel>
-__device__ __forceinline__ double encounter_leg_km(double lon1, double lat1, double lon2, double lat2) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double a1 = lat1 * kDeg2Rad, a2 = lat2 * kDeg2Rad;
-        return sphere_dist_km(lon1 * kDeg2Rad, a1, cos(a1), lon2 * kDeg2Rad, a2, cos(a2));
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (lon1 + lat1 + lon2 + lat2) * 0.0;
-        return wgs84_leg(lon1, lat1, lon2, lat2).dist_km + poison;
     }
 }
 
@@ -256,7 +241,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const bool bad = status != 0;
     const bool found = !bad && c.best_q < __builtin_inf();
     if constexpr (kModel != kNoLeg) {
-        p.min_dist[o] = found ? encounter_leg_km<kModel>(c.xi, c.yi, c.xj, c.yj) : nan;
+        p.min_dist[o] = found ? leg_km_deg<kModel>(c.xi, c.yi, c.xj, c.yj) : nan;
     }
     if (p.min_time) p.min_time[o] = found ? c.min_time : nan;
     if constexpr (kWithin) {

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/ste.h"
 #include "ste_math.h"
 
 #pragma clang fp contract(off)
@@ -510,6 +511,27 @@ __device__ Leg wgs84_leg(double lon1, double lat1, double lon2, double lat2) {
     r.dist_km = (0.0 + s12x) * 1e-3;
     r.head_deg = floored_mod360(atan2d(salp1, calp1) + 360.0);
     return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the metric kernels (encounters, positions, sites, lines, routes) share, compiled without contraction like the rest.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kNoLeg = -1;  // the kModel of a kernel whose distance output was not asked for: no leg function in it
+
+__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
+__device__ __forceinline__ bool is_finite(double x) { return x * 0.0 == 0.0; }
+
+// the leg of path_metrics between two positions given in degrees
+template <int kModel>
+__device__ __forceinline__ double leg_km_deg(double lon1, double lat1, double lon2, double lat2) {
+    if constexpr (kModel == STE_PREP_SPHERE) {
+        const double a1 = lat1 * kDeg2Rad, a2 = lat2 * kDeg2Rad;
+        return sphere_dist_km(lon1 * kDeg2Rad, a1, cos(a1), lon2 * kDeg2Rad, a2, cos(a2));
+    } else {
+        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
+        const double poison = (lon1 + lat1 + lon2 + lat2) * 0.0;
+        return wgs84_leg(lon1, lat1, lon2, lat2).dist_km + poison;
+    }
 }
 
 }  // namespace

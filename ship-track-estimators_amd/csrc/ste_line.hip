@@ -42,7 +42,6 @@
 namespace ste {
 namespace {
 
-constexpr int kNoLeg = -1;  // min_dist not asked for: no leg function in the kernel
 constexpr int kLineChunk = STE_LINE_CHUNK;
 static_assert(kLineChunk >= 1 && kLineChunk <= 64, "a chunk is staged by one pass of the wave plus one vertex");
 constexpr double kKd = kEarthKm * kDeg2Rad;  // km per degree of a great circle, one double
@@ -71,21 +70,6 @@ struct LineParams {
     int32_t* line_status;    // [M] or nullptr
 };
 
-__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
-__device__ __forceinline__ bool finite(double x) { return x * 0.0 == 0.0; }
-
-// the leg of path_metrics between two positions given in degrees
-template <int kModel>
-__device__ __forceinline__ double line_leg_km(double lon1, double lat1, double lon2, double lat2) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double a1 = lat1 * kDeg2Rad, a2 = lat2 * kDeg2Rad;
-        return sphere_dist_km(lon1 * kDeg2Rad, a1, cos(a1), lon2 * kDeg2Rad, a2, cos(a2));
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (lon1 + lat1 + lon2 + lat2) * 0.0;
-        return wgs84_leg(lon1, lat1, lon2, lat2).dist_km + poison;
-    }
-}
 
 template <int kModel, bool kCross>
 __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const LineParams p) {
@@ -104,12 +88,12 @@ __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const Line
     const int nseg = range_ok ? f1 - f0 - 1 : 0;
     const double* vx = p.vert + (range_ok ? f0 : 0);
     const double* vy = vx + V;
-    bool lbad = !range_ok || !finite(ref);
+    bool lbad = !range_ok || !is_finite(ref);
     if (range_ok) {
         bool mine = false;
         for (int i = lane; i <= nseg; i += 64) {
             const double x = vx[i], y = vy[i];
-            if (!(finite(x) && finite(y) && fabs(x - ref) <= 90.0)) mine = true;
+            if (!(is_finite(x) && is_finite(y) && fabs(x - ref) <= 90.0)) mine = true;
         }
         lbad = lbad || __ballot(mine) != 0;
     }
@@ -131,7 +115,7 @@ __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const Line
     const size_t t = (size_t)ttile * 64 + lane;
     const bool live = t < (size_t)p.B;
     const double t0 = live && p.t0 ? p.t0[t] : 0.0;
-    bool tbad = !finite(t0);
+    bool tbad = !is_finite(t0);
     // a bad line is walked by the block of line 0 alone, for the track's own outputs
     const bool walk = live && !tbad && (!lbad || m == 0);
     const int ns = walk ? min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax) : 0;
@@ -166,12 +150,12 @@ __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const Line
             plon = st[(r * 4) * ld];
             plat = st[(r * 4 + 1) * ld];
         }
-        if (active && !(dtk >= 0.0 && finite(dtk))) tbad = true;
+        if (active && !(dtk >= 0.0 && is_finite(dtk))) tbad = true;
         const double lo = t0 + T, T1 = T + dtk, hi = t0 + T1;
         const double len = hi - lo;
         const double delta = wrap180(lon1 - lon);
         const bool examined = active && hi > lo;
-        const bool sound = examined && fabs(delta) < 90.0 && finite(lat) && finite(lat1);
+        const bool sound = examined && fabs(delta) < 90.0 && is_finite(lat) && is_finite(lat1);
         if (examined && !sound) ++nbroken;
         if (sound) sound_time = sound_time + len;
         if (L > 0 && __ballot(sound) != 0) {  // uniform
@@ -292,7 +276,7 @@ __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const Line
         double d = nan;
         if (found) {  // seg < nseg: both vertices lie inside the line's range
             const double ax = vx[seg], ay = vy[seg], bx = vx[seg + 1], by = vy[seg + 1];
-            d = line_leg_km<kModel>(posx, posy, ax + frac * (bx - ax), ay + frac * (by - ay));
+            d = leg_km_deg<kModel>(posx, posy, ax + frac * (bx - ax), ay + frac * (by - ay));
         }
         p.min_dist[o] = d;
     }

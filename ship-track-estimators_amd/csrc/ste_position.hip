@@ -58,8 +58,6 @@ struct PosParams {
 
 constexpr size_t kLaneLoopQueries = (size_t)1 << 14;  // 256 waves, one for every CU: the two mappings tie at 10 000 queries
 
-__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
-__device__ __forceinline__ bool is_finite(double x) { return x * 0.0 == 0.0; }
 
 __global__ __launch_bounds__(64) void position_knots(const PosParams p) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;

@@ -41,7 +41,6 @@
 namespace ste {
 namespace {
 
-constexpr int kNoLeg = -1;  // frechet not asked for: no leg function in the kernel
 constexpr int kLdsCols = STE_ROUTE_LDS_COLS;
 constexpr int kRing = 128;               // columns of track j staged at a time: the chunk being swept and the one before it
 constexpr int kWorkWaves = 2048;         // blocks of a launch that needs `work`: one slice each
@@ -84,19 +83,6 @@ __device__ __forceinline__ void unit_vector(double lon, double lat, double& x, d
     x = c * cos(lam);
     y = c * sin(lam);
     z = sin(phi);
-}
-
-// the leg of path_metrics between two positions given in degrees
-template <int kModel>
-__device__ __forceinline__ double route_leg_km(double lon1, double lat1, double lon2, double lat2) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double a1 = lat1 * kDeg2Rad, a2 = lat2 * kDeg2Rad;
-        return sphere_dist_km(lon1 * kDeg2Rad, a1, cos(a1), lon2 * kDeg2Rad, a2, cos(a2));
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (lon1 + lat1 + lon2 + lat2) * 0.0;
-        return wgs84_leg(lon1, lat1, lon2, lat2).dist_km + poison;
-    }
 }
 
 template <int kModel, bool kDtw>
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(64) void route_metrics(const RouteParams p) {
             if constexpr (kModel != kNoLeg) {
                 double d = nan;
                 if (!bad) {  // oa <= ns_i and rj <= ns_j: rows that the sweep has read
-                    d = route_leg_km<kModel>(sti[((size_t)oa * 4) * ld], sti[((size_t)oa * 4 + 1) * ld],
+                    d = leg_km_deg<kModel>(sti[((size_t)oa * 4) * ld], sti[((size_t)oa * 4 + 1) * ld],
                                              stj[((size_t)rj * 4) * ld], stj[((size_t)rj * 4 + 1) * ld]);
                 }
                 p.frechet[o] = d;

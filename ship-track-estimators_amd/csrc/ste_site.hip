@@ -36,7 +36,6 @@
 namespace ste {
 namespace {
 
-constexpr int kNoLeg = -1;                    // min_dist not asked for: no leg function in the kernel
 constexpr int kSiteTile = STE_SITE_TILE;
 constexpr double kKd = kEarthKm * kDeg2Rad;   // km per degree of a great circle, one double
 
@@ -62,23 +61,8 @@ struct SiteParams {
     int32_t* site_status;   // [M] or nullptr
 };
 
-__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
-__device__ __forceinline__ bool finite(double x) { return x * 0.0 == 0.0; }
 __device__ __forceinline__ bool site_is_bad(double X, double Y, double R) {
-    return !(finite(X) && finite(Y) && R >= 0.0 && R <= STE_ENCOUNTER_MAX_RADIUS_KM);
-}
-
-// the leg of path_metrics between two positions given in degrees
-template <int kModel>
-__device__ __forceinline__ double site_leg_km(double lon1, double lat1, double lon2, double lat2) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double a1 = lat1 * kDeg2Rad, a2 = lat2 * kDeg2Rad;
-        return sphere_dist_km(lon1 * kDeg2Rad, a1, cos(a1), lon2 * kDeg2Rad, a2, cos(a2));
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (lon1 + lat1 + lon2 + lat2) * 0.0;
-        return wgs84_leg(lon1, lat1, lon2, lat2).dist_km + poison;
-    }
+    return !(is_finite(X) && is_finite(Y) && R >= 0.0 && R <= STE_ENCOUNTER_MAX_RADIUS_KM);
 }
 
 template <int kModel, bool kWithin>
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STE_SITE_WAV
     int nbroken = 0;
 
     const double t0 = p.t0 ? p.t0[t] : 0.0;
-    bool tbad = !finite(t0);
+    bool tbad = !is_finite(t0);
     const int ns = tbad ? 0 : min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     const double* dtp = p.dt + t;
@@ -147,12 +131,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STE_SITE_WAV
             plon = st[(r * 4) * ld];
             plat = st[(r * 4 + 1) * ld];
         }
-        if (!(dtk >= 0.0 && finite(dtk))) tbad = true;
+        if (!(dtk >= 0.0 && is_finite(dtk))) tbad = true;
         const double lo = t0 + T, T1 = T + dtk, hi = t0 + T1;
         const double len = hi - lo;
         const double delta = wrap180(lon1 - lon);
         const bool examined = hi > lo;
-        const bool sound = examined && fabs(delta) < 90.0 && finite(lat) && finite(lat1);
+        const bool sound = examined && fabs(delta) < 90.0 && is_finite(lat) && is_finite(lat1);
         if (examined && !sound) ++nbroken;
         if (sound) {
             sound_time = sound_time + len;
@@ -249,7 +233,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STE_SITE_WAV
             const int m = m0 + j;
             const double x = spx[j][lane], y = spy[j][lane];
             double d = nan;
-            if (x == x) d = site_leg_km<kModel>(x, y, p.sites[m], p.sites[(size_t)M + m]);
+            if (x == x) d = leg_km_deg<kModel>(x, y, p.sites[m], p.sites[(size_t)M + m]);
             p.min_dist[(s * (size_t)M + (size_t)m) * ld + t] = d;
         }
     }

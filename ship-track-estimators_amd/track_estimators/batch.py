@@ -414,6 +414,46 @@ def pack_uniform(sb, substeps: int, H, Q, R, P0) -> HostBatch:
 # ----------------------------------------------------------------------------------------------------------------
 # device side
 # ----------------------------------------------------------------------------------------------------------------
+def states_in_place(shape, strides, Nmax: int, ld: int) -> bool:
+    """Are the rows of a (S, Nmax+1, 4, B) tensor with these strides (in elements) the rows of a fleet ``ld`` tracks wide, so
+    that a metric call can read it where it lies?  The stride of a dimension of size 1 is never used and is ignored."""
+    fleet_strides = ((Nmax + 1) * 4 * ld, 4 * ld, ld, 1)
+    return all(n == 1 or sd == fd for n, sd, fd in zip(shape, strides, fleet_strides))
+
+
+def _metric_model(model) -> int:
+    """STE_PREP_* of a leg function's name."""
+    if model not in DeviceBatch._PATH_MODELS:
+        raise ValueError(f"model must be one of {sorted(DeviceBatch._PATH_MODELS)}, got {model!r}")
+    return DeviceBatch._PATH_MODELS[model]
+
+
+def _index_tensor(x, name: str, tail_shape: tuple, limit: int):
+    """A list of track indices (``pairs`` (P, 2), ``qtrack`` (Q,)) given as an integer array or tensor, as an integer
+    tensor of shape (n,) + ``tail_shape`` with 1 <= n <= ``limit``; an array comes back as int64 on the host."""
+    import torch
+
+    letter = name[0].upper()
+    shape = "(" + ", ".join([letter] + [str(n) for n in tail_shape]) + ("," if not tail_shape else "") + ")"
+    if not isinstance(x, torch.Tensor):
+        x = np.asarray(x)
+        if x.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be a {shape} integer array or tensor, got dtype {x.dtype}")
+        x = torch.from_numpy(np.ascontiguousarray(x.astype(np.int64)))
+    elif x.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"{name} must be a {shape} integer array or tensor, got dtype {x.dtype}")
+    if x.dim() != 1 + len(tail_shape) or tuple(x.shape[1:]) != tuple(tail_shape) or not 1 <= x.shape[0] <= limit:
+        raise ValueError(f"{name} must have shape {shape} with 1 <= {letter} <= {limit}, got {tuple(x.shape)}")
+    return x
+
+
+def _index_int32(x):
+    """An integer tensor as contiguous int32 for a kernel: an index that does not fit 32 bits stays outside [0, B)."""
+    import torch
+
+    return x.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+
+
 class DeviceBatch:
     """A HostBatch resident in HBM plus its output buffers; ``forward`` / ``backward`` / ``run`` launch the kernels."""
 
@@ -600,6 +640,81 @@ class DeviceBatch:
         self._last_use = self.torch.cuda.Event()
         self._last_use.record(stream)
 
+    # -- the front end the metric calls share ("Metric front end") ---------------------------------------
+    _PATH_MODELS = {"sphere": binding.STE_PREP_SPHERE, "wgs84": binding.STE_PREP_WGS84}
+    _PATH_AXES = {"lon": 0, "lat": 1}
+
+    def _ordered_stream(self, stream):
+        """The stream a call runs on (default: the current one), ordered after the current stream's work, the batch's
+        upload and the pipeline that last ran it."""
+        cur = self.torch.cuda.current_stream(self.device)
+        st = cur if stream is None else stream
+        if st is not cur:
+            st.wait_stream(cur)  # whatever the caller queued on the current stream (inputs, histories) comes first
+        st.wait_event(self._uploaded)
+        if self._pipeline_done is not None:
+            st.wait_event(self._pipeline_done)
+        return st
+
+    def _metric_states(self, states):
+        """``states`` of a metric call as (S, Nmax+1, 4, B), and S."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
+            raise ValueError(want)
+        if states.dim() == 3:
+            states = states.unsqueeze(0)
+        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
+            raise ValueError(want + f", got {tuple(states.shape)}")
+        return states, int(states.shape[0])
+
+    def _fleet_layout(self, states, keep, needs_dt: bool):
+        """How a metric call reads ``states``: in place when the tensor's rows are the fleet's (ld tracks wide, this window's
+        columns), else as a batch of its own, made contiguous.  Returns (a copy of the batch struct for the call, states,
+        the width of a row of per-track outputs, this batch's first column in it).  ``needs_dt``: the call reads ``dt``,
+        the one batch array read in rows of track_stride, so a window that is not read in place gets a copy of its
+        columns.  Inside the stream context; what the call must outlive is appended to ``keep``."""
+        N, B = int(self.struct.Nmax), self.ntracks
+        ld = int(self.struct.track_stride or self.struct.B)
+        s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+        keep.append(states)
+        if states_in_place(states.shape, states.stride(), N, ld):
+            return s, states, ld, self.lo
+        states = states.contiguous()
+        s.track_stride = 0
+        keep.append(states)
+        if needs_dt and ld != B:
+            dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
+            s.dt = dt.data_ptr()
+            keep.append(dt)
+        return s, states, B, 0
+
+    def _track_clock(self, t0, width, col, keep):
+        """``t0`` of a metric call (None, a scalar or one clock time per track) as the pointer the kernel takes, or None.
+        Inside the stream context."""
+        if t0 is None:
+            return None
+        torch, B = self.torch, self.ntracks
+        tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
+        if tv.dim() == 0:
+            tv = tv.expand(B)
+        if tuple(tv.shape) != (B,):
+            raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+        clock = torch.zeros((width,), dtype=torch.float64, device=self.device)
+        clock[col:col + B] = tv
+        keep.append(clock)
+        return clock.data_ptr() + 8 * col
+
+    def _finish(self, st, keep, out):
+        """After the launch: inputs and outputs stay allocated until ``st`` has passed it."""
+        for ten in keep:
+            ten.record_stream(st)
+        self._mark_use(st)
+        for ten in out.values():
+            ten.record_stream(st)
+        return out
+
     @staticmethod
     def slice_bounds(nsteps: int, slices: int):
         """Step ranges of a forward pass cut into ``slices`` time slices: boundaries on multiples of STE_SLICE_ALIGN (64
@@ -664,13 +779,7 @@ class DeviceBatch:
         a track's last step.  ``stream``: the stream the pass runs on (default: the current one); it is ordered after the
         current stream's work and the batch's upload, and the results are read back on it once the pass is done."""
         torch = self.torch
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)  # whatever the caller queued on the current stream (inputs, histories) comes first
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         B, N = self.ntracks, int(self.struct.Nmax)
         ld = int(self.struct.track_stride or self.struct.B)
         col = self.lo  # a window's first column in rows of `ld` (0 for a batch of its own)
@@ -725,13 +834,7 @@ class DeviceBatch:
         if S < 1:
             raise ValueError(f"nsamples must be >= 1, got {nsamples!r}")
         ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         with torch.cuda.stream(st):
             if draws is None:
                 gen = torch.Generator(device=self.device)
@@ -760,9 +863,6 @@ class DeviceBatch:
         return out
 
     # -- path quantities ------------------------------------------------------------------------------------------
-    _PATH_MODELS = {"sphere": binding.STE_PREP_SPHERE, "wgs84": binding.STE_PREP_WGS84}
-    _PATH_AXES = {"lon": 0, "lat": 1}
-
     def path_metrics(self, states, model: str = "sphere", cumulative: bool = False, line_axis=None, line_value=None,
                      stream=None):
         """Distance sailed and, given a line, the time of its first crossing, for tracks that are on the device
@@ -780,50 +880,21 @@ class DeviceBatch:
         same bits.  ``stream`` is ordered as in ``sample_smoothed``."""
         torch = self.torch
         N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         if line_axis is not None and line_axis not in self._PATH_AXES:
             raise ValueError(f"line_axis must be None, 'lon' or 'lat', got {line_axis!r}")
         if (line_axis is None) != (line_value is None):
             raise ValueError("line_axis and line_value go together: a line is an axis ('lon' / 'lat') and its value in degrees")
-        S = int(states.shape[0])
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         with torch.cuda.stream(st):
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if line_axis is not None and ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = []
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=line_axis is not None)
             dist = torch.empty((S, width), **f64)
             cum = torch.full((S, N + 1, width), float("nan"), **f64) if cumulative else None
             pm = binding.StePathF64()
-            pm.nstates, pm.model, pm.states = S, self._PATH_MODELS[model], states.data_ptr()
+            pm.nstates, pm.model, pm.states = S, model_id, states.data_ptr()
             pm.dist = dist.data_ptr() + 8 * col
             pm.cumdist = None if cum is None else cum.data_ptr() + 8 * col
             pm.line_axis, pm.reserved = -1, 0
@@ -842,17 +913,12 @@ class DeviceBatch:
                 pm.cross_time, pm.ncross = ct.data_ptr() + 8 * col, nc.data_ptr() + 4 * col
                 keep.append(line)
             binding.check(self.lib.ste_path_metrics_f64(C.byref(s), C.byref(pm), self._stream(st)), "ste_path_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
             out = {"distance": dist[:, col:col + B]}
             if cum is not None:
                 out["cumulative"] = cum[..., col:col + B]
             if ct is not None:
                 out["cross_time"], out["ncross"] = ct[:, col:col + B], nc[:, col:col + B]
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- regions --------------------------------------------------------------------------------------------------
     def region_metrics(self, states, polygon, model: str = "sphere", distance: bool = False, mask: bool = False, stream=None):
@@ -869,69 +935,36 @@ class DeviceBatch:
         polygon alone."""
         torch = self.torch
         N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         poly = polygon if isinstance(polygon, RegionPolygon) else region_polygon(polygon)
-        S, V = int(states.shape[0]), int(poly.vert.shape[1])
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        V = int(poly.vert.shape[1])
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         with torch.cuda.stream(st):
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
             vert = torch.from_numpy(poly.vert).to(self.device)
-            keep = [states, vert]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = [vert]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
             tin, first = torch.empty((S, width), **f64), torch.empty((S, width), **f64)
             nent, nbrk = torch.empty((S, width), **i32), torch.empty((S, width), **i32)
             din = torch.empty((S, width), **f64) if distance else None
             flags = torch.zeros((S, N + 1, width), dtype=torch.uint8, device=self.device) if mask else None
             rg = binding.SteRegionF64()
-            rg.nstates, rg.model, rg.states = S, self._PATH_MODELS[model], states.data_ptr()
+            rg.nstates, rg.model, rg.states = S, model_id, states.data_ptr()
             rg.nvert, rg.reserved, rg.vert, rg.lon_ref = V, 0, vert.data_ptr(), float(poly.lon_ref)
             rg.time_inside, rg.first_entry = tin.data_ptr() + 8 * col, first.data_ptr() + 8 * col
             rg.nenter, rg.nbroken = nent.data_ptr() + 4 * col, nbrk.data_ptr() + 4 * col
             rg.dist_inside = None if din is None else din.data_ptr() + 8 * col
             rg.inside = None if flags is None else flags.data_ptr() + col
             binding.check(self.lib.ste_region_metrics_f64(C.byref(s), C.byref(rg), self._stream(st)), "ste_region_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
             out = {"time_inside": tin[:, col:col + B], "first_entry": first[:, col:col + B], "nenter": nent[:, col:col + B],
                    "nbroken": nbrk[:, col:col + B]}
             if din is not None:
                 out["dist_inside"] = din[:, col:col + B]
             if flags is not None:
                 out["inside"] = flags[..., col:col + B]
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- grids ----------------------------------------------------------------------------------------------------
     def grid_metrics(self, states, grid, entries: bool = False, out=None, stream=None):
@@ -946,17 +979,11 @@ class DeviceBatch:
         the grid's bits do not depend on how the tracks were split into calls.  Windows, in-place views and ``stream`` as in
         ``path_metrics``."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
+        B = self.ntracks
+        states, S = self._metric_states(states)
         if not isinstance(grid, TrackGrid):
             raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
-        S, nx, ny = int(states.shape[0]), grid.nx, grid.ny
+        nx, ny = grid.nx, grid.ny
         i64 = dict(dtype=torch.int64, device=self.device)
         if out is not None:
             ticks, ent = out.get("ticks"), out.get("entries")
@@ -964,36 +991,15 @@ class DeviceBatch:
                 if (not isinstance(ten, torch.Tensor) or ten.dtype != torch.int64 or ten.device != self.device
                         or tuple(ten.shape) != (ny, nx) or not ten.is_contiguous()):
                     raise ValueError(f"out[{name!r}] must be a contiguous int64 tensor of shape ({ny}, {nx}) on {self.device}")
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         with torch.cuda.stream(st):
             if out is None:
                 ticks = torch.zeros((ny, nx), **i64)
                 ent = torch.zeros((ny, nx), **i64) if entries else None
             elif not entries:
                 ent = None
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, ticks] + ([ent] if ent is not None else [])
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = [ticks] + ([ent] if ent is not None else [])
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
             outside, total = torch.zeros((S, width), **i64), torch.zeros((S, width), **i64)
             nbrk = torch.zeros((S, width), dtype=torch.int32, device=self.device)
             g = binding.SteGridF64()
@@ -1002,16 +1008,11 @@ class DeviceBatch:
             g.ticks, g.entries = ticks.data_ptr(), None if ent is None else ent.data_ptr()
             g.outside, g.total, g.nbroken = outside.data_ptr() + 8 * col, total.data_ptr() + 8 * col, nbrk.data_ptr() + 4 * col
             binding.check(self.lib.ste_grid_metrics_f64(C.byref(s), C.byref(g), self._stream(st)), "ste_grid_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
             res = {"ticks": ticks, "hours": ticks.to(torch.float64) / float(binding.STE_GRID_TICKS_PER_HOUR),
                    "outside": outside[:, col:col + B], "total": total[:, col:col + B], "nbroken": nbrk[:, col:col + B]}
             if ent is not None:
                 res["entries"] = ent
-            for ten in res.values():
-                ten.record_stream(st)
-        return res
+            return self._finish(st, keep, res)
 
     # -- encounters -----------------------------------------------------------------------------------------------
     def encounter_metrics(self, states, pairs, radius_km, t0=None, model: str = "sphere", stream=None):
@@ -1031,71 +1032,24 @@ class DeviceBatch:
         views and ``stream`` as in ``path_metrics``; every value depends on the two tracks' rows, ``dt``, ``t0`` and the
         radius alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         radius_km = float(radius_km)
         if not (np.isfinite(radius_km) and 0.0 <= radius_km <= binding.STE_ENCOUNTER_MAX_RADIUS_KM):
             raise ValueError(f"radius_km must be finite and between 0 and {binding.STE_ENCOUNTER_MAX_RADIUS_KM:g}, got {radius_km!r}")
-        if not isinstance(pairs, torch.Tensor):
-            pairs = np.asarray(pairs)
-            if pairs.dtype.kind not in "iu":
-                raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
-            pairs = torch.from_numpy(np.ascontiguousarray(pairs.astype(np.int64)))
-        elif pairs.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-            raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
-        if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= binding.STE_ENCOUNTER_MAX_PAIRS:
-            raise ValueError(f"pairs must have shape (P, 2) with 1 <= P <= {binding.STE_ENCOUNTER_MAX_PAIRS}, got {tuple(pairs.shape)}")
-        S, P = int(states.shape[0]), int(pairs.shape[0])
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        pairs = _index_tensor(pairs, "pairs", (2,), binding.STE_ENCOUNTER_MAX_PAIRS)
+        P = int(pairs.shape[0])
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         with torch.cuda.stream(st):
-            # an index that does not fit 32 bits stays outside [0, B)
-            pr = pairs.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, pr]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            pr = _index_int32(pairs.to(self.device))
+            keep = [pr]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
             en = binding.SteEncounterF64()
-            en.nstates, en.model, en.states = S, self._PATH_MODELS[model], states.data_ptr()
+            en.nstates, en.model, en.states = S, model_id, states.data_ptr()
             en.npairs, en.pairs, en.radius_km, en.flags, en.reserved = P, pr.data_ptr(), radius_km, 0, 0
-            if t0 is not None:
-                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
-                if tv.dim() == 0:
-                    tv = tv.expand(B)
-                if tuple(tv.shape) != (B,):
-                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
-                clock = torch.zeros((width,), **f64)
-                clock[col:col + B] = tv
-                en.t0 = clock.data_ptr() + 8 * col
-                keep.append(clock)
+            en.t0 = self._track_clock(t0, width, col, keep)
             out = {k: torch.empty((S, P), **f64) for k in ("min_dist", "min_time", "time_within", "first_within", "overlap")}
             out.update({k: torch.empty((S, P), **i32) for k in ("nwithin", "nbroken")})
             out["status"] = torch.empty((P,), **i32)
@@ -1103,12 +1057,7 @@ class DeviceBatch:
                 setattr(en, k, ten.data_ptr())
             binding.check(self.lib.ste_encounter_metrics_f64(C.byref(s), C.byref(en), self._stream(st)),
                           "ste_encounter_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- positions at query times ---------------------------------------------------------------------------------
     def positions_at(self, states, qtrack, qtime, t0=None, velocity: bool = False, anchor=None, accumulate=None, knots=None,
@@ -1131,23 +1080,9 @@ class DeviceBatch:
         takes the list as it is.  No value depends on the order.  Windows, in-place views and ``stream`` as in ``path_metrics``."""
         torch = self.torch
         N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if not isinstance(qtrack, torch.Tensor):
-            qtrack = np.asarray(qtrack)
-            if qtrack.dtype.kind not in "iu":
-                raise ValueError(f"qtrack must be a (Q,) integer array or tensor, got dtype {qtrack.dtype}")
-            qtrack = torch.from_numpy(np.ascontiguousarray(qtrack.astype(np.int64)))
-        elif qtrack.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-            raise ValueError(f"qtrack must be a (Q,) integer array or tensor, got dtype {qtrack.dtype}")
-        if qtrack.dim() != 1 or not 1 <= qtrack.shape[0] <= binding.STE_POSITIONS_MAX_QUERIES:
-            raise ValueError(f"qtrack must have shape (Q,) with 1 <= Q <= {binding.STE_POSITIONS_MAX_QUERIES}, got {tuple(qtrack.shape)}")
-        S, Q = int(states.shape[0]), int(qtrack.shape[0])
+        states, S = self._metric_states(states)
+        qtrack = _index_tensor(qtrack, "qtrack", (), binding.STE_POSITIONS_MAX_QUERIES)
+        Q = int(qtrack.shape[0])
         qtime = torch.as_tensor(qtime, dtype=torch.float64)
         if tuple(qtime.shape) != (Q,):
             raise ValueError(f"qtime must have shape ({Q},) like qtrack, got {tuple(qtime.shape)}")
@@ -1167,54 +1102,23 @@ class DeviceBatch:
         if knots is not None and not (isinstance(knots, torch.Tensor) and knots.dtype == torch.float64 and knots.device == self.device
                                       and tuple(knots.shape) == (N + 1, B)):
             raise ValueError(f"knots must be the float64 ({N + 1}, {B}) tensor a previous call on this batch returned")
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         with torch.cuda.stream(st):
-            # an index that does not fit 32 bits stays outside [0, B)
-            qt = qtrack.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+            qt = _index_int32(qtrack.to(self.device))
             tq = qtime.to(self.device).contiguous()
             perm = None
             if sort and Q > 1:
                 by_time = torch.sort(tq, stable=True).indices
                 perm = by_time[torch.sort(qt[by_time], stable=True).indices]
                 qt, tq = qt[perm].contiguous(), tq[perm].contiguous()
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, qt, tq]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B and knots is None:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = [qt, tq]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=knots is None)  # given knots, dt is not read
             po = binding.StePositionsF64()
             po.nstates, po.flags, po.states = S, 0, states.data_ptr()
             po.nqueries, po.qtrack, po.qtime = Q, qt.data_ptr(), tq.data_ptr()
-            if t0 is not None:
-                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
-                if tv.dim() == 0:
-                    tv = tv.expand(B)
-                if tuple(tv.shape) != (B,):
-                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
-                clock = torch.zeros((width,), **f64)
-                clock[col:col + B] = tv
-                po.t0 = clock.data_ptr() + 8 * col
-                keep.append(clock)
+            po.t0 = self._track_clock(t0, width, col, keep)
             if knots is not None and knots.stride() == (width, 1):
                 kn = knots  # the view a call of the same kind returned: read where it lies
                 po.knots = kn.data_ptr()
@@ -1262,12 +1166,7 @@ class DeviceBatch:
                     cnt, mom = accumulate
                 out["count"], out["moments"] = cnt, mom
             out["knots"] = kn
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- fixed sites ----------------------------------------------------------------------------------------------
     _SITE_OUT3 = ("min_dist", "min_time", "time_within", "first_within", "longest")
@@ -1287,67 +1186,30 @@ class DeviceBatch:
         views and ``stream`` as in ``path_metrics``; for a window read in place the per-track outputs are views of rows as
         wide as the fleet's.  Every value depends on the track's rows, ``dt``, ``t0`` and the site's three numbers alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        B = self.ntracks
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         sv = torch.as_tensor(sites, dtype=torch.float64)
         if sv.dim() != 2 or sv.shape[1] != 2 or not 1 <= sv.shape[0] <= binding.STE_SITES_MAX:
             raise ValueError(f"sites must have shape (M, 2) (lon, lat) with 1 <= M <= {binding.STE_SITES_MAX}, got {tuple(sv.shape)}")
-        S, M = int(states.shape[0]), int(sv.shape[0])
+        M = int(sv.shape[0])
         rv = torch.as_tensor(radius_km, dtype=torch.float64)
         if rv.dim() == 0:
             rv = rv.expand(M)
         if tuple(rv.shape) != (M,):
             raise ValueError(f"radius_km must be a scalar or have shape ({M},), got {tuple(rv.shape)}")
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         with torch.cuda.stream(st):
             xy = sv.to(self.device).t().contiguous()  # [2][M]: lon then lat
             rad = rv.to(self.device).contiguous()
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, xy, rad]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = [xy, rad]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
             si = binding.SteSiteF64()
-            si.nstates, si.model, si.states = S, self._PATH_MODELS[model], states.data_ptr()
+            si.nstates, si.model, si.states = S, model_id, states.data_ptr()
             si.nsites, si.sites, si.radius_km, si.flags, si.reserved = M, xy.data_ptr(), rad.data_ptr(), 0, 0
-            if t0 is not None:
-                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
-                if tv.dim() == 0:
-                    tv = tv.expand(B)
-                if tuple(tv.shape) != (B,):
-                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
-                clock = torch.zeros((width,), **f64)
-                clock[col:col + B] = tv
-                si.t0 = clock.data_ptr() + 8 * col
-                keep.append(clock)
+            si.t0 = self._track_clock(t0, width, col, keep)
             # rows as wide as the states': the window's columns are what the call writes and what is returned
             full = {k: torch.empty((S, M, width), **f64) for k in self._SITE_OUT3}
             full["nwithin"] = torch.empty((S, M, width), **i32)
@@ -1360,12 +1222,7 @@ class DeviceBatch:
             out["site_status"] = torch.empty((M,), **i32)
             si.site_status = out["site_status"].data_ptr()
             binding.check(self.lib.ste_site_metrics_f64(C.byref(s), C.byref(si), self._stream(st)), "ste_site_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- polylines ------------------------------------------------------------------------------------------------
     _LINE_OUT3 = {"min_dist": False, "min_time": False, "min_seg": True, "min_frac": False}  # name -> int32?
@@ -1386,60 +1243,23 @@ class DeviceBatch:
         ``line_status`` (M,) int32, STE_LINE_BAD_LINE.  Windows, in-place views and ``stream`` as in ``site_metrics``.  Every
         value depends on the track's rows, ``dt``, ``t0`` and the line's vertices alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        B = self.ntracks
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         tl = lines if isinstance(lines, TrackLines) else track_lines(lines)
-        S, M, V = int(states.shape[0]), tl.nlines, int(tl.vert.shape[1])
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
+        M, V = tl.nlines, int(tl.vert.shape[1])
+        st = self._ordered_stream(stream)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         with torch.cuda.stream(st):
             vert, first, ref = tl.on(self.device)
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, vert, first, ref]
-            if in_place:
-                width, col = ld, self.lo
-            else:
-                states = states.contiguous()
-                width, col = B, 0
-                s.track_stride = 0
-                keep.append(states)
-                if ld != B:  # dt is the one batch array the call reads in rows of track_stride
-                    dt = self.t["dt"][:, self.lo:self.lo + B].contiguous()
-                    s.dt = dt.data_ptr()
-                    keep.append(dt)
+            keep = [vert, first, ref]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
             li = binding.SteLineF64()
-            li.nstates, li.model, li.states = S, self._PATH_MODELS[model], states.data_ptr()
+            li.nstates, li.model, li.states = S, model_id, states.data_ptr()
             li.nlines, li.nvert, li.vert, li.first, li.lon_ref = M, V, vert.data_ptr(), first.data_ptr(), ref.data_ptr()
             li.flags, li.reserved = 0, 0
-            if t0 is not None:
-                tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
-                if tv.dim() == 0:
-                    tv = tv.expand(B)
-                if tuple(tv.shape) != (B,):
-                    raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
-                clock = torch.zeros((width,), **f64)
-                clock[col:col + B] = tv
-                li.t0 = clock.data_ptr() + 8 * col
-                keep.append(clock)
+            li.t0 = self._track_clock(t0, width, col, keep)
             # rows as wide as the states': the window's columns are what the call writes and what is returned
             names = dict(self._LINE_OUT3)
             if crossings:
@@ -1454,12 +1274,7 @@ class DeviceBatch:
             out["line_status"] = torch.empty((M,), **i32)
             li.line_status = out["line_status"].data_ptr()
             binding.check(self.lib.ste_line_metrics_f64(C.byref(s), C.byref(li), self._stream(st)), "ste_line_metrics_f64")
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            return self._finish(st, keep, out)
 
     # -- routes: pairs of tracks as curves ------------------------------------------------------------------------
     def route_metrics(self, states, pairs, dtw: bool = False, band: int = 0, reverse: bool = False, model: str = "sphere",
@@ -1477,59 +1292,20 @@ class DeviceBatch:
         more than ``ste_route_lds_cols()`` rows is allocated here.  Windows, in-place views and ``stream`` as in
         ``path_metrics``; every value depends on the two tracks' rows, ``band`` and ``reverse`` alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
-        want = f"states must be a float64 tensor of shape (S, {N + 1}, 4, {B}) or ({N + 1}, 4, {B}) on {self.device}"
-        if not isinstance(states, torch.Tensor) or states.dtype != torch.float64 or states.device != self.device:
-            raise ValueError(want)
-        if states.dim() == 3:
-            states = states.unsqueeze(0)
-        if states.dim() != 4 or tuple(states.shape[1:]) != (N + 1, 4, B) or states.shape[0] < 1:
-            raise ValueError(want + f", got {tuple(states.shape)}")
-        if model not in self._PATH_MODELS:
-            raise ValueError(f"model must be one of {sorted(self._PATH_MODELS)}, got {model!r}")
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
         band = int(band)
         if not 0 <= band < 2 ** 31:
             raise ValueError(f"band must be >= 0 (0 = no band) and below 2^31, got {band!r}")
-        if not isinstance(pairs, torch.Tensor):
-            pairs = np.asarray(pairs)
-            if pairs.dtype.kind not in "iu":
-                raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
-            pairs = torch.from_numpy(np.ascontiguousarray(pairs.astype(np.int64)))
-        elif pairs.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-            raise ValueError(f"pairs must be a (P, 2) integer array or tensor, got dtype {pairs.dtype}")
-        if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= binding.STE_ROUTE_MAX_PAIRS:
-            raise ValueError(f"pairs must have shape (P, 2) with 1 <= P <= {binding.STE_ROUTE_MAX_PAIRS}, got {tuple(pairs.shape)}")
-        S, P = int(states.shape[0]), int(pairs.shape[0])
-        ld = int(self.struct.track_stride or self.struct.B)
-        cur = torch.cuda.current_stream(self.device)
-        st = cur if stream is None else stream
-        if st is not cur:
-            st.wait_stream(cur)
-        st.wait_event(self._uploaded)
-        if self._pipeline_done is not None:
-            st.wait_event(self._pipeline_done)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        pairs = _index_tensor(pairs, "pairs", (2,), binding.STE_ROUTE_MAX_PAIRS)
+        st = self._ordered_stream(stream)
         with torch.cuda.stream(st):
-            # an index that does not fit 32 bits stays outside [0, B)
-            pr = pairs.to(self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
-            # in place when the tensor's rows are the fleet's (ld tracks wide, this window's columns); else a batch of its own
-            fleet_strides = ((N + 1) * 4 * ld, 4 * ld, ld, 1)
-            in_place = all(n == 1 or sd == fd for n, sd, fd in zip(states.shape, states.stride(), fleet_strides))
-            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            keep = [states, pr]
-            if not in_place:
-                states = states.contiguous()
-                s.track_stride = 0
-                keep.append(states)
-            out = _route_call(self.lib, torch, s, states, S, pr, dtw, band, reverse, self._PATH_MODELS[model], self.device,
-                              self._stream(st), keep)
-            for ten in keep:
-                ten.record_stream(st)
-            self._mark_use(st)
-            for ten in out.values():
-                ten.record_stream(st)
-        return out
+            pr = _index_int32(pairs.to(self.device))
+            keep = [pr]
+            s, states, _, _ = self._fleet_layout(states, keep, needs_dt=False)  # a curve has no clock
+            out = _route_call(self.lib, torch, s, states, S, pr, dtw, band, reverse, model_id, self.device, self._stream(st),
+                              keep)
+            return self._finish(st, keep, out)
 
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
@@ -2533,6 +2309,52 @@ def sample_tracks(hb_or_db, nsamples: int, seed: int = 0, device="cuda:0"):
     return dev_t.cpu().numpy(), status
 
 
+def _posterior_batch(hb_or_db, nsamples, chunk, device, who: str):
+    """What a ``*_statistics`` function samples from: a ``HostBatch`` is uploaded and ``run()``, a ``DeviceBatch`` (or a
+    window of one) is taken to hold a completed ``run()``.  Returns (batch, nsamples, chunk), the two as checked ints."""
+    nsamples, chunk = int(nsamples), int(chunk)
+    if nsamples < 1 or chunk < 1:
+        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device)
+        db.run()
+    if db.sm_mean is None:
+        raise ValueError(f"{who}() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    return db, nsamples, chunk
+
+
+class _PosteriorChunks:
+    """The posterior-sampling loop of the ``*_statistics`` functions: ``nsamples`` posterior tracks of ``db``, ``chunk`` at
+    a time.  Iterating yields (i, n, samples): samples i .. i+n-1 as ``sample_smoothed`` returned them, in the one draw
+    buffer of ``min(chunk, nsamples)`` samples, so a chunk is gone when the next is drawn.  One generator, seeded once,
+    fills the buffer chunk after chunk: the draws depend on ``(seed, chunk)``, and with ``chunk >= nsamples`` they are those
+    of ``sample_smoothed(nsamples, seed)``.  ``draws(z, i)``, if given, fills a chunk's buffer ``z`` with the standard
+    normal draws of samples i .. i+n-1 in place of the generator.  ``status`` (B,) int32 gathers the sampler's STE_STATUS_*
+    bits, after the loop body has run for the chunk."""
+
+    def __init__(self, db: DeviceBatch, nsamples: int, seed: int, chunk: int, draws=None):
+        torch = db.torch
+        self.db, self.nsamples, self.chunk, self.draws = db, nsamples, chunk, draws
+        self.gen = torch.Generator(device=db.device)
+        self.gen.manual_seed(int(seed))
+        self.buf = torch.empty((min(chunk, nsamples), int(db.struct.Nmax) + 1, 4, db.ntracks), dtype=torch.float64,
+                               device=db.device)
+        self.status = torch.zeros((db.ntracks,), dtype=torch.int32, device=db.device)
+
+    def __iter__(self):
+        for i in range(0, self.nsamples, self.chunk):
+            n = min(self.chunk, self.nsamples - i)
+            z = self.buf[:n]
+            if self.draws is None:
+                z.normal_(generator=self.gen)
+            else:
+                self.draws(z, i)
+            yield i, n, self.db.sample_smoothed(n, draws=z)
+            self.status |= self.db.sample_status
+
+
 def path_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, model: str = "sphere", line_axis=None,
                     line_value=None, quantiles=(0.05, 0.5, 0.95), device="cuda:0"):
     """Distance sailed -- and, given a line, the time of its first crossing -- with the uncertainty of the smoothing posterior,
@@ -2554,35 +2376,20 @@ def path_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, mod
     a ``chunk``-sample buffer.  With ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("path_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "path_statistics")
     torch = db.torch
-    N, B = int(db.struct.Nmax), db.ntracks
+    B = db.ntracks
     line = dict(line_axis=line_axis, line_value=line_value)
     smoothed = db.path_metrics(db.sm_mean, model=model)["distance"][0]
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), dtype=torch.float64, device=db.device)
     dist = torch.empty((nsamples, B), dtype=torch.float64, device=db.device)
     ctime = torch.empty((nsamples, B), dtype=torch.float64, device=db.device) if line_axis is not None else None
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        draws = buf[:n]
-        draws.normal_(generator=gen)
-        m = db.path_metrics(db.sample_smoothed(n, draws=draws), model=model, **line)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for i, n, samples in chunks:
+        m = db.path_metrics(samples, model=model, **line)
         dist[i:i + n] = m["distance"]
         if ctime is not None:
             ctime[i:i + n] = m["cross_time"]
-        status |= db.sample_status
+    status = chunks.status
     q = np.asarray(quantiles, dtype=np.float64)
     d = dist.cpu().numpy()
     out = {"distance_smoothed": smoothed.cpu().numpy(), "distance": d, "distance_mean": d.mean(axis=0),
@@ -2656,40 +2463,25 @@ def region_statistics(hb_or_db, polygon, nsamples: int, seed: int = 0, chunk: in
     the sampler's STE_STATUS_* bits."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
     poly = polygon if isinstance(polygon, RegionPolygon) else region_polygon(polygon)
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("region_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "region_statistics")
     torch = db.torch
     N, B = int(db.struct.Nmax), db.ntracks
     kw = dict(model=model, distance=distance, mask=True)
     smoothed = db.region_metrics(db.sm_mean, poly, **kw)
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
     f64 = dict(dtype=torch.float64, device=db.device)
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
     tin, first = torch.empty((nsamples, B), **f64), torch.empty((nsamples, B), **f64)
     nent = torch.empty((nsamples, B), dtype=torch.int32, device=db.device)
     din = torch.empty((nsamples, B), **f64) if distance else None
     count = torch.zeros((N + 1, B), dtype=torch.int32, device=db.device)
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        draws = buf[:n]
-        draws.normal_(generator=gen)
-        m = db.region_metrics(db.sample_smoothed(n, draws=draws), poly, **kw)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for i, n, samples in chunks:
+        m = db.region_metrics(samples, poly, **kw)
         tin[i:i + n], first[i:i + n], nent[i:i + n] = m["time_inside"], m["first_entry"], m["nenter"]
         if din is not None:
             din[i:i + n] = m["dist_inside"]
         count += m["inside"].sum(dim=0, dtype=torch.int32)
-        status |= db.sample_status
+    status = chunks.status
     q = np.asarray(quantiles, dtype=np.float64)
     t, fe, ne = tin.cpu().numpy(), first.cpu().numpy(), nent.cpu().numpy()
     nsteps = db.t["nsteps"][db.lo:db.lo + B].cpu().numpy()
@@ -2775,43 +2567,29 @@ def grid_statistics(hb_or_db, grid: TrackGrid, nsamples: int, seed: int = 0, chu
     ``entries`` also ``entries_mean`` (ny, nx), entries per cell and sample; ``outside_hours`` (nsamples, B), the time of
     each sampled track off the grid; ``total_ticks`` (nsamples, B) int64, the ticks of each sampled track's sound steps;
     ``nbroken`` (nsamples, B) int32; and ``status`` (B,), the sampler's STE_STATUS_* bits."""
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
     if not isinstance(grid, TrackGrid):
         raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
     if isinstance(hb_or_db, (list, tuple)):
         dbs = list(hb_or_db)
         if not dbs or not all(isinstance(d, DeviceBatch) for d in dbs):
             raise ValueError("a list given to grid_statistics() must hold DeviceBatch windows, and at least one")
-    elif isinstance(hb_or_db, DeviceBatch):
-        dbs = [hb_or_db]
     else:
-        dbs = [DeviceBatch(hb_or_db, device=device)]
-        dbs[0].run()
+        dbs = [hb_or_db]
     smoothed = acc = None
     per_track = []
     for db in dbs:
-        if db.sm_mean is None:
-            raise ValueError("grid_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+        db, nsamples, chunk = _posterior_batch(db, nsamples, chunk, device, "grid_statistics")
         torch = db.torch
-        N, B = int(db.struct.Nmax), db.ntracks
+        B = db.ntracks
         smoothed = db.grid_metrics(db.sm_mean, grid, out=smoothed)
-        gen = torch.Generator(device=db.device)
-        gen.manual_seed(int(seed))
-        buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), dtype=torch.float64, device=db.device)
         outside = torch.empty((nsamples, B), dtype=torch.int64, device=db.device)
         total = torch.empty((nsamples, B), dtype=torch.int64, device=db.device)
         nbrk = torch.empty((nsamples, B), dtype=torch.int32, device=db.device)
-        status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-        for i in range(0, nsamples, chunk):
-            n = min(chunk, nsamples - i)
-            draws = buf[:n]
-            draws.normal_(generator=gen)
-            acc = db.grid_metrics(db.sample_smoothed(n, draws=draws), grid, entries=entries, out=acc)
+        chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+        for i, n, samples in chunks:
+            acc = db.grid_metrics(samples, grid, entries=entries, out=acc)
             outside[i:i + n], total[i:i + n], nbrk[i:i + n] = acc["outside"], acc["total"], acc["nbroken"]
-            status |= db.sample_status
-        per_track.append((outside.cpu().numpy(), total.cpu().numpy(), nbrk.cpu().numpy(), status.cpu().numpy()))
+        per_track.append((outside.cpu().numpy(), total.cpu().numpy(), nbrk.cpu().numpy(), chunks.status.cpu().numpy()))
     tph = float(binding.STE_GRID_TICKS_PER_HOUR)
     ticks = acc["ticks"].cpu().numpy()
     out = {"hours_smoothed": smoothed["ticks"].cpu().numpy() / tph, "hours_mean": ticks / (tph * nsamples), "ticks": ticks}
@@ -2916,38 +2694,22 @@ def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 
     STE_STATUS_* bits per track."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("encounter_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "encounter_statistics")
     torch = db.torch
-    N, B = int(db.struct.Nmax), db.ntracks
     kw = dict(t0=t0, model=model)
     smoothed = db.encounter_metrics(db.sm_mean, pairs, radius_km, **kw)
     P = int(smoothed["status"].shape[0])
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
     f64 = dict(dtype=torch.float64, device=db.device)
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
     names = ("min_dist", "min_time", "time_within", "first_within")
     acc = {k: torch.empty((nsamples, P), **f64) for k in names}
     nwit = torch.empty((nsamples, P), dtype=torch.int32, device=db.device)
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        draws = buf[:n]
-        draws.normal_(generator=gen)
-        m = db.encounter_metrics(db.sample_smoothed(n, draws=draws), pairs, radius_km, **kw)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for i, n, samples in chunks:
+        m = db.encounter_metrics(samples, pairs, radius_km, **kw)
         for k in names:
             acc[k][i:i + n] = m[k]
         nwit[i:i + n] = m["nwithin"]
-        status |= db.sample_status
+    status = chunks.status
     q = np.asarray(quantiles, dtype=np.float64)
     host = {k: v.cpu().numpy() for k, v in acc.items()}
     nw = nwit.cpu().numpy()
@@ -3009,18 +2771,9 @@ def site_statistics(hb_or_db, sites, radius_km, nsamples: int, seed: int = 0, ch
     B doubles per quantity, and are refused when that exceeds ``max_bytes``."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("site_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "site_statistics")
     torch = db.torch
-    N, B = int(db.struct.Nmax), db.ntracks
+    B = db.ntracks
     M = int(np.shape(sites)[0]) if not isinstance(sites, torch.Tensor) else int(sites.shape[0])
     qnames = ("min_dist", "time_within", "longest")
     if quantiles is not None:
@@ -3030,23 +2783,14 @@ def site_statistics(hb_or_db, sites, radius_km, nsamples: int, seed: int = 0, ch
                              f"max_bytes = {int(max_bytes)}: lower nsamples, split the sites, raise max_bytes or pass quantiles=None")
     kw = dict(t0=t0, model=model)
     smoothed = db.site_metrics(db.sm_mean, sites, radius_km, **kw)
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
     f64 = dict(dtype=torch.float64, device=db.device)
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
     visits, calls, have = (torch.zeros((M, B), dtype=torch.int32, device=db.device) for _ in range(3))
     sums = {k: torch.zeros((M, B), **f64) for k in qnames}
     kept = {k: torch.empty((nsamples, M, B), **f64) for k in qnames} if quantiles is not None else None
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
     stay = float(min_stay_h)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        z = buf[:n]
-        if draws is None:
-            z.normal_(generator=gen)
-        else:
-            draws(z, i)
-        m = db.site_metrics(db.sample_smoothed(n, draws=z), sites, radius_km, **kw)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk, draws=draws)
+    for i, n, samples in chunks:
+        m = db.site_metrics(samples, sites, radius_km, **kw)
         came = m["nwithin"] > 0
         found = ~torch.isnan(m["min_dist"])
         dist = torch.where(found, m["min_dist"], torch.zeros_like(m["min_dist"]))
@@ -3060,7 +2804,7 @@ def site_statistics(hb_or_db, sites, radius_km, nsamples: int, seed: int = 0, ch
         if kept is not None:
             for k in qnames:
                 kept[k][i:i + n] = m[k]
-        status |= db.sample_status
+    status = chunks.status
     out = {k + "_smoothed": smoothed[k][0].cpu().numpy() for k in DeviceBatch._SITE_OUT3 + ("nwithin",)}
     count = have.cpu().numpy()
     out["visit_prob"] = visits.cpu().numpy() / float(nsamples)
@@ -3159,8 +2903,7 @@ def line_chainage(lines, min_seg, min_frac, model: str = "sphere"):
 
     from . import utils
 
-    if model not in DeviceBatch._PATH_MODELS:
-        raise ValueError(f"model must be one of {sorted(DeviceBatch._PATH_MODELS)}, got {model!r}")
+    _metric_model(model)
     tl = track_lines(lines)
     M = tl.nlines
     if min_seg.dim() < 2 or min_seg.shape[-2] != M or min_seg.shape != min_frac.shape:
@@ -3209,19 +2952,10 @@ def line_statistics(hb_or_db, lines, nsamples: int, seed: int = 0, chunk: int = 
     every sample's value, nsamples x M x B doubles per quantity, and are refused when that exceeds ``max_bytes``."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
     tl = track_lines(lines)
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("line_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "line_statistics")
     torch = db.torch
-    N, B, M = int(db.struct.Nmax), db.ntracks, tl.nlines
+    B, M = db.ntracks, tl.nlines
     qnames = ("min_dist", "first_cross")
     if quantiles is not None:
         need = 8 * nsamples * M * B
@@ -3239,21 +2973,12 @@ def line_statistics(hb_or_db, lines, nsamples: int, seed: int = 0, chunk: int = 
         near = near.reshape((M, 1))
     kw = dict(t0=t0, model=model)
     smoothed = db.line_metrics(db.sm_mean, tl, **kw)
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
     crossed, net, have, close = (torch.zeros((M, B), dtype=torch.int32, device=db.device) for _ in range(4))
     sums = {k: torch.zeros((M, B), **f64) for k in qnames}
     kept = {k: torch.empty((nsamples, M, B), **f64) for k in qnames} if quantiles is not None else None
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        z = buf[:n]
-        if draws is None:
-            z.normal_(generator=gen)
-        else:
-            draws(z, i)
-        m = db.line_metrics(db.sample_smoothed(n, draws=z), tl, **kw)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk, draws=draws)
+    for i, n, samples in chunks:
+        m = db.line_metrics(samples, tl, **kw)
         found = ~torch.isnan(m["min_dist"])
         dist = torch.where(found, m["min_dist"], torch.zeros_like(m["min_dist"]))
         came = m["ncross"] > 0
@@ -3269,7 +2994,7 @@ def line_statistics(hb_or_db, lines, nsamples: int, seed: int = 0, chunk: int = 
         if kept is not None:
             for k in qnames:
                 kept[k][i:i + n] = m[k]
-        status |= db.sample_status
+    status = chunks.status
     names = tuple(DeviceBatch._LINE_OUT3) + tuple(DeviceBatch._LINE_CROSS)
     out = {k + "_smoothed": smoothed[k][0].cpu().numpy() for k in names}
     count, ncount = have.cpu().numpy(), crossed.cpu().numpy()
@@ -3392,35 +3117,19 @@ def route_statistics(hb_or_db, pairs, within_km, nsamples: int, seed: int = 0, c
     ``dtw_per_cell_mean``, the mean of dtw / dtw_len; and ``sample_status`` (B,), the sampler's STE_STATUS_* bits."""
     import warnings
 
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
     within_km = float(within_km)
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("route_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "route_statistics")
     torch = db.torch
-    N, B = int(db.struct.Nmax), db.ntracks
     kw = dict(dtw=dtw, band=band, reverse=reverse, model=model)
     smoothed = db.route_metrics(db.sm_mean, pairs, **kw)
     P = int(smoothed["status"].shape[1])
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
     f64 = dict(dtype=torch.float64, device=db.device)
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
     within, nbad = (torch.zeros((P,), dtype=torch.int32, device=db.device) for _ in range(2))
     fsum, wsum = torch.zeros((P,), **f64), torch.zeros((P,), **f64)
     kept = torch.empty((nsamples, P), **f64) if quantiles is not None else None
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        draws = buf[:n]
-        draws.normal_(generator=gen)
-        m = db.route_metrics(db.sample_smoothed(n, draws=draws), pairs, **kw)
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for i, n, samples in chunks:
+        m = db.route_metrics(samples, pairs, **kw)
         good = m["status"] == 0
         fre = torch.where(good, m["frechet"], torch.zeros_like(m["frechet"]))
         for s in range(n):  # sample by sample: the sums take their terms in sample order whatever the chunk
@@ -3431,7 +3140,7 @@ def route_statistics(hb_or_db, pairs, within_km, nsamples: int, seed: int = 0, c
                 wsum += torch.where(good[s], m["dtw"][s] / m["dtw_len"][s].clamp(min=1), torch.zeros_like(fsum))
         if kept is not None:
             kept[i:i + n] = m["frechet"]
-        status |= db.sample_status
+    status = chunks.status
     count = nsamples - nbad.cpu().numpy()
     out = {"frechet_smoothed": smoothed["frechet"][0].cpu().numpy(), "frechet_at_smoothed": smoothed["frechet_at"][0].cpu().numpy(),
            "status": smoothed["status"][0].cpu().numpy(), "prob_within": within.cpu().numpy() / float(nsamples),
@@ -3473,8 +3182,7 @@ def curve_distance(curves_a, curves_b, dtw: bool = False, band: int = 0, reverse
     for c in ca + cb:
         if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1:
             raise ValueError(f"a curve must be an (n, 2) array of lon / lat with n >= 1, got shape {c.shape}")
-    if model not in DeviceBatch._PATH_MODELS:
-        raise ValueError(f"model must be one of {sorted(DeviceBatch._PATH_MODELS)}, got {model!r}")
+    model_id = _metric_model(model)
     band = int(band)
     if not 0 <= band < 2 ** 31:
         raise ValueError(f"band must be >= 0 (0 = no band) and below 2^31, got {band!r}")
@@ -3495,7 +3203,7 @@ def curve_distance(curves_a, curves_b, dtw: bool = False, band: int = 0, reverse
         s = binding.SteUkfBatchF64()
         s.B, s.Nmax, s.nsteps = B, rows - 1, ns.data_ptr()
         keep = [states, ns, pr]
-        out = _route_call(lib, torch, s, states, 1, pr, dtw, band, reverse, DeviceBatch._PATH_MODELS[model], dev,
+        out = _route_call(lib, torch, s, states, 1, pr, dtw, band, reverse, model_id, dev,
                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), keep)
         res = {k: v[0].cpu().numpy() for k, v in out.items()}  # the download waits for the launch
     return res
@@ -3553,20 +3261,10 @@ def position_statistics(hb_or_db, qtrack, qtime, nsamples: int, seed: int = 0, c
     ``mean_east_km``, ``mean_north_km`` (the samples' mean about the smoothed position), ``cov_km`` (Q, 2, 2),
     ``semi_major_km``, ``semi_minor_km``, ``orientation_deg`` for ``prob``; and ``sample_status`` (B,), the sampler's
     STE_STATUS_* bits per track."""
-    nsamples, chunk = int(nsamples), int(chunk)
-    if nsamples < 1 or chunk < 1:
-        raise ValueError(f"nsamples and chunk must be >= 1, got {nsamples!r} and {chunk!r}")
     if not 0.0 < float(prob) < 1.0:
         raise ValueError(f"prob must lie strictly between 0 and 1, got {prob!r}")
-    if isinstance(hb_or_db, DeviceBatch):
-        db = hb_or_db
-    else:
-        db = DeviceBatch(hb_or_db, device=device)
-        db.run()
-    if db.sm_mean is None:
-        raise ValueError("position_statistics() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "position_statistics")
     torch = db.torch
-    N, B = int(db.struct.Nmax), db.ntracks
     smoothed = db.positions_at(db.sm_mean, qtrack, qtime, t0=t0, velocity=True)
     Q = int(smoothed["status"].shape[0])
     # the kernel's order once, for every chunk: by (track, time)
@@ -3577,18 +3275,11 @@ def position_statistics(hb_or_db, qtrack, qtime, nsamples: int, seed: int = 0, c
     qt, tq = qt[perm], tq[perm]
     anchor = torch.stack([smoothed["lon"][0], smoothed["lat"][0]])[:, perm].contiguous()
     knots = smoothed["knots"]
-    gen = torch.Generator(device=db.device)
-    gen.manual_seed(int(seed))
-    f64 = dict(dtype=torch.float64, device=db.device)
-    buf = torch.empty((min(chunk, nsamples), N + 1, 4, B), **f64)
-    acc = (torch.zeros((Q,), dtype=torch.int32, device=db.device), torch.zeros((5, Q), **f64))
-    status = torch.zeros((B,), dtype=torch.int32, device=db.device)
-    for i in range(0, nsamples, chunk):
-        n = min(chunk, nsamples - i)
-        draws = buf[:n]
-        draws.normal_(generator=gen)
-        db.positions_at(db.sample_smoothed(n, draws=draws), qt, tq, t0=t0, anchor=anchor, accumulate=acc, knots=knots, sort=False)
-        status |= db.sample_status
+    acc = (torch.zeros((Q,), dtype=torch.int32, device=db.device), torch.zeros((5, Q), dtype=torch.float64, device=db.device))
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for _, _, samples in chunks:
+        db.positions_at(samples, qt, tq, t0=t0, anchor=anchor, accumulate=acc, knots=knots, sort=False)
+    status = chunks.status
     inv = torch.empty_like(perm)
     inv[perm] = torch.arange(Q, device=db.device)
     count, moments = acc[0][inv].cpu().numpy(), acc[1][:, inv].cpu().numpy()

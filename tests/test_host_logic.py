@@ -237,3 +237,79 @@ def test_wgs84_legs_near_the_antipode_are_solved_silently():
         assert 0 < utils.geographiclib_distance(-30.5, -0.5, 20.0, 40.0) < 2.1e4
         d = utils.geographiclib_distance(0.0, 0.0, 179.7, 0.2)
     assert 19_900 < d < 20_004
+
+
+def test_states_in_place_predicate():
+    """The one rule by which a metric call reads ``states`` where it lies (track_estimators.batch.states_in_place): the rows
+    are the fleet's, ld = 7 tracks wide with Nmax = 2, and the stride of a dimension of size 1 does not count.  The answers
+    are those of the expression every metric method carried before it was shared."""
+    import torch
+
+    from track_estimators.batch import states_in_place
+
+    N, ld = 2, 7
+    full = torch.zeros((5, N + 1, 4, ld), dtype=torch.float64)
+
+    def in_place(t):
+        return states_in_place(t.shape, t.stride(), N, ld)
+
+    window = full[..., 2:5]
+    assert window.stride() == (84, 28, 7, 1) and in_place(window) is True
+    one_sample = full[1][None][..., 2:5]  # S = 1: whatever stride the size-1 dimension has is not used
+    assert one_sample.shape == (1, 3, 4, 3) and in_place(one_sample) is True
+    assert states_in_place((1, 3, 4, 3), (999, 28, 7, 1), N, ld) is True
+    one_track = full[..., 4:5]  # B = 1
+    assert one_track.shape == (5, 3, 4, 1) and in_place(one_track) is True
+    assert states_in_place((5, 3, 4, 1), (84, 28, 7, 999), N, ld) is True
+    assert in_place(full) is True
+    copied = window.contiguous()
+    assert copied.stride() == (36, 12, 3, 1) and in_place(copied) is False
+    wider = torch.zeros((5, N + 1, 4, 9), dtype=torch.float64)[..., 2:5]
+    assert wider.stride() == (108, 36, 9, 1) and in_place(wider) is False
+    permuted = torch.zeros((5, 4, N + 1, ld), dtype=torch.float64).permute(0, 2, 1, 3)[..., 2:5]
+    assert permuted.shape == (5, 3, 4, 3) and permuted.stride() == (84, 7, 21, 1) and in_place(permuted) is False
+    assert in_place(window[::2]) is False  # every other sample: the rows are the fleet's, the samples are not adjacent
+
+
+@pytest.mark.parametrize("name,tail,limit_name", [("pairs", (2,), "STE_ENCOUNTER_MAX_PAIRS"), ("pairs", (2,), "STE_ROUTE_MAX_PAIRS"),
+                                                  ("qtrack", (), "STE_POSITIONS_MAX_QUERIES")])
+def test_index_tensor(name, tail, limit_name):
+    """The index lists of encounter_metrics / route_metrics (``pairs``) and positions_at (``qtrack``): what is accepted, what
+    is refused and with which message, and the int32 form the kernels get."""
+    import re
+
+    import torch
+
+    from track_estimators._hip import binding
+    from track_estimators.batch import _index_int32, _index_tensor
+
+    limit = getattr(binding, limit_name)
+    assert limit == 1 << 26
+    letter, shape = ("P", "(P, 2)") if name == "pairs" else ("Q", "(Q,)")
+    rows = np.arange(6).reshape((3,) + tail) if tail else np.arange(3)
+    for given in (rows.tolist(), rows.astype(np.int32), torch.from_numpy(rows.astype(np.uint8)), torch.from_numpy(rows.astype(np.int64))):
+        got = _index_tensor(given, name, tail, limit)
+        assert isinstance(got, torch.Tensor) and tuple(got.shape) == (3,) + tail and np.array_equal(got.numpy(), rows)
+    assert _index_tensor(rows.tolist(), name, tail, limit).dtype == torch.int64  # an array comes back as int64
+    for bad, dtype in ((rows.astype(np.float64), "float64"), (rows.astype(bool), "bool"),
+                       (torch.from_numpy(rows.astype(np.float32)), "torch.float32"), (torch.from_numpy(rows.astype(bool)), "torch.bool")):
+        with pytest.raises(ValueError, match=re.escape(f"{name} must be a {shape} integer array or tensor, got dtype {dtype}")):
+            _index_tensor(bad, name, tail, limit)
+    wrong_rank = np.zeros((3, 2, 1), dtype=np.int64) if tail else np.zeros((3, 1), dtype=np.int64)
+    empty = np.zeros((0,) + tail, dtype=np.int64)
+    too_long = torch.zeros((1,) + tail, dtype=torch.int8).expand((limit + 1,) + tail)  # no memory behind it
+    other_tail = [np.zeros((3, 3), dtype=np.int64), np.zeros((3,), dtype=np.int64)] if tail else []
+    for bad in [wrong_rank, empty, too_long] + other_tail:
+        want = f"{name} must have shape {shape} with 1 <= {letter} <= {limit}, got {tuple(bad.shape)}"
+        with pytest.raises(ValueError, match=re.escape(want)):
+            _index_tensor(bad, name, tail, limit)
+    assert tuple(_index_tensor(too_long[:limit], name, tail, limit).shape) == (limit,) + tail  # the limit itself is allowed
+    # the int32 form: an index that does not fit 32 bits stays outside [0, B), a negative one stays negative
+    B = 70
+    big = torch.tensor([0, B - 1, 2 ** 31, 2 ** 40, -5, -(2 ** 40), 2 ** 31 - 1], dtype=torch.int64)
+    small = _index_int32(big)
+    assert small.dtype == torch.int32 and small.is_contiguous()
+    assert small.tolist() == [0, B - 1, 2 ** 31 - 1, 2 ** 31 - 1, -1, -1, 2 ** 31 - 1]
+    inside = (small >= 0) & (small < B)
+    assert inside.tolist() == [True, True, False, False, False, False, False]
+    assert _index_int32(torch.arange(6).reshape(3, 2).t()).is_contiguous()

@@ -23,16 +23,11 @@ usage: tools/encounter_metrics_timing.py [--tracks 10000] [--steps 500] [--round
 import argparse
 import ctypes as C
 import hashlib
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+from metrics_timing_common import ROOT, append_json, bare_batch, timed  # and the import path of the package
 
 OUTPUTS = ("min_dist", "min_time", "time_within", "first_within", "nwithin", "overlap", "nbroken", "status")
 
@@ -61,11 +56,7 @@ def main():
     steps = rng.normal(0.0, 0.004, (2, B))[None] + rng.normal(0.0, 0.002, (N, 2, B))
     track = np.concatenate([start[None], start[None] + np.cumsum(steps, axis=0)])  # (N + 1, 2, B)
     dt = rng.uniform(0.05, 0.15, (N, B))
-    z = np.zeros((N, B))
-    hb = batch.HostBatch(B=B, Nmax=N, Tmax=1, H=np.eye(4), Q=np.eye(4), R=np.eye(4), nsteps=np.full(B, N, dtype=np.int32),
-                         x0=np.zeros((4, B)), P0=np.eye(4).reshape(16), dt=dt, sog_rate=z, cog_rate=z.copy(), sog_rate_rts=None,
-                         cog_rate_rts=None, upd_idx=np.full((N, B), -1, dtype=np.int32), z=np.zeros((1, 4, B)))
-    db = batch.DeviceBatch(hb, histories=False)
+    db = bare_batch(np.full(B, N), dt)
     lib, s = db.lib, db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
     i32 = dict(dtype=torch.int32, device=db.device)
@@ -77,19 +68,6 @@ def main():
     gen = torch.Generator(device=db.device)
     gen.manual_seed(1)
     orders = {"sorted": pairs, "shuffled": pairs[torch.randperm(P, generator=gen, device=db.device)].contiguous()}
-
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
 
     def encounter(states, S, pr, out):
         en = binding.SteEncounterF64()
@@ -112,7 +90,6 @@ def main():
     pieces = int(count["nbroken"].sum(dtype=torch.int64).item())
     del broken, count
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
         states = base[None].repeat(S, 1, 1, 1)
         if S > 1:
@@ -121,7 +98,7 @@ def main():
                "radius_km": args.radius, "pieces": pieces, "enc_ms": {}, "enc_samples": {}}
         res = outputs(S)
         for name, pr in orders.items():
-            out["enc_ms"][name], out["enc_samples"][name] = timed(encounter(states, S, pr, res))
+            out["enc_ms"][name], out["enc_samples"][name] = timed(encounter(states, S, pr, res), args.rounds)
         call = encounter(states, S, pairs, res)
         call()
         torch.cuda.synchronize()
@@ -131,9 +108,9 @@ def main():
         out["checksum"] = h.hexdigest()
         out["pairs_within"] = int((res["nwithin"][0] > 0).sum().item())
         out["pairs_with_overlap"] = int((res["overlap"][0] > 0).sum().item())
-        out["enc_no_leg_ms"] = timed(encounter(states, S, pairs, {k: v for k, v in res.items() if k != "min_dist"}))[0]
+        out["enc_no_leg_ms"] = timed(encounter(states, S, pairs, {k: v for k, v in res.items() if k != "min_dist"}), args.rounds)[0]
         out["enc_no_within_ms"] = timed(encounter(states, S, pairs, {k: v for k, v in res.items() if k not in (
-            "time_within", "first_within", "nwithin")}))[0]
+            "time_within", "first_within", "nwithin")}), args.rounds)[0]
         dist = torch.empty((S, B), **f64)
         pm = binding.StePathF64()
         pm.nstates, pm.model, pm.states, pm.dist, pm.line_axis = S, binding.STE_PREP_SPHERE, states.data_ptr(), dist.data_ptr(), -1
@@ -141,16 +118,13 @@ def main():
         def path():
             binding.check(lib.ste_path_metrics_f64(C.byref(db.struct), C.byref(pm), s), "ste_path_metrics_f64")
 
-        out["path_ms"], out["path_samples"] = timed(path)
+        out["path_ms"], out["path_samples"] = timed(path, args.rounds)
         ms = out["enc_ms"]["sorted"]
         out["ratio_to_path"] = {k: v / out["path_ms"] for k, v in out["enc_ms"].items()}
         out["pieces_per_s"] = S * pieces / (ms * 1e-3)
         out["bytes_per_s"] = 32.0 * out["pieces_per_s"]
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; enc_ms keyed by pair order"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del states, res, dist
 
 

@@ -22,18 +22,11 @@ usage: tools/grid_metrics_timing.py [--tracks 10000] [--rounds 7] [--samples 1 4
 """
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-NOBS, SUBSTEPS = 126, 4  # bench.py: 125 gaps of 4 filter steps = 500 steps, 501 rows per track
+from metrics_timing_common import ROOT, append_json, bench_batch, posterior_draws, timed  # and the import path of the package
 
 
 def main():
@@ -46,15 +39,10 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from track_estimators import batch, synthetic
+    from track_estimators import batch
     from track_estimators._hip import binding
 
-    H, Q, R, P0 = synthetic.example_matrices()
-    sb = synthetic.make_batch(args.tracks, nobs=NOBS, gap_h=1.0, seed0=0)
-    hb = batch.pack_uniform(sb, SUBSTEPS, H, Q, R, P0)
-    db = batch.DeviceBatch(hb)
-    db.run()
-    torch.cuda.synchronize()
+    db, hb = bench_batch(args.tracks)
     lib, B, rows = db.lib, hb.B, hb.Nmax + 1
     s = db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
@@ -70,26 +58,8 @@ def main():
              "onecell": batch.track_grid(-180.0, -90.0, 360.0, 180.0, 1, 1),
              "clear": batch.track_grid(far - 4.0, lat_c - 4.0, 0.25, 0.25, 32, 32)}
 
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
-
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
-        gen = torch.Generator(device=db.device)
-        gen.manual_seed(0)
-        draws = torch.randn((S, rows, 4, B), generator=gen, **f64)
-        sm, status, keep = db._sample_struct(draws, S)
-        binding.check(lib.ste_urtss_sample_f64(C.byref(db.struct), None, C.byref(sm), s), "ste_urtss_sample_f64")
+        draws, sm, status, keep, _ = posterior_draws(db, S)
         outside, total = torch.empty((S, B), **i64), torch.empty((S, B), **i64)
         nbrk = torch.empty((S, B), dtype=torch.int32, device=db.device)
         dist = torch.empty((S, B), **f64)
@@ -107,9 +77,9 @@ def main():
             def call():
                 binding.check(lib.ste_grid_metrics_f64(C.byref(db.struct), C.byref(g), s), "ste_grid_metrics_f64")
 
-            out["grid_ms"][name], out["grid_samples"][name] = timed(call)
+            out["grid_ms"][name], out["grid_samples"][name] = timed(call, args.rounds)
             g.entries = ent.data_ptr()
-            out["grid_entries_ms"][name] = timed(call)[0]
+            out["grid_entries_ms"][name] = timed(call, args.rounds)[0]
             ticks.zero_()
             ent.zero_()
             call()
@@ -126,13 +96,10 @@ def main():
         def path():
             binding.check(lib.ste_path_metrics_f64(C.byref(db.struct), C.byref(pm), s), "ste_path_metrics_f64")
 
-        out["path_ms"], out["path_samples"] = timed(path)
+        out["path_ms"], out["path_samples"] = timed(path, args.rounds)
         out["sampler_status_any"] = int(status.cpu().numpy().any())
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; grid_ms keyed by case"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del draws, sm, keep
 
 

@@ -26,16 +26,11 @@ usage: tools/line_metrics_timing.py [--tracks 10000] [--steps 500] [--lines 16] 
 import argparse
 import ctypes as C
 import hashlib
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+from metrics_timing_common import ROOT, append_json, bare_batch, timed  # and the import path of the package
 
 LINE3 = ("min_dist", "min_time", "min_seg", "min_frac", "ncross", "net_cross", "first_cross", "last_cross")
 LINE_OUTPUTS = LINE3 + ("sound_time", "nbroken", "track_status", "line_status")
@@ -81,11 +76,7 @@ def main():
     tl = batch.track_lines(lines)
     V = int(tl.vert.shape[1])
 
-    z = np.zeros((N, B))
-    hb = batch.HostBatch(B=B, Nmax=N, Tmax=1, H=np.eye(4), Q=np.eye(4), R=np.eye(4), nsteps=np.full(B, N, dtype=np.int32),
-                         x0=np.zeros((4, B)), P0=np.eye(4).reshape(16), dt=dt, sog_rate=z, cog_rate=z.copy(), sog_rate_rts=None,
-                         cog_rate_rts=None, upd_idx=np.full((N, B), -1, dtype=np.int32), z=np.zeros((1, 4, B)))
-    db = batch.DeviceBatch(hb, histories=False)
+    db = bare_batch(np.full(B, N), dt)
     lib, s = db.lib, db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
     i32 = dict(dtype=torch.int32, device=db.device)
@@ -96,19 +87,6 @@ def main():
     rad = torch.full((V,), args.radius, **f64)
     gen = torch.Generator(device=db.device)
     gen.manual_seed(1)
-
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
 
     def line_call(states, S, out):
         li = binding.SteLineF64()
@@ -130,7 +108,6 @@ def main():
         shape = {"sound_time": (S, B), "nbroken": (S, B), "track_status": (B,), "line_status": (M,), "site_status": (V,)}
         return {k: torch.empty(shape.get(k, (S, width, B)), **(i32 if k in INT32 else f64)) for k in names}
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
         states = base[None].repeat(S, 1, 1, 1)
         if S > 1:
@@ -138,33 +115,30 @@ def main():
         out = {"label": args.label, "tracks": B, "rows": N + 1, "lines": M, "segments": L, "nsamples": S, "rounds": args.rounds,
                "line_chunk": int(lib.ste_line_chunk()), "pairs": B * M * L * N}
         res = outputs(LINE_OUTPUTS, S, M)
-        out["line_ms"], out["line_samples"] = timed(line_call(states, S, res))
+        out["line_ms"], out["line_samples"] = timed(line_call(states, S, res), args.rounds)
         h = hashlib.sha256()
         for k in LINE_OUTPUTS:
             h.update(res[k].cpu().numpy().tobytes())
         out["checksum"] = h.hexdigest()
         out["pairs_crossed"] = int((res["ncross"][0] > 0).sum().item())
         out["line_no_cross_ms"] = timed(line_call(states, S, {k: v for k, v in res.items() if k not in (
-            "ncross", "net_cross", "first_cross", "last_cross")}))[0]
-        out["line_no_leg_ms"] = timed(line_call(states, S, {k: v for k, v in res.items() if k != "min_dist"}))[0]
+            "ncross", "net_cross", "first_cross", "last_cross")}), args.rounds)[0]
+        out["line_no_leg_ms"] = timed(line_call(states, S, {k: v for k, v in res.items() if k != "min_dist"}), args.rounds)[0]
         out["pairs_per_s"] = S * out["pairs"] / (out["line_ms"] * 1e-3)
         del res
         if not args.no_site:
             sres = outputs(SITE_OUTPUTS, S, V)
             out["sites"], out["radius_km"], out["site_tile"] = V, args.radius, int(lib.ste_site_tile())
             out["site_pieces"] = B * V * N
-            out["site_ms"], out["site_samples"] = timed(site_call(states, S, sres))
+            out["site_ms"], out["site_samples"] = timed(site_call(states, S, sres), args.rounds)
             out["site_no_within_ms"] = timed(site_call(states, S, {k: v for k, v in sres.items() if k not in (
-                "time_within", "first_within", "longest", "nwithin")}))[0]
+                "time_within", "first_within", "longest", "nwithin")}), args.rounds)[0]
             out["site_pieces_per_s"] = S * out["site_pieces"] / (out["site_ms"] * 1e-3)
             out["site_pieces_per_s_no_within"] = S * out["site_pieces"] / (out["site_no_within_ms"] * 1e-3)
             out["pairs_per_s_over_site_pieces_per_s"] = out["pairs_per_s"] / out["site_pieces_per_s"]
             del sres
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del states
 
 

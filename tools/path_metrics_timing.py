@@ -15,18 +15,9 @@ usage: tools/path_metrics_timing.py [--tracks 10000] [--rounds 7] [--samples 1 4
 """
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import numpy as np  # noqa: E402
-
-NOBS, SUBSTEPS = 126, 4  # bench.py: 125 gaps of 4 filter steps = 500 steps, 501 rows per track
+from metrics_timing_common import ROOT, append_json, bench_batch, posterior_draws, timed  # and the import path of the package
 
 
 def main():
@@ -38,39 +29,16 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from track_estimators import batch, synthetic
     from track_estimators._hip import binding
 
-    H, Q, R, P0 = synthetic.example_matrices()
-    sb = synthetic.make_batch(args.tracks, nobs=NOBS, gap_h=1.0, seed0=0)
-    hb = batch.pack_uniform(sb, SUBSTEPS, H, Q, R, P0)
-    db = batch.DeviceBatch(hb)
-    db.run()
-    torch.cuda.synchronize()
+    db, hb = bench_batch(args.tracks)
     lib, B, rows = db.lib, hb.B, hb.Nmax + 1
     s = db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
     line_value = db.sm_mean[0, 1].clone()  # every ship's first smoothed latitude: the tracks cross it or hover about it
 
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
-
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
-        gen = torch.Generator(device=db.device)
-        gen.manual_seed(0)
-        draws = torch.randn((S, rows, 4, B), generator=gen, **f64)
-        sm, status, keep = db._sample_struct(draws, S)
+        draws, sm, status, keep, gen = posterior_draws(db, S, sample=False)
         binding.check(lib.ste_urtss_sample_prepare_f64(C.byref(db.struct), None, C.byref(sm), s), "ste_urtss_sample_prepare_f64")
 
         def draw():
@@ -78,7 +46,7 @@ def main():
 
         out = {"tracks": B, "rows": rows, "nsamples": S, "rounds": args.rounds}
         # timed first, on the fresh draws and then on what the call before left; the last call's output is not a set of tracks
-        out["draw_ms"], out["draw_samples"] = timed(draw)
+        out["draw_ms"], out["draw_samples"] = timed(draw, args.rounds)
         draws.normal_(generator=gen)
         draw()  # the tracks the path kernels are timed on: one draw from fresh normal deviates
         dist = torch.empty((S, B), **f64)
@@ -97,7 +65,7 @@ def main():
                     binding.check(lib.ste_path_metrics_f64(C.byref(db.struct), C.byref(pm), s), "ste_path_metrics_f64")
 
                 key = model + ("+line" if line else "")
-                ms, samples = timed(path)
+                ms, samples = timed(path, args.rounds)
                 nbytes = S * B * (16 * rows + 8) + (S * B * (8 * (rows - 1) + 12) if line else 0)
                 out["path_ms"][key], out["path_samples"][key] = ms, samples
                 out["path_gbs"][key] = round(nbytes / (ms * 1e-3) / 1e9, 1)
@@ -105,10 +73,7 @@ def main():
         out["cross_fraction"] = float((~torch.isnan(ctime)).double().mean().item())
         out["sampler_status_any"] = int(status.cpu().numpy().any())
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; path_* keyed by model (+line)"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del draws, sm, keep
 
 

@@ -23,18 +23,10 @@ usage: tools/position_metrics_timing.py [--tracks 10000] [--per-ship 100] [--rou
 import argparse
 import ctypes as C
 import hashlib
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from metrics_timing_common import ROOT, append_json, bench_batch, timed  # and the import path of the package
 
-import numpy as np  # noqa: E402
-
-NOBS, SUBSTEPS = 126, 4  # bench.py: 125 gaps of 4 filter steps = 500 steps, 501 rows per track
 PLAIN = ("lon", "lat", "speed", "heading", "step", "frac", "status")
 
 
@@ -49,15 +41,9 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from track_estimators import batch, synthetic
     from track_estimators._hip import binding
 
-    H, Qm, R, P0 = synthetic.example_matrices()
-    sb = synthetic.make_batch(args.tracks, nobs=NOBS, gap_h=1.0, seed0=0)
-    hb = batch.pack_uniform(sb, SUBSTEPS, H, Qm, R, P0)
-    db = batch.DeviceBatch(hb)
-    db.run()
-    torch.cuda.synchronize()
+    db, hb = bench_batch(args.tracks)
     lib, B, rows = db.lib, hb.B, hb.Nmax + 1
     s = db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
@@ -72,19 +58,6 @@ def main():
     perm = torch.randperm(Q, generator=gen, device=db.device)
     orders = {"sorted": (qtrack, qtime, None), "shuffled": (qtrack[perm].contiguous(), qtime[perm].contiguous(), perm)}
     knots = torch.empty((rows, B), **f64)
-
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
 
     def positions(states, S, order, out, reuse, anchor=None):
         po = binding.StePositionsF64()
@@ -108,7 +81,6 @@ def main():
     anchors["shuffled"] = anchors["sorted"][:, perm].contiguous()
     located, interior = int((sm["step"] >= 0).sum().item()), int((sm["frac"] > 0).sum().item())
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
         states = db.sample_smoothed(S, seed=0)
         torch.cuda.synchronize()
@@ -117,12 +89,12 @@ def main():
         res = outputs(S)
         acc = {"count": torch.zeros((Q,), **i32), "moments": torch.zeros((5, Q), **f64)}
         for name in orders:
-            out["pos_ms"][name], out["samples_ms"]["pos " + name] = timed(positions(states, S, name, res, False))
-            out["pos_reuse_ms"][name], out["samples_ms"]["pos_reuse " + name] = timed(positions(states, S, name, res, True))
-            out["mom_ms"][name], out["samples_ms"]["mom " + name] = timed(positions(states, S, name, acc, True, anchors[name]))
+            out["pos_ms"][name], out["samples_ms"]["pos " + name] = timed(positions(states, S, name, res, False), args.rounds)
+            out["pos_reuse_ms"][name], out["samples_ms"]["pos_reuse " + name] = timed(positions(states, S, name, res, True), args.rounds)
+            out["mom_ms"][name], out["samples_ms"]["mom " + name] = timed(positions(states, S, name, acc, True, anchors[name]), args.rounds)
         out["knots_ms"] = out["pos_ms"]["sorted"] - out["pos_reuse_ms"]["sorted"]
-        out["pos_lonlat_ms"] = timed(positions(states, S, "sorted", {k: v for k, v in res.items() if k not in ("speed", "heading")}, True))[0]
-        out["mom_all_ms"] = timed(positions(states, S, "sorted", {**res, **acc}, True, anchors["sorted"]))[0]
+        out["pos_lonlat_ms"] = timed(positions(states, S, "sorted", {k: v for k, v in res.items() if k not in ("speed", "heading")}, True), args.rounds)[0]
+        out["mom_all_ms"] = timed(positions(states, S, "sorted", {**res, **acc}, True, anchors["sorted"]), args.rounds)[0]
         acc["count"].zero_()
         acc["moments"].zero_()
         positions(states, S, "sorted", {**res, **acc}, True, anchors["sorted"])()
@@ -139,16 +111,13 @@ def main():
         def path():
             binding.check(lib.ste_path_metrics_f64(C.byref(db.struct), C.byref(pm), s), "ste_path_metrics_f64")
 
-        out["path_ms"], out["samples_ms"]["path"] = timed(path)
+        out["path_ms"], out["samples_ms"]["path"] = timed(path, args.rounds)
         out["ratio_to_path"] = {"pos " + k: v / out["path_ms"] for k, v in out["pos_reuse_ms"].items()}
         out["ratio_to_path"].update({"mom " + k: v / out["path_ms"] for k, v in out["mom_ms"].items()})
         out["values_per_s"] = S * Q / (out["pos_reuse_ms"]["sorted"] * 1e-3)
         out["bytes_per_s"] = 96.0 * out["values_per_s"]
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; keyed by the order of the query list"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del states, res, acc, dist
 
 

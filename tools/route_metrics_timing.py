@@ -21,16 +21,11 @@ usage: tools/route_metrics_timing.py [--tracks 10000] [--steps 500] [--rounds 7]
 import argparse
 import ctypes as C
 import hashlib
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+from metrics_timing_common import ROOT, append_json, bare_batch, timed  # and the import path of the package
 
 OUTPUTS = ("frechet", "frechet_at", "dtw", "dtw_len", "status")
 FRECHET = ("frechet", "frechet_at", "status")
@@ -61,11 +56,7 @@ def main():
     start = centre + rng.uniform(-1.5, 1.5, (2, B))
     steps = rng.normal(0.0, 0.004, (2, B))[None] + rng.normal(0.0, 0.002, (N, 2, B))
     track = np.concatenate([start[None], start[None] + np.cumsum(steps, axis=0)])  # (N + 1, 2, B)
-    z = np.zeros((N, B))
-    hb = batch.HostBatch(B=B, Nmax=N, Tmax=1, H=np.eye(4), Q=np.eye(4), R=np.eye(4), nsteps=np.full(B, N, dtype=np.int32),
-                         x0=np.zeros((4, B)), P0=np.eye(4).reshape(16), dt=z + 0.1, sog_rate=z, cog_rate=z.copy(), sog_rate_rts=None,
-                         cog_rate_rts=None, upd_idx=np.full((N, B), -1, dtype=np.int32), z=np.zeros((1, 4, B)))
-    db = batch.DeviceBatch(hb, histories=False)
+    db = bare_batch(np.full(B, N), np.full((N, B), 0.1))
     lib, s = db.lib, db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
     i32 = dict(dtype=torch.int32, device=db.device)
@@ -80,19 +71,6 @@ def main():
     a = np.arange(rows)
     cells = {0: P * rows * rows, args.band: P * int((np.abs(a[:, None] - a[None, :]) <= args.band).sum())}
 
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
-
     need = int(lib.ste_route_workspace(N, max(args.samples), P))
     work = torch.empty((max(need, 8) // 8,), **f64)
 
@@ -105,7 +83,6 @@ def main():
             setattr(ro, k, ten.data_ptr())
         return lambda: binding.check(lib.ste_route_metrics_f64(C.byref(db.struct), C.byref(ro), s), "ste_route_metrics_f64")
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
         states = base[None].repeat(S, 1, 1, 1)
         if S > 1:
@@ -118,7 +95,7 @@ def main():
         for band in (0, args.band):
             for name, want in (("frechet", FRECHET), ("dtw", OUTPUTS)):
                 key = f"{name}_band{band}"
-                ms, samples = timed(route(states, S, band, {k: res[k] for k in want}))
+                ms, samples = timed(route(states, S, band, {k: res[k] for k in want}), args.rounds)
                 out["route_ms"][key], out["route_samples"][key] = ms, samples
                 out["cells_per_s"][key] = S * cells[band] / (ms * 1e-3)
             torch.cuda.synchronize()  # res holds the `dtw` call of this band
@@ -135,13 +112,10 @@ def main():
         def path():
             binding.check(lib.ste_path_metrics_f64(C.byref(db.struct), C.byref(pm), s), "ste_path_metrics_f64")
 
-        out["path_ms"], out["path_samples"] = timed(path)
+        out["path_ms"], out["path_samples"] = timed(path, args.rounds)
         out["ratio_to_path"] = {k: v / out["path_ms"] for k, v in out["route_ms"].items()}
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; route_ms keyed by outputs and band"
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del states, res, dist
 
 

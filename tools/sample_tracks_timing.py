@@ -17,18 +17,10 @@ usage: tools/sample_tracks_timing.py [--tracks 10000] [--rounds 7] [--samples 1 
 """
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from metrics_timing_common import ROOT, append_json, bench_batch, posterior_draws, timed  # and the import path of the package
 
-import numpy as np  # noqa: E402
-
-NOBS, SUBSTEPS = 126, 4  # bench.py: 125 gaps of 4 filter steps = 500 steps per track
 SMOOTHER_TBS = 4.9  # README.md: what the one-kernel smoother moves at this batch
 
 
@@ -40,40 +32,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "track_sampling_timing.jsonl"))
     args = ap.parse_args()
 
-    import torch
-    from track_estimators import batch, synthetic
     from track_estimators._hip import binding
 
-    H, Q, R, P0 = synthetic.example_matrices()
-    sb = synthetic.make_batch(args.tracks, nobs=NOBS, gap_h=1.0, seed0=0)
-    hb = batch.pack_uniform(sb, SUBSTEPS, H, Q, R, P0)
-    db = batch.DeviceBatch(hb)
-    db.forward()
-    torch.cuda.synchronize()
+    db, hb = bench_batch(args.tracks, smooth=False)
     lib, B, rows = db.lib, hb.B, hb.Nmax + 1
     s = db._stream(None)
     lib.ste_dbg_sample_lanes.restype = C.c_int
     lib.ste_dbg_sample_lanes.argtypes = [C.c_int]
 
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
-
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
-        gen = torch.Generator(device=db.device)
-        gen.manual_seed(0)
-        draws = torch.randn((S, rows, 4, B), generator=gen, dtype=torch.float64, device=db.device)
-        sm, status, keep = db._sample_struct(draws, S)
+        draws, sm, status, keep, _ = posterior_draws(db, S, sample=False)
 
         def prepare():
             binding.check(lib.ste_urtss_sample_prepare_f64(C.byref(db.struct), None, C.byref(sm), s), "ste_urtss_sample_prepare_f64")
@@ -84,20 +52,17 @@ def main():
         model_bytes = B * rows * (64 * S + 240)
         out = {"tracks": B, "rows": rows, "nsamples": S, "rounds": args.rounds, "model_bytes": model_bytes,
                "smoother_tbs": SMOOTHER_TBS}
-        out["prepare_ms"], out["prepare_samples"] = timed(prepare)
+        out["prepare_ms"], out["prepare_samples"] = timed(prepare, args.rounds)
         out["recur_ms"], out["recur_gbs"], out["recur_samples"] = {}, {}, {}
         for spl in (1, 2, 4, 0):  # 0: the library's own choice by launch size, what callers get
             lib.ste_dbg_sample_lanes(spl)
-            ms, samples = timed(draw)
+            ms, samples = timed(draw, args.rounds)
             key = str(spl) if spl else "library"
             out["recur_ms"][key], out["recur_samples"][key] = ms, samples
             out["recur_gbs"][key] = round(model_bytes / (ms * 1e-3) / 1e9, 1)
         out["sampler_status_any"] = int(status.cpu().numpy().any())
         out["what"] = "HIP events on the current stream, median of rounds after one warm-up; recur_* keyed by samples per lane"
-        line = json.dumps(out)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+        append_json(args.out, out)
         del draws, sm, keep
 
 

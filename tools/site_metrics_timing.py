@@ -26,17 +26,12 @@ usage: tools/site_metrics_timing.py [--tracks 10000] [--steps 500] [--sites 256]
 import argparse
 import ctypes as C
 import hashlib
-import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "ship-track-estimators_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+from metrics_timing_common import ROOT, append_json, bare_batch, timed  # and the import path of the package
 
 SITE3 = ("min_dist", "min_time", "time_within", "first_within", "longest", "nwithin")
 SITE_OUTPUTS = SITE3 + ("sound_time", "nbroken", "track_status", "site_status")
@@ -59,7 +54,6 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from track_estimators import batch
     from track_estimators._hip import binding
 
     B, N, M = args.tracks, args.steps, args.sites
@@ -74,14 +68,7 @@ def main():
     srng = np.random.default_rng(2)
     sites = (centres[:, np.arange(M) % ncl] + srng.uniform(-1.5, 1.5, (2, M)))  # [2][M]: lon then lat
 
-    def bare(nsteps, dts):
-        b, z = dts.shape[1], np.zeros(dts.shape)
-        return batch.HostBatch(B=b, Nmax=N, Tmax=1, H=np.eye(4), Q=np.eye(4), R=np.eye(4), nsteps=nsteps.astype(np.int32),
-                               x0=np.zeros((4, b)), P0=np.eye(4).reshape(16), dt=dts, sog_rate=z, cog_rate=z.copy(),
-                               sog_rate_rts=None, cog_rate_rts=None, upd_idx=np.full((N, b), -1, dtype=np.int32),
-                               z=np.zeros((1, 4, b)))
-
-    db = batch.DeviceBatch(bare(np.full(B, N), dt), histories=False)
+    db = bare_batch(np.full(B, N), dt)
     lib, s = db.lib, db._stream(None)
     f64 = dict(dtype=torch.float64, device=db.device)
     i32 = dict(dtype=torch.int32, device=db.device)
@@ -92,19 +79,6 @@ def main():
     rad = torch.full((M,), args.radius, **f64)
     gen = torch.Generator(device=db.device)
     gen.manual_seed(1)
-
-    def timed(fn):
-        fn()  # warm-up
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(args.rounds):
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        return float(np.median(samples)), [round(v, 3) for v in samples]
 
     def site_call(states, S, out):
         si = binding.SteSiteF64()
@@ -118,7 +92,6 @@ def main():
         shape = {"sound_time": (S, B), "nbroken": (S, B), "track_status": (B,), "site_status": (M,)}
         return {k: torch.empty(shape.get(k, (S, M, B)), **(i32 if k in INT32 else f64)) for k in SITE_OUTPUTS}
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for S in args.samples:
         states = base[None].repeat(S, 1, 1, 1)
         if S > 1:
@@ -126,15 +99,15 @@ def main():
         out = {"label": args.label, "tracks": B, "rows": N + 1, "sites": M, "nsamples": S, "rounds": args.rounds,
                "radius_km": args.radius, "site_tile": int(lib.ste_site_tile()), "pieces": B * M * N}
         res = site_outputs(S)
-        out["site_ms"], out["site_samples"] = timed(site_call(states, S, res))
+        out["site_ms"], out["site_samples"] = timed(site_call(states, S, res), args.rounds)
         h = hashlib.sha256()
         for k in SITE_OUTPUTS:
             h.update(res[k].cpu().numpy().tobytes())
         out["checksum"] = h.hexdigest()
         out["pairs_within"] = int((res["nwithin"][0] > 0).sum().item())
-        out["site_no_leg_ms"] = timed(site_call(states, S, {k: v for k, v in res.items() if k != "min_dist"}))[0]
+        out["site_no_leg_ms"] = timed(site_call(states, S, {k: v for k, v in res.items() if k != "min_dist"}), args.rounds)[0]
         out["site_no_within_ms"] = timed(site_call(states, S, {k: v for k, v in res.items() if k not in (
-            "time_within", "first_within", "longest", "nwithin")}))[0]
+            "time_within", "first_within", "longest", "nwithin")}), args.rounds)[0]
         out["pieces_per_s"] = S * out["pieces"] / (out["site_ms"] * 1e-3)
         if not args.no_encounter:
             # the route that existed: one stationary ship per site in every sample, and every (track, site) as a pair
@@ -144,7 +117,7 @@ def main():
             dt2 = np.ones((N, B + M))
             dt2[:, :B] = dt
             dt2[0, B:] = span + 2.0
-            edb = batch.DeviceBatch(bare(np.concatenate([np.full(B, N), np.ones(M)]), dt2), histories=False)
+            edb = bare_batch(np.concatenate([np.full(B, N), np.ones(M)]), dt2)
             est = torch.zeros((S, N + 1, 4, B + M), **f64)
             est[..., :B] = states
             est[:, :, 0, B:], est[:, :, 1, B:] = xy[0], xy[1]
@@ -166,7 +139,7 @@ def main():
             def enc_call():
                 binding.check(lib.ste_encounter_metrics_f64(C.byref(edb.struct), C.byref(en), es), "ste_encounter_metrics_f64")
 
-            out["enc_ms"], out["enc_samples"] = timed(enc_call)
+            out["enc_ms"], out["enc_samples"] = timed(enc_call, args.rounds)
             out["enc_pairs"] = P
             out["ratio"] = out["enc_ms"] / out["site_ms"]
             agree = {}
@@ -182,10 +155,7 @@ def main():
             del est, eres, pairs, edb
         out["what"] = ("HIP events on the current stream, median of rounds after one warm-up; enc_setup_ms by the wall clock, in no "
                        "other figure")
-        line_json = json.dumps(out)
-        print(line_json, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line_json + "\n")
+        append_json(args.out, out)
         del states, res
 
 
