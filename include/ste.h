@@ -31,6 +31,8 @@
  *                            line, track) block (no counterpart in the reference)
  *   ste_route_metrics_f64    discrete Frechet distance and time-warping cost of pairs of such tracks as curves without a clock
  *                            (the reference's performance_metrics.py compares two tracks row by row, which needs equal rows)
+ *   ste_speed_metrics_f64    speed made good per step, its maximum, hours per speed band and runs at or below (above) a speed
+ *                            threshold (stops, sustained speed) of such tracks: the per-leg distance of utils.py:9-113 over dt
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -70,7 +72,8 @@ extern "C" {
                            (ste_track_positions_f64).  Unnumbered addition: tracks on the device against fixed sites
                            (ste_site_metrics_f64).  Unnumbered addition: tracks on the device against polylines
                            (ste_line_metrics_f64).  Unnumbered addition: pairs of tracks on the device as curves
-                           (ste_route_metrics_f64).
+                           (ste_route_metrics_f64).  Unnumbered addition: speed made good, speed bands and stops of tracks on
+                           the device (ste_speed_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -926,6 +929,82 @@ int ste_route_metrics_f64(const ste_ukf_batch_f64* b, const ste_route_f64* ro, v
 size_t ste_route_workspace(int32_t Nmax, int32_t nstates, int64_t npairs);
 /* columns of track j whose boundary row the kernel keeps in LDS; a pair with more goes through `work` */
 int ste_route_lds_cols(void);
+
+/*
+ * SPEEDS: how fast tracks that stay on the device went (an unnumbered addition, like ste_route_f64): the speed made good of every
+ * step, its maximum and when, the hours spent in each of up to STE_SPEED_MAX_BANDS speed bands, and the RUNS of steps at or below
+ * a speed threshold (stops, loitering) or, with STE_SPEED_ABOVE, at or above it (sustained speed): how often, for how long, from
+ * when, and the longest.  `states` is that of ste_path_f64, the leg that of ste_path_metrics_f64 for `model`, the clock that of
+ * ste_site_f64 without t0: times are hours from row 0, as cross_time is.  Every expression below is evaluated as written, left to
+ * right, without contraction.
+ *   - Clock.  T_0 = 0, T_{k+1} = T_k + dt_k, summed in order.
+ *   - Bad clock, bad limit.  A track's clock is bad when some dt_k, k < nsteps[t], is not finite or is negative
+ *     (STE_SPEED_BAD_TIME).  Its limit is bad when a run output is asked for and its threshold thr (threshold[t], or threshold_all
+ *     where threshold is NULL) is not finite or is negative (STE_SPEED_BAD_LIMIT); a call without run outputs reads no threshold
+ *     and never sets that bit.  Either bit gives NaN for vmax, vmax_time, first_run, longest_start and every speed row below
+ *     nsteps[t], and zero for every other output of that track, for every sample.
+ *   - Step.  Step k of track t, k < nsteps[t], is examined when dt_k > 0.  A SKIPPED step (dt_k == 0) writes NaN to speed and
+ *     closes the run.  L_k is the leg of ste_path_metrics_f64 for `model` from row k to row k + 1, and v_k = L_k / dt_k.  An
+ *     examined step is BROKEN when v_k is not finite (a coordinate that is not finite, or a quotient that overflows): it adds 1 to
+ *     nbroken, writes NaN to speed, closes the run and adds nothing else.  Every other examined step is SOUND and writes
+ *     speed = v_k.  Steps are examined in the order of k, which defines "first" below.
+ *   - Sums.  dist and sound_time add L_k and dt_k over the sound steps, in order: where every step of a track is examined and
+ *     sound, dist has the bits of ste_path_metrics_f64's dist.
+ *   - Maximum.  A sound step becomes the best one when v_k > vmax (vmax starts below every speed; strict, so the first step wins
+ *     a tie); it records vmax = v_k and vmax_time = T_k, the start of the step.  Without a sound step both are NaN.
+ *   - Bands.  j = (number of i in 0 .. nbands with band_edges[i] <= v_k) - 1; a sound step adds dt_k to band_time of band j when
+ *     0 <= j < nbands.  A speed below band_edges[0], or at or above band_edges[nbands], falls in no band.
+ *   - Runs.  A sound step QUALIFIES when v_k <= thr, or with STE_SPEED_ABOVE when v_k >= thr; cond_time is the sum of dt_k over
+ *     the qualifying steps, in order.  A RUN is a maximal sequence of consecutive qualifying steps: its length is the sum of their
+ *     dt_k in order, its start T_k of its first step.  A step that does not qualify, a broken step, a skipped step and the end
+ *     of the track close the run.  On closing, a run of length len >= min_run_h adds 1 to nruns and len to run_time, and the
+ *     first such run sets first_run to its start; any run with len > longest (strict: the first of equal ones) sets longest = len
+ *     and longest_start to its start, whether it reaches min_run_h or not.  No tolerance anywhere.
+ *   - Every value's bits depend on the track's rows, its dt and its threshold, and on band_edges and min_run_h alone: not on S,
+ *     the window, the lane, or which outputs were asked for (a bad limit excepted: it exists only with a run output).
+ *   - The call reads only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and writes nothing of
+ *     the batch; windows and addressing are those of ste_path_metrics_f64, threshold and track_status like nsteps.  Rows past
+ *     nsteps[t] of states are not read, and rows k >= nsteps[t] of speed are not written.  Per (sample, track) outputs are
+ *     out[s * track_stride + t], speed is speed[(s * Nmax + k) * track_stride + t] and band_time is
+ *     band_time[(s * nbands + j) * track_stride + t] (track_stride = B where it is 0).
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or sp NULL; states NULL; nstates < 1 or
+ *     > 65535; an unknown model; flags with any other bit than STE_SPEED_ABOVE; nbands < 0 or > STE_SPEED_MAX_BANDS; band_edges
+ *     NULL with nbands > 0, or given with nbands == 0; an edge that is not finite, is negative or does not ascend strictly;
+ *     band_time given with nbands == 0; min_run_h not finite or negative; a run output (cond_time, run_time, first_run, longest,
+ *     longest_start, nruns) given while threshold is NULL and threshold_all is not finite or is negative; b->dt NULL; every
+ *     output NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B.
+ */
+#define STE_SPEED_MAX_BANDS 32
+#define STE_SPEED_ABOVE 0x1u      /* flags: a step qualifies when v >= threshold (sustained speed); default v <= threshold (stops) */
+#define STE_SPEED_BAD_TIME 0x1    /* track_status: a dt below nsteps that is not finite and >= 0 */
+#define STE_SPEED_BAD_LIMIT 0x2   /* track_status: the track's threshold is not finite or is < 0 */
+typedef struct ste_speed_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;           /* STE_PREP_SPHERE / STE_PREP_WGS84: the leg function */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64; components 0 and 1 are read */
+    uint32_t flags;          /* STE_SPEED_ABOVE or 0 */
+    int32_t nbands;          /* 0 .. STE_SPEED_MAX_BANDS */
+    const double* band_edges;/* HOST [nbands + 1]: km/h, finite, >= 0, strictly ascending; NULL iff nbands == 0 */
+    const double* threshold; /* DEVICE [track_stride]: km/h per track, or NULL: threshold_all for every track */
+    double threshold_all;    /* km/h; NaN = no run output may be asked for */
+    double min_run_h;        /* hours, finite, >= 0: a run QUALIFIES when its length >= min_run_h */
+    double* speed;           /* DEVICE [S][Nmax][track_stride] or NULL: km/h of step k; NaN for a skipped or broken step */
+    double* dist;            /* DEVICE [S][track_stride] or NULL: km over the sound steps, in order */
+    double* sound_time;      /* DEVICE [S][track_stride] or NULL: hours of the sound steps, in order */
+    double* vmax;            /* DEVICE [S][track_stride] or NULL: the largest speed of a sound step; NaN = none */
+    double* vmax_time;       /* DEVICE [S][track_stride] or NULL: T_k of that step (hours from row 0, its start); NaN = none */
+    double* band_time;       /* DEVICE [S][nbands][track_stride] or NULL: hours of sound steps with edges[j] <= v < edges[j+1] */
+    double* cond_time;       /* DEVICE [S][track_stride] or NULL: hours of qualifying steps, whatever their run */
+    double* run_time;        /* DEVICE [S][track_stride] or NULL: hours inside qualifying runs */
+    double* first_run;       /* DEVICE [S][track_stride] or NULL: T at the start of the first qualifying run; NaN = none */
+    double* longest;         /* DEVICE [S][track_stride] or NULL: length of the longest run, qualifying or not; 0 = none */
+    double* longest_start;   /* DEVICE [S][track_stride] or NULL: T at its start; NaN = none */
+    int32_t* nruns;          /* DEVICE [S][track_stride] or NULL: qualifying runs */
+    int32_t* nbroken;        /* DEVICE [S][track_stride] or NULL: broken examined steps */
+    int32_t* track_status;   /* DEVICE [track_stride] or NULL: STE_SPEED_BAD_* (does not depend on the sample) */
+} ste_speed_f64;             /* 168 bytes */
+
+int ste_speed_metrics_f64(const ste_ukf_batch_f64* b, const ste_speed_f64* sp, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

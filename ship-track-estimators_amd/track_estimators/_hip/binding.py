@@ -348,6 +348,42 @@ class SteRouteF64(C.Structure):
     ]
 
 
+STE_SPEED_MAX_BANDS = 32
+STE_SPEED_ABOVE = 0x1
+STE_SPEED_BAD_TIME = 0x1
+STE_SPEED_BAD_LIMIT = 0x2
+
+
+class SteSpeedF64(C.Structure):
+    """Mirror of ``struct ste_speed_f64`` (include/ste.h): speeds, speed bands and runs of tracks on the device."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("flags", C.c_uint32),
+        ("nbands", C.c_int32),
+        ("band_edges", _dp),
+        ("threshold", _dp),
+        ("threshold_all", C.c_double),
+        ("min_run_h", C.c_double),
+        ("speed", _dp),
+        ("dist", _dp),
+        ("sound_time", _dp),
+        ("vmax", _dp),
+        ("vmax_time", _dp),
+        ("band_time", _dp),
+        ("cond_time", _dp),
+        ("run_time", _dp),
+        ("first_run", _dp),
+        ("longest", _dp),
+        ("longest_start", _dp),
+        ("nruns", _dp),
+        ("nbroken", _dp),
+        ("track_status", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -467,6 +503,7 @@ SYMBOLS = {
     "ste_route_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRouteF64), C.c_void_p]),
     "ste_route_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
     "ste_route_lds_cols": (C.c_int, []),
+    "ste_speed_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSpeedF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

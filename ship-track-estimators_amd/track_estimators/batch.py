@@ -1307,6 +1307,75 @@ class DeviceBatch:
                               keep)
             return self._finish(st, keep, out)
 
+    # -- speeds ---------------------------------------------------------------------------------------------------
+    _SPEED_OUT = ("dist", "sound_time", "vmax", "vmax_time")
+    _SPEED_RUNS = {"cond_time": False, "run_time": False, "first_run": False, "longest": False, "longest_start": False,
+                   "nruns": True}  # name -> int32?
+
+    def speed_metrics(self, states, bands=None, threshold=None, above: bool = False, min_run_h: float = 0.0,
+                      model: str = "sphere", per_step: bool = False, stream=None):
+        """How fast tracks that are on the device went (include/ste.h: ste_speed_metrics_f64; DESIGN.md, "Speeds"): the speed
+        made good of a step is its leg over its ``dt``, in km/h (``KNOT_KMH`` km/h to the knot).  ``states`` and ``model`` as in
+        ``path_metrics``.  ``bands``: None, or nbands + 1 <= 33 band edges in km/h, finite, >= 0 and strictly ascending.
+        ``threshold``: None, a scalar or one speed per track ((B,) array or tensor), km/h: a step qualifies at or below it
+        (stops, loitering), with ``above`` at or above it (sustained speed), and consecutive qualifying steps form a run that
+        counts when it lasts ``min_run_h`` hours or longer.  Returns a dict of device tensors, (S, B) unless said otherwise:
+        ``dist`` (km) and ``sound_time`` (hours) over the sound steps; ``vmax`` and ``vmax_time``, the largest speed and the
+        hours from row 0 to the start of its step, NaN without a sound step; ``nbroken`` int32, the steps left out (a
+        coordinate that is not finite); ``track_status`` (B,) int32, STE_SPEED_BAD_TIME (a ``dt`` that is not finite and >= 0)
+        and STE_SPEED_BAD_LIMIT (such a threshold): neither is refused, a bad track gives NaN / 0; with ``bands``
+        ``band_time`` (S, nbands, B), the hours with edges[j] <= v < edges[j+1]; with ``threshold`` ``cond_time`` (hours of
+        qualifying steps), ``run_time`` (hours in runs that count), ``nruns`` int32, ``first_run`` (hours from row 0 to the start
+        of the first run that counts, NaN = none), ``longest`` and ``longest_start`` (the longest run, counting or not); with
+        ``per_step`` ``speed`` (S, Nmax, B), NaN for a step of zero ``dt``, a broken step and past ``nsteps[b]``.  Windows,
+        in-place views and ``stream`` as in ``path_metrics``; every value depends on its own track's rows, ``dt`` and threshold
+        alone, and ``dist`` has the bits of ``path_metrics`` where every step is sound."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
+        edges = None
+        if bands is not None:
+            edges = np.ascontiguousarray(bands.cpu().numpy() if isinstance(bands, torch.Tensor) else bands, dtype=np.float64)
+            if edges.ndim != 1 or not 2 <= edges.size <= binding.STE_SPEED_MAX_BANDS + 1:
+                raise ValueError(f"bands must be None or 2 .. {binding.STE_SPEED_MAX_BANDS + 1} band edges, got shape {edges.shape}")
+        st = self._ordered_stream(stream)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            keep = []
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
+            sp = binding.SteSpeedF64()
+            sp.nstates, sp.model, sp.states = S, model_id, states.data_ptr()
+            sp.flags, sp.min_run_h = (binding.STE_SPEED_ABOVE if above else 0), float(min_run_h)
+            sp.nbands, sp.band_edges = (0, None) if edges is None else (edges.size - 1, edges.ctypes.data)
+            sp.threshold, sp.threshold_all = None, float("nan")
+            if threshold is not None:
+                tv = torch.as_tensor(threshold, dtype=torch.float64)
+                if tv.dim() == 0:
+                    sp.threshold_all = float(tv)
+                elif tuple(tv.shape) == (B,):
+                    limit = torch.zeros((width,), **f64)
+                    limit[col:col + B] = tv.to(self.device)
+                    keep.append(limit)
+                    sp.threshold = limit.data_ptr() + 8 * col
+                else:
+                    raise ValueError(f"threshold must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+            # rows as wide as the states': the window's columns are what the call writes and what is returned
+            full = {k: torch.empty((S, width), **f64) for k in self._SPEED_OUT}
+            full["nbroken"] = torch.empty((S, width), **i32)
+            full["track_status"] = torch.empty((width,), **i32)
+            if edges is not None:
+                full["band_time"] = torch.empty((S, edges.size - 1, width), **f64)
+            if threshold is not None:
+                full.update({k: torch.empty((S, width), **(i32 if int32 else f64)) for k, int32 in self._SPEED_RUNS.items()})
+            if per_step:
+                full["speed"] = torch.full((S, N, width), float("nan"), **f64)
+            for k, ten in full.items():
+                setattr(sp, k, ten.data_ptr() + ten.element_size() * col)
+            binding.check(self.lib.ste_speed_metrics_f64(C.byref(s), C.byref(sp), self._stream(st)), "ste_speed_metrics_f64")
+            return self._finish(st, keep, {k: ten[..., col:col + B] for k, ten in full.items()})
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2400,6 +2469,77 @@ def path_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, mod
         with warnings.catch_warnings():  # a track that no sample takes across the line: all-NaN column, NaN quantiles
             warnings.simplefilter("ignore", RuntimeWarning)
             out["cross_time_quantiles"] = np.nanquantile(ct, q, axis=0)
+    out["status"] = status.cpu().numpy()
+    return out
+
+
+KNOT_KMH = 1.852  # km/h to the knot: speeds here are km/h
+
+
+def speed_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, bands=None, threshold=None, above: bool = False,
+                     min_run_h: float = 0.0, limit_kmh=None, quantiles=(0.05, 0.5, 0.95), model: str = "sphere",
+                     device="cuda:0", draws=None):
+    """How fast the ships went, with the uncertainty of the smoothing posterior, per track: ``nsamples`` posterior tracks are
+    drawn (``DeviceBatch.sample_smoothed``), reduced to their speeds (``DeviceBatch.speed_metrics``) and discarded, ``chunk``
+    samples at a time, with the generator discipline of ``path_statistics`` (``draws`` as in ``site_statistics``).  What stays
+    is (nsamples, B) for the largest speed and the mean speed, and sums per track that take their terms in sample order, so
+    for given draws they do not depend on ``chunk``.  Given a ``HostBatch`` it uploads it and runs the forward pass and the
+    smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``bands``, ``threshold``,
+    ``above``, ``min_run_h`` and ``model`` as in ``speed_metrics``; ``limit_kmh``: None, a scalar or one speed per track, the
+    speed the ship cannot make.
+
+    Returns a dict of NumPy arrays in the batch's slot order: every output of ``speed_metrics`` for the smoothed track
+    ``sm_mean`` under ``*_smoothed`` names ((B,), ``band_time_smoothed`` (nbands, B)) with ``mean_speed_smoothed`` =
+    dist / sound_time (NaN without a sound step); ``mean_speed`` and ``vmax`` (nsamples, B) with ``*_mean``, ``*_std`` (ddof = 1,
+    0 for a single sample) and ``*_quantiles`` (len(quantiles), B) over the samples that have a value; with ``limit_kmh``
+    ``exceed_prob`` (B,), the fraction of samples with vmax > limit_kmh; with ``threshold`` ``run_prob``, the fraction with a
+    run that counts, ``cond_time_mean`` and ``run_time_mean``; with ``bands`` ``band_time_mean`` (nbands, B);
+    ``track_status`` (B,) and ``status`` (B,), the sampler's STE_STATUS_* bits."""
+    import warnings
+
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "speed_statistics")
+    torch = db.torch
+    B = db.ntracks
+    limit = None
+    if limit_kmh is not None:
+        limit = np.asarray(limit_kmh.cpu().numpy() if isinstance(limit_kmh, torch.Tensor) else limit_kmh, dtype=np.float64)
+        if limit.ndim and limit.shape != (B,):
+            raise ValueError(f"limit_kmh must be None, a scalar or have shape ({B},), got {limit.shape}")
+    kw = dict(bands=bands, threshold=threshold, above=above, min_run_h=min_run_h, model=model)
+    smoothed = db.speed_metrics(db.sm_mean, **kw)
+    f64 = dict(dtype=torch.float64, device=db.device)
+    kept = {k: torch.empty((nsamples, B), **f64) for k in ("mean_speed", "vmax")}
+    sums = {k: torch.zeros_like(smoothed[k][0]) for k in ("band_time", "cond_time", "run_time") if k in smoothed}
+    with_run = torch.zeros((B,), dtype=torch.int32, device=db.device) if threshold is not None else None
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk, draws=draws)
+    for i, n, samples in chunks:
+        m = db.speed_metrics(samples, **kw)
+        kept["mean_speed"][i:i + n] = m["dist"] / m["sound_time"]  # 0 / 0 = NaN: no sound step
+        kept["vmax"][i:i + n] = m["vmax"]
+        for s in range(n):  # sample by sample: the sums take their terms in sample order whatever the chunk
+            for k in sums:
+                sums[k] += m[k][s]
+            if with_run is not None:
+                with_run += m["nruns"][s] > 0
+    status = chunks.status
+    out = {k + "_smoothed": v[0].cpu().numpy() for k, v in smoothed.items() if k != "track_status"}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["mean_speed_smoothed"] = out["dist_smoothed"] / out["sound_time_smoothed"]
+    q = np.asarray(quantiles, dtype=np.float64)
+    with warnings.catch_warnings():  # a track no sample gives a sound step: all-NaN column, NaN out
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for k, ten in kept.items():
+            a = ten.cpu().numpy()
+            out[k], out[k + "_mean"], out[k + "_quantiles"] = a, np.nanmean(a, axis=0), np.nanquantile(a, q, axis=0)
+            out[k + "_std"] = np.nanstd(a, axis=0, ddof=1) if nsamples > 1 else np.where(np.isnan(a[0]), np.nan, 0.0)
+    if limit is not None:
+        with np.errstate(invalid="ignore"):
+            out["exceed_prob"] = (out["vmax"] > limit).mean(axis=0)
+    if with_run is not None:
+        out["run_prob"] = with_run.cpu().numpy() / float(nsamples)
+    for k, ten in sums.items():
+        out[k + "_mean"] = ten.cpu().numpy() / float(nsamples)
+    out["track_status"] = smoothed["track_status"].cpu().numpy()
     out["status"] = status.cpu().numpy()
     return out
 

@@ -449,6 +449,47 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         res.update({k: out[k][:, 0] for k in ("visit_prob", "call_prob", "min_dist_mean", "time_within_mean", "longest_mean")})
         return res
 
+    def speed_profile(self, bands=None, threshold=None, above: bool = False, min_run_h: float = 0.0, limit_kmh=None,
+                      nsamples: int = 0, model: str = "sphere", random_state: int = 0):
+        """How fast the track ``run`` filtered went (``DeviceBatch.speed_metrics`` and
+        ``track_estimators.batch.speed_statistics``; no counterpart in the reference).  Speeds are km/h
+        (``track_estimators.batch.KNOT_KMH`` to the knot), times hours from the first row; ``bands``, ``threshold``, ``above``
+        and ``min_run_h`` as in ``speed_metrics``.  ``nsamples == 0``: a dict of the smoothed track's values, ``dist``,
+        ``sound_time``, ``mean_speed``, ``vmax``, ``vmax_time``, ``nbroken``, ``speed`` (one per step), with ``bands``
+        ``band_time`` (nbands,), with ``threshold`` ``cond_time``, ``run_time``, ``nruns``, ``first_run``, ``longest``,
+        ``longest_start``, and with ``limit_kmh`` ``exceeds``, whether ``vmax`` is above it.  Otherwise those (but ``speed`` and
+        ``exceeds``) under ``*_smoothed`` names and, over that many tracks drawn from the joint smoothing posterior, the
+        ``*_mean``, ``*_std`` and ``*_quantiles`` of ``mean_speed`` and ``vmax``, ``exceed_prob`` (with ``limit_kmh``),
+        ``run_prob``, ``cond_time_mean``, ``run_time_mean`` (with ``threshold``) and ``band_time_mean`` (with ``bands``).  The
+        track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("speed_profile() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("speed_profile() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        nsamples = int(nsamples)
+        if nsamples < 0:
+            raise ValueError(f"nsamples must be >= 0, got {nsamples!r}")
+        kw = dict(bands=bands, threshold=threshold, above=above, min_run_h=min_run_h, model=model)
+        if nsamples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            got = db.speed_metrics(db.sm_mean, per_step=True, **kw)
+            res = {k: v[0, ..., 0].cpu().numpy() for k, v in got.items() if k != "track_status"}
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res["mean_speed"] = res["dist"] / res["sound_time"]
+            if limit_kmh is not None:
+                res["exceeds"] = bool(res["vmax"] > float(limit_kmh))
+            return res
+        out = _batch.speed_statistics(hb, nsamples, seed=int(random_state), chunk=nsamples, limit_kmh=limit_kmh, **kw)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return {k: v[..., 0] for k, v in out.items() if k not in ("status", "track_status", "mean_speed", "vmax")}
+
     def line_approach(self, lines, nsamples: int = 0, within_km=None, model: str = "sphere", random_state: int = 0):
         """The track ``run`` filtered against polylines -- coasts, cables, routes, gates -- (``DeviceBatch.line_metrics``
         and ``track_estimators.batch.line_statistics``; no counterpart in the reference).  ``lines``: a list of (n, 2) lon /
