@@ -33,6 +33,9 @@
  *                            (the reference's performance_metrics.py compares two tracks row by row, which needs equal rows)
  *   ste_speed_metrics_f64    speed made good per step, its maximum, hours per speed band and runs at or below (above) a speed
  *                            threshold (stops, sustained speed) of such tracks: the per-leg distance of utils.py:9-113 over dt
+ *   ste_track_errors_f64     error of such tracks against truth positions at the tracks' own rows, in km, split along and across
+ *                            the true course and scored against the track's covariance (performance_metrics.py: rmse,
+ *                            cum_abs_diff and abs_diff compare in degrees, one ship at a time, on downloaded arrays)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -73,7 +76,8 @@ extern "C" {
                            (ste_site_metrics_f64).  Unnumbered addition: tracks on the device against polylines
                            (ste_line_metrics_f64).  Unnumbered addition: pairs of tracks on the device as curves
                            (ste_route_metrics_f64).  Unnumbered addition: speed made good, speed bands and stops of tracks on
-                           the device (ste_speed_metrics_f64).
+                           the device (ste_speed_metrics_f64).  Unnumbered addition: errors of tracks on the device against
+                           truth positions (ste_track_errors_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1005,6 +1009,83 @@ typedef struct ste_speed_f64 {
 } ste_speed_f64;             /* 168 bytes */
 
 int ste_speed_metrics_f64(const ste_ukf_batch_f64* b, const ste_speed_f64* sp, void* stream);
+
+/*
+ * ERRORS: how far tracks that stay on the device are from where the ship really was (an unnumbered addition, like ste_speed_f64):
+ * the distance of every row from a truth position of that row, in km, its sums, its split along and across the true course, and its
+ * score against the track's own covariance (NEES and coverage).  `states` is that of ste_path_f64.  Every expression below is
+ * evaluated as written, left to right, without contraction.
+ *   - Rows.  Row k of track t, 0 <= k <= nsteps[t], is TRUTHED when both coordinates of truth row k are finite.  A truthed row is
+ *     BROKEN when the state's lon or lat is not finite, or when the leg below is not finite: it adds 1 to nbroken, writes NaN to
+ *     the row outputs err, along, cross and nees, and adds nothing else.  Every other truthed row is SOUND.  Rows are taken in the
+ *     order of k, which defines "first" below.
+ *   - Error.  e_k is the distance of the leg of `model` FROM the truth (point 1) TO the state (point 2), km, and h_k that leg's
+ *     initial heading, degrees in [0, 360): sphere_leg / wgs84_leg of ste_geodesy.h, what ste_track_prep_f64 computes for two
+ *     observations (WGS84: 0 and 0 for points closer than 1e-8 degrees in both coordinates).
+ *   - Sums over the sound rows, in order: n counts them, sum_err adds e_k, sum_sq adds e_k * e_k.  A sound row becomes the worst
+ *     one when e_k > max_err (strict, so the first row wins a tie); it records max_err = e_k and max_row = k.  With no sound row
+ *     max_err is NaN and max_row is -1.  cumerr row k is sum_err after row k; rows that are not sound carry the running value, so
+ *     sum_err equals cumerr row nsteps[t] bit for bit (cum_abs_diff in km; rmse is sqrt(sum_sq / n)).
+ *   - Along and cross (with `course`).  A sound row is COURSED when course row k is finite.  theta = (h_k - course_k) * kDeg2Rad
+ *     (0.017453292519943295), along_k = e_k * cos(theta), positive when the state is ahead of the truth, cross_k =
+ *     e_k * sin(theta), positive to starboard.  ncoursed counts the coursed rows; sum_along, sum_along_sq, sum_cross and
+ *     sum_cross_sq add along_k, along_k * along_k, cross_k and cross_k * cross_k over them, in order.  A sound row without a
+ *     course writes NaN to along and cross and adds nothing to these sums.
+ *   - NEES (with `cov`).  dx = wrap180(lon - lon_t), dy = lat - lat_t, degrees, wrap180(y) = floored_mod(y + 180, 360) - 180;
+ *     a, b, c are entries 00, 01 and 11 of the covariance of row k (rows 0, 1, 5 of 16, rows 0, 1, 4 of 10);
+ *     det = a * c - b * b; q_k = (c * dx * dx - 2.0 * b * dx * dy + a * dy * dy) / det.  A sound row is SCORED when a, b, c and
+ *     q_k are finite, a > 0 and det > 0.  nscored counts the scored rows, sum_nees adds q_k over them in order, ninside counts
+ *     those with q_k <= nees_limit (coverage is ninside / nscored; -2 ln(1 - p) is the chi-square quantile for 2 degrees of
+ *     freedom).  A row that is not scored writes NaN to nees.
+ *   - Row outputs.  err, along, cross and nees of a row k <= nsteps[t] that is not truthed, or not sound, are NaN; cumerr of
+ *     such a row is the running value.  Rows past nsteps[t] of every row output are not written.  No tolerance anywhere.
+ *   - Every value's bits depend on the track's rows, truth, course and covariance, and on nees_limit alone: not on S, the window,
+ *     the lane, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride and nsteps (NULL = Nmax for every track) of the batch, no dt, and writes nothing
+ *     of the batch; windows and addressing are those of ste_path_metrics_f64: truth, course and cov are rows of track_stride tracks
+ *     like the batch's own arrays and do not depend on the sample.  Rows past nsteps[t] are not read.  Per (sample, track)
+ *     outputs are out[s * track_stride + t], row outputs out[(s * (Nmax + 1) + k) * track_stride + t] (track_stride = B where it
+ *     is 0).
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or er NULL; states or truth NULL; nstates < 1
+ *     or > 65535; an unknown model; cov_rows not 16 or 10 while cov is given; cov with nstates > 1 (a covariance belongs to one
+ *     track, not to its samples); nees_limit not finite or <= 0 while cov is given; an along / cross output (sum_along,
+ *     sum_along_sq, sum_cross, sum_cross_sq, ncoursed, along, cross) without course; a NEES output (sum_nees, nscored, ninside,
+ *     nees) without cov; reserved != 0; every output NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B.
+ */
+#define STE_ERRORS_COV_FULL 16    /* cov_rows: full 4 x 4 matrices, row-major (sm_cov without STE_FLAG_PACKED_COV) */
+#define STE_ERRORS_COV_PACKED 10  /* cov_rows: upper triangles 00 01 02 03 11 12 13 22 23 33 (STE_FLAG_PACKED_COV) */
+typedef struct ste_errors_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    int32_t model;           /* STE_PREP_SPHERE / STE_PREP_WGS84: the leg function */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64; components 0 and 1 are read */
+    const double* truth;     /* DEVICE [Nmax+1][2][track_stride]: lon, lat in degrees; a row that is not finite has no truth */
+    const double* course;    /* DEVICE [Nmax+1][track_stride] or NULL: the true course over ground, degrees */
+    const double* cov;       /* DEVICE [Nmax+1][cov_rows][track_stride] or NULL: the track's covariance (sm_cov, fwd_cov); S == 1 */
+    int32_t cov_rows;        /* STE_ERRORS_COV_FULL or STE_ERRORS_COV_PACKED; read only with cov */
+    int32_t reserved;        /* 0 */
+    double nees_limit;       /* q_k <= nees_limit counts as inside; finite and > 0; read only with cov */
+    double* sum_err;         /* DEVICE [S][track_stride] or NULL: km, the sum of e_k over the sound rows */
+    double* sum_sq;          /* DEVICE [S][track_stride] or NULL: km^2 */
+    double* max_err;         /* DEVICE [S][track_stride] or NULL: the largest e_k; NaN = no sound row */
+    double* sum_along;       /* DEVICE [S][track_stride] or NULL: km over the coursed rows */
+    double* sum_along_sq;    /* DEVICE [S][track_stride] or NULL */
+    double* sum_cross;       /* DEVICE [S][track_stride] or NULL */
+    double* sum_cross_sq;    /* DEVICE [S][track_stride] or NULL */
+    double* sum_nees;        /* DEVICE [S][track_stride] or NULL: the sum of q_k over the scored rows */
+    int32_t* n;              /* DEVICE [S][track_stride] or NULL: sound rows */
+    int32_t* max_row;        /* DEVICE [S][track_stride] or NULL: the row of max_err; -1 = none */
+    int32_t* nbroken;        /* DEVICE [S][track_stride] or NULL: broken rows */
+    int32_t* ncoursed;       /* DEVICE [S][track_stride] or NULL: coursed rows */
+    int32_t* nscored;        /* DEVICE [S][track_stride] or NULL: scored rows */
+    int32_t* ninside;        /* DEVICE [S][track_stride] or NULL: scored rows with q_k <= nees_limit */
+    double* err;             /* DEVICE [S][Nmax+1][track_stride] or NULL: e_k; NaN for a row without truth and for a broken row */
+    double* cumerr;          /* DEVICE [S][Nmax+1][track_stride] or NULL: sum_err after row k */
+    double* along;           /* DEVICE [S][Nmax+1][track_stride] or NULL: NaN unless coursed */
+    double* cross;           /* DEVICE [S][Nmax+1][track_stride] or NULL: NaN unless coursed */
+    double* nees;            /* DEVICE [S][Nmax+1][track_stride] or NULL: q_k; NaN unless scored */
+} ste_errors_f64;            /* 208 bytes */
+
+int ste_track_errors_f64(const ste_ukf_batch_f64* b, const ste_errors_f64* er, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -6,4 +6,4 @@ runs in hand-written HIP kernels (csrc/) reached through the C ABI of include/st
 """
 __version__ = "0.1.0+mi355x"
 
-__all__ = ["__version__", "kalman_filters", "utils", "constants", "ship_track", "batch", "synthetic"]
+__all__ = ["__version__", "kalman_filters", "utils", "constants", "ship_track", "batch", "synthetic", "performance_metrics"]

@@ -384,6 +384,45 @@ class SteSpeedF64(C.Structure):
     ]
 
 
+STE_ERRORS_COV_FULL = 16
+STE_ERRORS_COV_PACKED = 10
+
+
+class SteErrorsF64(C.Structure):
+    """Mirror of ``struct ste_errors_f64`` (include/ste.h): errors of tracks on the device against truth positions."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("model", C.c_int32),
+        ("states", _dp),
+        ("truth", _dp),
+        ("course", _dp),
+        ("cov", _dp),
+        ("cov_rows", C.c_int32),
+        ("reserved", C.c_int32),
+        ("nees_limit", C.c_double),
+        ("sum_err", _dp),
+        ("sum_sq", _dp),
+        ("max_err", _dp),
+        ("sum_along", _dp),
+        ("sum_along_sq", _dp),
+        ("sum_cross", _dp),
+        ("sum_cross_sq", _dp),
+        ("sum_nees", _dp),
+        ("n", _dp),
+        ("max_row", _dp),
+        ("nbroken", _dp),
+        ("ncoursed", _dp),
+        ("nscored", _dp),
+        ("ninside", _dp),
+        ("err", _dp),
+        ("cumerr", _dp),
+        ("along", _dp),
+        ("cross", _dp),
+        ("nees", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -504,6 +543,7 @@ SYMBOLS = {
     "ste_route_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
     "ste_route_lds_cols": (C.c_int, []),
     "ste_speed_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSpeedF64), C.c_void_p]),
+    "ste_track_errors_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteErrorsF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1376,6 +1376,110 @@ class DeviceBatch:
             binding.check(self.lib.ste_speed_metrics_f64(C.byref(s), C.byref(sp), self._stream(st)), "ste_speed_metrics_f64")
             return self._finish(st, keep, {k: ten[..., col:col + B] for k, ten in full.items()})
 
+    # -- errors ---------------------------------------------------------------------------------------------------
+    _ERROR_OUT = {"sum_err": False, "sum_sq": False, "max_err": False, "n": True, "max_row": True, "nbroken": True}  # name -> int32?
+    _ERROR_COURSE = {"sum_along": False, "sum_along_sq": False, "sum_cross": False, "sum_cross_sq": False, "ncoursed": True}
+    _ERROR_NEES = {"sum_nees": False, "nscored": True, "ninside": True}
+
+    def _track_rows(self, x, name: str, mid, width, col, keep):
+        """A per-row input of a metric call that does not depend on the sample -- (Nmax+1, B), or (Nmax+1, r, B) with r in
+        ``mid`` -- as (the pointer the kernel takes, r): an array is uploaded; a device tensor whose rows already are ``width``
+        tracks wide and start at this batch's column (``window.sm_cov`` beside ``window.sm_mean``) is read where it lies,
+        anything else is copied into such rows.  Inside the stream context."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        shapes = [(N + 1, B)] if mid is None else [(N + 1, r, B) for r in mid]
+        if x.dtype != torch.float64 or tuple(x.shape) not in shapes:
+            raise ValueError(f"{name} must be float64 of shape {' or '.join(str(s) for s in shapes)}, got {x.dtype} {tuple(x.shape)}")
+        r = 1 if mid is None else int(x.shape[1])
+        x = x.to(self.device)
+        rows_strides = (r * width, 1) if mid is None else (r * width, width, 1)
+        if all(n == 1 or sd == fd for n, sd, fd in zip(x.shape, x.stride(), rows_strides)):
+            keep.append(x)
+            return x.data_ptr(), r
+        wide = torch.full(x.shape[:-1] + (width,), float("nan"), dtype=torch.float64, device=self.device)
+        wide[..., col:col + B] = x
+        keep.append(wide)
+        return wide.data_ptr() + 8 * col, r
+
+    def track_errors(self, states, truth, course=None, cov=None, coverage: float = 0.95, model: str = "sphere", rows: bool = False,
+                     cumulative: bool = False, stream=None):
+        """How far tracks that are on the device are from where the ship really was (include/ste.h: ste_track_errors_f64;
+        DESIGN.md, "Errors").  ``states`` and ``model`` as in ``path_metrics``.  ``truth``: (Nmax+1, 2, B), lon and lat in
+        degrees at the tracks' own rows, track last, NaN where there is no truth (``observation_rows`` and ``hold_out`` make
+        one); the error of a row is the leg of ``model`` from the truth to the state, in km.  ``course``: None or (Nmax+1, B),
+        the true course over ground in degrees (``truth_course``), which splits the error into ``along`` (positive when the
+        state is ahead of the truth: timing) and ``cross`` (positive to starboard: route).  ``cov``: None, "sm" or "fwd" (this
+        batch's smoothed or filtered covariance) or a (Nmax+1, 10 or 16, B) tensor, upper triangles or full matrices, for S = 1
+        only: q = d^T C^-1 d of the position error d in degrees against the 2 x 2 position block C is the NEES of a row, and
+        a row is inside when q <= -2 ln(1 - ``coverage``), the chi-square quantile for 2 degrees of freedom.
+
+        Returns a dict of device tensors, (S, B): ``sum_err`` (km; cum_abs_diff's last value), ``sum_sq``, ``max_err`` and
+        ``max_row`` int32 (NaN and -1 without a sound row), ``n`` int32 (the rows with truth and a finite error) and
+        ``nbroken`` int32 (rows with truth whose state or leg is not finite), and derived from them ``rmse`` =
+        sqrt(sum_sq / n) and ``mean_err``; with ``course`` ``sum_along``, ``sum_along_sq``, ``sum_cross``, ``sum_cross_sq``,
+        ``ncoursed`` int32, ``mean_along`` and ``rms_cross``; with ``cov`` ``sum_nees``, ``nscored`` and ``ninside`` int32,
+        ``mean_nees`` and ``coverage`` = ninside / nscored.  A derived value is NaN where its count is 0.  With ``rows`` the
+        per-row values (S, Nmax+1, B) ``err``, and ``along``, ``cross``, ``nees`` where they exist, NaN where the row has none
+        and past ``nsteps[b]``; with ``cumulative`` ``cumerr``, the running sum_err, NaN past ``nsteps[b]``.  Windows, in-place
+        views and ``stream`` as in ``path_metrics``; every value depends on its own track's rows, truth, course and covariance
+        alone."""
+        import math
+
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        states, S = self._metric_states(states)
+        model_id = _metric_model(model)
+        if isinstance(cov, str):
+            if cov not in ("sm", "fwd"):
+                raise ValueError(f"cov must be None, 'sm', 'fwd' or a tensor, got {cov!r}")
+            cov = self.sm_cov if cov == "sm" else self.fwd_cov
+            if cov is None:
+                raise ValueError("this batch holds no such covariance history (alloc_smoothed=False or histories=False)")
+        if cov is not None:
+            if S != 1:
+                raise ValueError(f"cov goes with one track per ship (a covariance belongs to one track, not to its samples), got S = {S}")
+            if not 0.0 < float(coverage) < 1.0:
+                raise ValueError(f"coverage must lie strictly between 0 and 1, got {coverage!r}")
+        st = self._ordered_stream(stream)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            keep = []
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=False)
+            er = binding.SteErrorsF64()
+            er.nstates, er.model, er.states, er.reserved = S, model_id, states.data_ptr(), 0
+            er.truth, _ = self._track_rows(truth, "truth", (2,), width, col, keep)
+            names = dict(self._ERROR_OUT)
+            per_row = ["err"] if rows else []
+            if course is not None:
+                er.course, _ = self._track_rows(course, "course", None, width, col, keep)
+                names.update(self._ERROR_COURSE)
+                per_row += ["along", "cross"] if rows else []
+            if cov is not None:
+                er.cov, er.cov_rows = self._track_rows(cov, "cov", (binding.STE_ERRORS_COV_PACKED, binding.STE_ERRORS_COV_FULL),
+                                                       width, col, keep)
+                er.nees_limit = -2.0 * math.log(1.0 - float(coverage))
+                names.update(self._ERROR_NEES)
+                per_row += ["nees"] if rows else []
+            per_row += ["cumerr"] if cumulative else []
+            # rows as wide as the states': the window's columns are what the call writes and what is returned
+            full = {k: torch.empty((S, width), **(i32 if int32 else f64)) for k, int32 in names.items()}
+            full.update({k: torch.full((S, N + 1, width), float("nan"), **f64) for k in per_row})
+            for k, ten in full.items():
+                setattr(er, k, ten.data_ptr() + ten.element_size() * col)
+            binding.check(self.lib.ste_track_errors_f64(C.byref(s), C.byref(er), self._stream(st)), "ste_track_errors_f64")
+            out = {k: ten[..., col:col + B] for k, ten in full.items()}
+            out["rmse"], out["mean_err"] = torch.sqrt(out["sum_sq"] / out["n"]), out["sum_err"] / out["n"]  # 0 / 0 = NaN
+            if course is not None:
+                out["mean_along"] = out["sum_along"] / out["ncoursed"]
+                out["rms_cross"] = torch.sqrt(out["sum_cross_sq"] / out["ncoursed"])
+            if cov is not None:
+                out["mean_nees"], out["coverage"] = out["sum_nees"] / out["nscored"], out["ninside"].double() / out["nscored"]
+            return self._finish(st, keep, out)
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -2540,6 +2644,132 @@ def speed_statistics(hb_or_db, nsamples: int, seed: int = 0, chunk: int = 16, ba
     for k, ten in sums.items():
         out[k + "_mean"] = ten.cpu().numpy() / float(nsamples)
     out["track_status"] = smoothed["track_status"].cpu().numpy()
+    out["status"] = status.cpu().numpy()
+    return out
+
+
+def observation_rows(hb: "HostBatch", upd_idx=None) -> np.ndarray:
+    """The truth array (Nmax+1, 2, B) that a batch's own observations define, for ``DeviceBatch.track_errors``: row 0 is
+    column 0 of ``hb.z`` (lon, lat) when ``hb.initial_update``; row k + 1 is column ``upd_idx[k]`` of ``z`` where
+    0 <= ``upd_idx[k]`` < Tmax (``upd_idx``: (Nmax, B), default ``hb.upd_idx``): the report that step k's update used.
+    Everything else is NaN."""
+    upd = np.asarray(hb.upd_idx if upd_idx is None else upd_idx)
+    if upd.shape != (hb.Nmax, hb.B):
+        raise ValueError(f"upd_idx must have shape ({hb.Nmax}, {hb.B}), got {upd.shape}")
+    truth = np.full((hb.Nmax + 1, 2, hb.B), np.nan)
+    if hb.initial_update:
+        truth[0] = hb.z[0, :2]
+    k, b = np.nonzero((upd >= 0) & (upd < hb.Tmax))
+    truth[k + 1, :, b] = hb.z[upd[k, b], :2, b]
+    return truth
+
+
+def hold_out(hb: "HostBatch", every: int, offset: int = 0):
+    """Withhold every ``every``-th report from the filter and keep it as truth: returns ``(hb_thin, truth)``.  In every track
+    the updates after the initial one (the steps with 0 <= ``upd_idx`` < Tmax) are counted in step order from 0; those whose
+    ordinal is ``offset`` modulo ``every`` get ``upd_idx`` = -1 in a copy of the batch, and ``truth`` (Nmax+1, 2, B, as
+    ``observation_rows``) holds the positions of exactly those withheld reports at their rows, NaN everywhere else.  The
+    initial update stays; ``every=1`` withholds all the others.
+
+    What this does not withhold: ``sog_rate`` / ``cog_rate`` (and their smoother counterparts) and the SOG / COG columns of
+    ``z`` were prepared from ALL reports, the withheld ones included, so the dynamics between two kept reports still carry
+    information from the report in between.  A stricter experiment thins the reports first and packs the batch again from
+    what is left."""
+    every, offset = int(every), int(offset)
+    if every < 1 or not 0 <= offset < every:
+        raise ValueError(f"every must be >= 1 and 0 <= offset < every, got every = {every} and offset = {offset}")
+    fires = (hb.upd_idx >= 0) & (hb.upd_idx < hb.Tmax)
+    ordinal = np.cumsum(fires, axis=0) - 1  # of the update of step k among its track's updates
+    withheld = fires & (ordinal % every == offset)
+    thin = dataclasses.replace(hb, upd_idx=np.ascontiguousarray(np.where(withheld, -1, hb.upd_idx).astype(hb.upd_idx.dtype)))
+    truth = observation_rows(hb, np.where(withheld, hb.upd_idx, -1))
+    truth[0] = np.nan
+    return thin, truth
+
+
+def truth_course(truth, model: str = "sphere", device="cuda:0") -> np.ndarray:
+    """The true course over ground (Nmax+1, B) that a truth array (Nmax+1, 2, B) implies, for ``DeviceBatch.track_errors``:
+    at a row with truth, the heading from it to the track's next row with truth; the last such row takes its predecessor's;
+    NaN at rows without truth and for a track with fewer than two of them.  It is the COG of ``prepare_observations``
+    (``ste_track_prep_f64``) for the rows with truth taken as consecutive reports, so the leg function is the project's."""
+    truth = np.asarray(truth, dtype=np.float64)
+    if truth.ndim != 3 or truth.shape[1] != 2:
+        raise ValueError(f"truth must have shape (Nmax+1, 2, B), got {truth.shape}")
+    _metric_model(model)
+    have = np.isfinite(truth[:, 0]) & np.isfinite(truth[:, 1])  # (Nmax+1, B)
+    course = np.full((truth.shape[0], truth.shape[2]), np.nan)
+    tracks = [b for b in range(truth.shape[2]) if have[:, b].sum() >= 2]
+    if not tracks:
+        return course
+    rows = [np.flatnonzero(have[:, b]) for b in tracks]
+    res = prepare_observations([truth[r, 0, b] for r, b in zip(rows, tracks)], [truth[r, 1, b] for r, b in zip(rows, tracks)],
+                               [np.ones(len(r) - 1) for r in rows], model=model, device=device)
+    for r, b, got in zip(rows, tracks, res):
+        course[r, b] = got["cog"]
+    return course
+
+
+def error_statistics(hb_or_db, truth, nsamples: int, seed: int = 0, chunk: int = 16, course=None, model: str = "sphere",
+                     within_km=None, quantiles=None, rows: bool = False, draws=None, device="cuda:0"):
+    """The error against truth positions with the uncertainty of the smoothing posterior, per track: ``nsamples`` posterior
+    tracks are drawn (``DeviceBatch.sample_smoothed``), held against ``truth`` (``DeviceBatch.track_errors``) and discarded,
+    ``chunk`` samples at a time, with the generator discipline of ``path_statistics`` (``draws`` as in ``site_statistics``), so
+    memory does not grow with ``nsamples``: what stays is (nsamples, B) for the rmse and, with ``rows``, one sum per row that
+    takes its terms in sample order, so for given draws nothing depends on ``chunk``.  Given a ``HostBatch`` it uploads it and
+    runs the forward pass and the smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed
+    ``run()``.  ``truth``, ``course`` and ``model`` as in ``track_errors``; ``within_km``: None, a scalar or one distance per
+    track.
+
+    Returns a dict of NumPy arrays in the batch's slot order.  Over the samples: ``rmse`` (nsamples, B), ``rmse_mean``,
+    ``rmse_std`` (ddof = 1, 0 for a single sample), with ``quantiles`` ``rmse_quantiles`` (len(quantiles), B), with
+    ``within_km`` ``within_prob``, the fraction of samples with rmse <= within_km, and with ``rows`` ``err_rows_mean``
+    (Nmax+1, B), the mean error of each row over the samples that have one (NaN where none has).  A track without a sound row
+    has NaN.  Beside them the smoothed track's own figures, scored against ``sm_cov``: ``n``, ``rmse_smoothed``,
+    ``mean_err_smoothed``, ``mean_nees_smoothed``, ``coverage_smoothed`` (at 0.95) and, with ``course``,
+    ``mean_along_smoothed`` and ``rms_cross_smoothed``; and ``status`` (B,), the sampler's STE_STATUS_* bits."""
+    import warnings
+
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "error_statistics")
+    torch = db.torch
+    B, N = db.ntracks, int(db.struct.Nmax)
+    limit = None
+    if within_km is not None:
+        limit = np.asarray(within_km.cpu().numpy() if isinstance(within_km, torch.Tensor) else within_km, dtype=np.float64)
+        if limit.ndim and limit.shape != (B,):
+            raise ValueError(f"within_km must be None, a scalar or have shape ({B},), got {limit.shape}")
+    up = lambda a: a if a is None or isinstance(a, torch.Tensor) else torch.from_numpy(  # noqa: E731
+        np.ascontiguousarray(a, dtype=np.float64)).to(db.device)
+    truth, course = up(truth), up(course)  # uploaded once, not once per chunk
+    smoothed = db.track_errors(db.sm_mean, truth, course=course, cov="sm", model=model)
+    f64 = dict(dtype=torch.float64, device=db.device)
+    rmse = torch.empty((nsamples, B), **f64)
+    row_sum = torch.zeros((N + 1, B), **f64) if rows else None
+    row_cnt = torch.zeros((N + 1, B), dtype=torch.int32, device=db.device) if rows else None
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk, draws=draws)
+    for i, n, samples in chunks:
+        m = db.track_errors(samples, truth, model=model, rows=rows)
+        rmse[i:i + n] = m["rmse"]
+        for s in range(n if rows else 0):  # sample by sample: the sums take their terms in sample order whatever the chunk
+            has = ~torch.isnan(m["err"][s])
+            row_sum += torch.where(has, m["err"][s], torch.zeros_like(row_sum))
+            row_cnt += has
+    status = chunks.status
+    a = rmse.cpu().numpy()
+    out = {"rmse": a, "n": smoothed["n"][0].cpu().numpy()}
+    with warnings.catch_warnings():  # a track without truth: all-NaN column, NaN out
+        warnings.simplefilter("ignore", RuntimeWarning)
+        out["rmse_mean"] = np.nanmean(a, axis=0)
+        out["rmse_std"] = np.nanstd(a, axis=0, ddof=1) if nsamples > 1 else np.where(np.isnan(a[0]), np.nan, 0.0)
+        if quantiles is not None:
+            out["rmse_quantiles"] = np.nanquantile(a, np.asarray(quantiles, dtype=np.float64), axis=0)
+    if limit is not None:
+        with np.errstate(invalid="ignore"):
+            out["within_prob"] = np.where(np.isnan(a).all(axis=0), np.nan, (a <= limit).mean(axis=0))
+    if rows:
+        out["err_rows_mean"] = (row_sum / row_cnt).cpu().numpy()  # 0 / 0 = NaN: no sample has an error in that row
+    for k in ("rmse", "mean_err", "mean_along", "rms_cross", "mean_nees", "coverage"):
+        if k in smoothed:
+            out[k + "_smoothed"] = smoothed[k][0].cpu().numpy()
     out["status"] = status.cpu().numpy()
     return out
 

@@ -490,6 +490,53 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return {k: v[..., 0] for k, v in out.items() if k not in ("status", "track_status", "mean_speed", "vmax")}
 
+    def track_error(self, truth=None, n_samples: int = 0, course=None, coverage: float = 0.95, within_km=None,
+                    quantiles=None, model: str = "sphere", random_state: int = 0):
+        """How far the track ``run`` filtered is from truth positions (``DeviceBatch.track_errors`` and
+        ``track_estimators.batch.error_statistics``; the reference's ``performance_metrics`` compares degrees row by row).
+        ``truth``: (Nmax+1, 2) lon / lat at the track's own rows, NaN where there is none; None takes the ship track's own
+        observations at the rows whose update used them (``track_estimators.batch.observation_rows``).  ``course``: None or
+        (Nmax+1,) degrees (``track_estimators.batch.truth_course``).  ``n_samples == 0``: a dict of the smoothed track's
+        values, every output of ``track_errors`` with ``cov="sm"``, per-row and cumulative ones included, scalars and
+        (Nmax+1,) arrays.  Otherwise the outputs of ``error_statistics`` for that many tracks drawn from the joint smoothing
+        posterior (``status`` apart), ``rmse`` as (n_samples,).  The track is packed as ``run`` packed it, as for
+        ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("track_error() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("track_error() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        if truth is None:
+            truth = _batch.observation_rows(hb)
+        else:
+            truth = np.asarray(truth, dtype=np.float64)
+            if truth.shape != (hb.Nmax + 1, 2):
+                raise ValueError(f"truth must be None or have shape ({hb.Nmax + 1}, 2), got {truth.shape}")
+            truth = np.ascontiguousarray(truth[:, :, None])
+        if course is not None:
+            course = np.asarray(course, dtype=np.float64)
+            if course.shape != (hb.Nmax + 1,):
+                raise ValueError(f"course must be None or have shape ({hb.Nmax + 1},), got {course.shape}")
+            course = np.ascontiguousarray(course[:, None])
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            got = db.track_errors(db.sm_mean, truth, course=course, cov="sm", coverage=coverage, model=model, rows=True,
+                                  cumulative=True)
+            return {k: v[0, ..., 0].cpu().numpy() for k, v in got.items()}
+        out = _batch.error_statistics(hb, truth, n_samples, seed=int(random_state), chunk=n_samples, course=course, model=model,
+                                      within_km=within_km, quantiles=quantiles)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return {k: v[..., 0] for k, v in out.items() if k != "status"}
+
     def line_approach(self, lines, nsamples: int = 0, within_km=None, model: str = "sphere", random_state: int = 0):
         """The track ``run`` filtered against polylines -- coasts, cables, routes, gates -- (``DeviceBatch.line_metrics``
         and ``track_estimators.batch.line_statistics``; no counterpart in the reference).  ``lines``: a list of (n, 2) lon /
