@@ -36,6 +36,9 @@
  *   ste_track_errors_f64     error of such tracks against truth positions at the tracks' own rows, in km, split along and across
  *                            the true course and scored against the track's covariance (performance_metrics.py: rmse,
  *                            cum_abs_diff and abs_diff compare in degrees, one ship at a time, on downloaded arrays)
+ *   ste_raster_metrics_f64   the values of a gridded field (land mask, depth, density) along such tracks: time with and without
+ *                            data, the time-weighted sum, extremes and when, and excursions past a threshold, in exact integer
+ *                            ticks (no counterpart in the reference: a download and a host loop)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -77,7 +80,8 @@ extern "C" {
                            (ste_line_metrics_f64).  Unnumbered addition: pairs of tracks on the device as curves
                            (ste_route_metrics_f64).  Unnumbered addition: speed made good, speed bands and stops of tracks on
                            the device (ste_speed_metrics_f64).  Unnumbered addition: errors of tracks on the device against
-                           truth positions (ste_track_errors_f64).
+                           truth positions (ste_track_errors_f64).  Unnumbered addition: the values of a gridded field along
+                           tracks on the device (ste_raster_metrics_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1086,6 +1090,84 @@ typedef struct ste_errors_f64 {
 } ste_errors_f64;            /* 208 bytes */
 
 int ste_track_errors_f64(const ste_ukf_batch_f64* b, const ste_errors_f64* er, void* stream);
+
+/*
+ * RASTERS: tracks that stay on the device against a GRIDDED FIELD (an unnumbered addition, like ste_grid_f64): a land mask,
+ * bathymetry, an ice concentration, a climatology, or the ship-hours map that ste_grid_metrics_f64 itself made of a fleet.
+ * ste_grid_metrics_f64 walks a track's pieces through the cells and ADDS to every cell; this call walks the same pieces and
+ * READS every cell.  `states` is that of ste_path_f64.
+ *   - Raster.  The grid is that of ste_grid_f64 (GRIDS: Grid.), member for member: nx, ny, lon0, lat0, dlon, dlat, lon_ref,
+ *     STE_GRID_PERIODIC_LON in `flags` with the same conditions, at most STE_GRID_MAX_CELLS cells.  `values` is a DEVICE array
+ *     double [ny][nx], one value per cell, constant over the cell, cell (ix, iy) at [iy * nx + ix].  NaN means NO DATA; +-inf
+ *     are values.
+ *   - Track.  Everything about the track is the grid call's, word for word (GRIDS: Unwrapping., Pieces., Runs.): unwrapping
+ *     about lon_ref, SOUND and BROKEN steps, dtq = rint(dt_k * 2^20), the split of a sound step at the grid lines strictly
+ *     between its ends (x-lines and y-lines merged by u, ties to x, tq = max(rint(u * dtq), the previous line's tick)), the
+ *     clipping by clamped line indices, and the dropped pieces of 0 ticks.
+ *   - Runs.  A RUN is the grid's: a maximal stretch of consecutive non-empty pieces in one cell (or outside), across steps and
+ *     across broken steps.  It has its cell, its ticks q, its START -- the ticks of the track's sound steps before its first
+ *     piece: the tick clock, which broken steps do not advance -- and its value v = values[cell].  A run outside has no value.
+ *     A run is VALID when it is on the grid and v is not NaN.
+ *   - total, outside, nbroken: as in ste_grid_metrics_f64, the same bits.  valid: the ticks of the valid runs.  nodata: the
+ *     ticks of the runs on the grid whose value is NaN.  EXACTLY: valid + nodata + outside = total.
+ *   - wsum = the sum over the valid runs, in track order, of (double)q * v, from 0.0: one multiplication and one addition per
+ *     run, not contracted.  The mean of the field along the track is wsum / valid.
+ *   - vmin, vmax: the least and the greatest value over the valid runs; tmin, tmax: the start of the FIRST run that attains
+ *     it.  From vmin = vmax = NaN, tmin = tmax = -1, in track order: if (!(vmin <= v)) { vmin = v; tmin = start; } and
+ *     if (!(vmax >= v)) { vmax = v; tmax = start; }.  A track without a valid run gives NaN and -1.
+ *   - Threshold.  A valid run is a HIT when v >= threshold, or v <= threshold with STE_RASTER_BELOW.  With
+ *     STE_RASTER_NO_THRESHOLD nothing is a hit, threshold and min_ticks are not looked at and the hit outputs must be NULL.  An
+ *     EXCURSION is a maximal stretch of consecutive runs that are all hits: a run that is no hit (a miss, no data, outside)
+ *     ends it, a broken step does not.  hit_ticks: the ticks of all hits.  hit_first: the start of the first hit, -1 = never.
+ *     nhit: the number of excursions.  nhit_long: those of at least min_ticks ticks.  hit_longest: the ticks of the longest
+ *     excursion, 0 without one.
+ *   - row_value[s][k][t], k <= nsteps[t]: the value of the cell that row k itself lies in, (floor((x_k - lon0) / dlon),
+ *     floor((lat_k - lat0) / dlat)), the column taken modulo nx (floored) when periodic; NaN where the row is off the grid or
+ *     its lon or lat is not finite.  Whether the steps about the row are sound does not matter.  Rows past nsteps[t] are not
+ *     written.
+ *   - A track with nsteps == 0 gives zeros, NaN and -1 as above, and its row 0 in row_value.
+ *   - Every per-track output is [S][track_stride] like outside / total of ste_grid_f64, and may be NULL; at least one output is
+ *     required.  The call reads the batch exactly as ste_grid_metrics_f64 does (B, Nmax, track_stride, nsteps, dt; windows)
+ *     and writes nothing of it.  Every value depends on its own track's rows and the raster alone, and every sum takes its
+ *     terms in track order: windows, sample slices and the outputs asked for cannot move a bit.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: every refusal of ste_grid_metrics_f64 (b or r
+ *     NULL; states NULL; nstates < 1 or > 65535; nx or ny < 1 or nx * ny > STE_GRID_MAX_CELLS; a non-finite lon0, lat0 or
+ *     lon_ref; dlon or dlat not finite or < 1e-6; the conditions of STE_GRID_PERIODIC_LON and of a grid without it; b->dt
+ *     NULL; B <= 0, Nmax < 0, or track_stride non-zero and below B); values NULL; unknown flag bits; a NaN threshold without
+ *     STE_RASTER_NO_THRESHOLD; min_ticks < 0; a hit output together with STE_RASTER_NO_THRESHOLD; every output NULL.
+ */
+#define STE_RASTER_BELOW 0x2u         /* a hit is v <= threshold (default: v >= threshold) */
+#define STE_RASTER_NO_THRESHOLD 0x4u  /* no threshold: the hit outputs must be NULL */
+typedef struct ste_raster_f64 {
+    int32_t nstates;       /* S >= 1 tracks per ship in `states` (<= 65535) */
+    uint32_t flags;        /* STE_GRID_PERIODIC_LON | STE_RASTER_* ; unknown bits refused */
+    const double* states;  /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64 / ste_grid_f64 */
+    int32_t nx, ny;        /* columns (lon) and rows (lat), >= 1, nx * ny <= STE_GRID_MAX_CELLS */
+    double lon0, lat0;     /* HOST: west and south edge of cell (0, 0), degrees */
+    double dlon, dlat;     /* HOST: cell size, finite, >= 1e-6 */
+    double lon_ref;        /* HOST: meridian the longitudes are unwrapped about */
+    const double* values;  /* DEVICE [ny][nx]: the field, a value per cell; NaN = no data */
+    double threshold;      /* HOST: not NaN, unless STE_RASTER_NO_THRESHOLD */
+    int64_t min_ticks;     /* HOST: >= 0; an excursion of at least this many ticks counts in nhit_long */
+    int64_t* total;        /* DEVICE [S][track_stride] out or NULL: ticks of all sound steps */
+    int64_t* outside;      /* DEVICE [S][track_stride] out or NULL: ticks spent off the grid */
+    int32_t* nbroken;      /* DEVICE [S][track_stride] out or NULL */
+    int64_t* valid;        /* DEVICE [S][track_stride] out or NULL: ticks of runs with a value */
+    int64_t* nodata;       /* DEVICE [S][track_stride] out or NULL: ticks of runs on the grid whose value is NaN */
+    double* wsum;          /* DEVICE [S][track_stride] out or NULL: sum of (double)q * v over the valid runs */
+    double* vmin;          /* DEVICE [S][track_stride] out or NULL: NaN without a valid run */
+    double* vmax;          /* DEVICE [S][track_stride] out or NULL */
+    int64_t* tmin;         /* DEVICE [S][track_stride] out or NULL: start of the first run at vmin, -1 without one */
+    int64_t* tmax;         /* DEVICE [S][track_stride] out or NULL */
+    int64_t* hit_ticks;    /* DEVICE [S][track_stride] out or NULL: ticks of all hits */
+    int64_t* hit_first;    /* DEVICE [S][track_stride] out or NULL: start of the first hit, -1 = never */
+    int32_t* nhit;         /* DEVICE [S][track_stride] out or NULL: excursions */
+    int32_t* nhit_long;    /* DEVICE [S][track_stride] out or NULL: excursions of at least min_ticks ticks */
+    int64_t* hit_longest;  /* DEVICE [S][track_stride] out or NULL: ticks of the longest excursion */
+    double* row_value;     /* DEVICE [S][Nmax+1][track_stride] out or NULL; rows past nsteps[t] untouched */
+} ste_raster_f64;          /* 216 bytes */
+
+int ste_raster_metrics_f64(const ste_ukf_batch_f64* b, const ste_raster_f64* r, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

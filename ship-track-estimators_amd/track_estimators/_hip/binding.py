@@ -191,6 +191,46 @@ class SteGridF64(C.Structure):
     ]
 
 
+STE_RASTER_BELOW = 0x2
+STE_RASTER_NO_THRESHOLD = 0x4
+
+
+class SteRasterF64(C.Structure):
+    """Mirror of ``struct ste_raster_f64`` (include/ste.h): tracks on the device against a gridded field."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("flags", C.c_uint32),
+        ("states", _dp),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("lon0", C.c_double),
+        ("lat0", C.c_double),
+        ("dlon", C.c_double),
+        ("dlat", C.c_double),
+        ("lon_ref", C.c_double),
+        ("values", _dp),
+        ("threshold", C.c_double),
+        ("min_ticks", C.c_int64),
+        ("total", _dp),
+        ("outside", _dp),
+        ("nbroken", _dp),
+        ("valid", _dp),
+        ("nodata", _dp),
+        ("wsum", _dp),
+        ("vmin", _dp),
+        ("vmax", _dp),
+        ("tmin", _dp),
+        ("tmax", _dp),
+        ("hit_ticks", _dp),
+        ("hit_first", _dp),
+        ("nhit", _dp),
+        ("nhit_long", _dp),
+        ("hit_longest", _dp),
+        ("row_value", _dp),
+    ]
+
+
 STE_ENCOUNTER_MAX_PAIRS = 1 << 26
 STE_ENCOUNTER_MAX_RADIUS_KM = 1000.0
 STE_ENC_BAD_INDEX = 0x1
@@ -544,6 +584,7 @@ SYMBOLS = {
     "ste_route_lds_cols": (C.c_int, []),
     "ste_speed_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSpeedF64), C.c_void_p]),
     "ste_track_errors_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteErrorsF64), C.c_void_p]),
+    "ste_raster_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRasterF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1014,6 +1014,63 @@ class DeviceBatch:
                 res["entries"] = ent
             return self._finish(st, keep, res)
 
+    # -- rasters --------------------------------------------------------------------------------------------------
+    def raster_metrics(self, states, raster, threshold=None, below: bool = False, min_hours: float = 0.0, rows: bool = False,
+                       stream=None):
+        """Tracks that are on the device against a gridded field (include/ste.h: ste_raster_metrics_f64; DESIGN.md,
+        "Rasters"): a land mask, a depth, a density, one value per cell of a ``TrackGrid``, NaN = no data.  ``states`` as in
+        ``path_metrics``; ``raster`` a ``TrackRaster`` (``track_raster`` makes one) on this batch's device.  Time is counted in
+        the integer ticks of ``grid_metrics`` (2^-20 h), over the same pieces and runs.  Returns a dict of device tensors,
+        (S, B) each: ``total``, ``outside`` int64 and ``nbroken`` int32 as in ``grid_metrics``; ``valid`` and ``nodata`` int64,
+        the ticks in cells with and without a value (valid + nodata + outside = total); ``wsum``, the sum of ticks x value over
+        the track's runs, and ``mean`` = wsum / valid, NaN where valid is 0; ``vmin``, ``vmax`` and ``tmin``, ``tmax`` int64, the
+        extremes and the tick at which the first run that attains them starts (NaN and -1 without a valid run).  With
+        ``threshold`` a run is a hit when its value is >= ``threshold`` (<= with ``below``), an excursion is a stretch of
+        consecutive hits, and the dict also has ``hit_ticks``, ``hit_first`` (-1 = never), ``hit_longest`` int64, ``nhit`` and
+        ``nhit_long`` int32, the excursions and those of at least ``min_hours`` (``min_ticks`` = rint(min_hours 2^20)).
+        Hours = ticks / 2^20: ``valid_hours``, ``tmin_hours``, ``tmax_hours``, ``hit_hours``, ``hit_first_hours``,
+        ``hit_longest_hours``, NaN where the tick is -1.  With ``rows`` also ``row_value`` (S, Nmax+1, B), the value of the cell
+        each row lies in, NaN off the grid and past ``nsteps[b]``.  Windows, in-place views and ``stream`` as in
+        ``grid_metrics``; every value depends on its own track's rows and the raster alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        states, S = self._metric_states(states)
+        if not isinstance(raster, TrackRaster):
+            raise ValueError("raster must be a TrackRaster (track_estimators.batch.track_raster makes one)")
+        if raster.values.device != self.device:
+            raise ValueError(f"the raster's values are on {raster.values.device}, this batch is on {self.device}")
+        flags, thr, min_ticks = _raster_threshold(threshold, below, min_hours)
+        grid = raster.grid
+        st = self._ordered_stream(stream)
+        with torch.cuda.stream(st):
+            keep = [raster.values]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
+            names = _RASTER_OUTPUTS + (_RASTER_HIT_OUTPUTS if threshold is not None else ())
+            ten = {k: torch.empty((S, width), dtype=getattr(torch, dt), device=self.device) for k, dt in names}
+            rv = torch.full((S, N + 1, width), float("nan"), dtype=torch.float64, device=self.device) if rows else None
+            r = binding.SteRasterF64()
+            r.nstates, r.states = S, states.data_ptr()
+            r.flags = flags | (binding.STE_GRID_PERIODIC_LON if grid.periodic else 0)
+            r.nx, r.ny, r.lon0, r.lat0, r.dlon, r.dlat, r.lon_ref = (grid.nx, grid.ny, grid.lon0, grid.lat0, grid.dlon, grid.dlat,
+                                                                     grid.lon_ref)
+            r.values, r.threshold, r.min_ticks = raster.values.data_ptr(), thr, min_ticks
+            for k, v in ten.items():
+                setattr(r, k, v.data_ptr() + v.element_size() * col)
+            r.row_value = None if rv is None else rv.data_ptr() + 8 * col
+            binding.check(self.lib.ste_raster_metrics_f64(C.byref(s), C.byref(r), self._stream(st)), "ste_raster_metrics_f64")
+            out = {k: v[:, col:col + B] for k, v in ten.items()}
+            tph = float(binding.STE_GRID_TICKS_PER_HOUR)
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
+            hours = {"valid": "valid_hours", "tmin": "tmin_hours", "tmax": "tmax_hours", "hit_ticks": "hit_hours",
+                     "hit_first": "hit_first_hours", "hit_longest": "hit_longest_hours"}
+            for k, name in hours.items():
+                if k in out:
+                    out[name] = torch.where(out[k] < 0, nan, out[k].to(torch.float64) / tph)
+            out["mean"] = torch.where(out["valid"] > 0, out["wsum"] / out["valid"].to(torch.float64), nan)
+            if rv is not None:
+                out["row_value"] = rv[..., col:col + B]
+            return self._finish(st, keep, out)
+
     # -- encounters -----------------------------------------------------------------------------------------------
     def encounter_metrics(self, states, pairs, radius_km, t0=None, model: str = "sphere", stream=None):
         """Pairs of tracks that are on the device against each other (include/ste.h: ste_encounter_metrics_f64; DESIGN.md,
@@ -2969,6 +3026,112 @@ def grid_statistics(hb_or_db, grid: TrackGrid, nsamples: int, seed: int = 0, chu
     out["total_ticks"] = np.concatenate([p[1] for p in per_track], axis=1)
     out["nbroken"] = np.concatenate([p[2] for p in per_track], axis=1)
     out["status"] = np.concatenate([p[3] for p in per_track])
+    return out
+
+
+_RASTER_OUTPUTS = (("total", "int64"), ("outside", "int64"), ("nbroken", "int32"), ("valid", "int64"), ("nodata", "int64"),
+                   ("wsum", "float64"), ("vmin", "float64"), ("vmax", "float64"), ("tmin", "int64"), ("tmax", "int64"))
+_RASTER_HIT_OUTPUTS = (("hit_ticks", "int64"), ("hit_first", "int64"), ("nhit", "int32"), ("nhit_long", "int32"),
+                       ("hit_longest", "int64"))
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackRaster:
+    """A gridded field as ``ste_raster_metrics_f64`` wants it (``track_raster`` makes one): ``grid``, a ``TrackGrid``, and
+    ``values``, a contiguous float64 device tensor (ny, nx), one value per cell, NaN = no data."""
+
+    grid: TrackGrid
+    values: object
+
+
+def track_raster(grid: TrackGrid, values, device="cuda:0") -> TrackRaster:
+    """A field on ``grid`` for ``DeviceBatch.raster_metrics``: ``values`` (ny, nx), an array or a tensor, one value per cell,
+    row iy at latitude lat0 + iy dlat upwards, NaN = no data.  A float64 contiguous tensor that already is on a GPU is used
+    where it lies -- ``grid_metrics(...)["hours"]`` goes back in without leaving the device --; anything else is converted to
+    float64 and copied to ``device``.  ``ValueError``: ``grid`` is no ``TrackGrid``; ``values`` is not (ny, nx); a dtype that
+    is neither real nor integer nor bool."""
+    import torch
+
+    if not isinstance(grid, TrackGrid):
+        raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
+    if isinstance(values, torch.Tensor):
+        ten = values
+        if ten.is_complex():
+            raise ValueError(f"a raster's values must be real numbers, got a tensor of {ten.dtype}")
+    else:
+        a = np.asarray(values)
+        if a.dtype.kind not in "fiub":
+            raise ValueError(f"a raster's values must be real numbers, got an array of dtype {a.dtype}")
+        ten = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+    if tuple(ten.shape) != (grid.ny, grid.nx):
+        raise ValueError(f"a raster's values must have shape (ny, nx) = ({grid.ny}, {grid.nx}), got {tuple(ten.shape)}")
+    if not (ten.is_cuda and ten.dtype == torch.float64 and ten.is_contiguous()):
+        ten = ten.to(device=ten.device if ten.is_cuda else device, dtype=torch.float64).contiguous()
+    return TrackRaster(grid=grid, values=ten)
+
+
+def _raster_threshold(threshold, below, min_hours):
+    """(flags, threshold, min_ticks) of ``ste_raster_f64`` for the arguments of ``raster_metrics``."""
+    min_hours = float(min_hours)
+    if not (min_hours >= 0.0 and np.isfinite(min_hours)):
+        raise ValueError(f"min_hours must be finite and >= 0, got {min_hours!r}")
+    if threshold is None:
+        return binding.STE_RASTER_NO_THRESHOLD, 0.0, 0
+    threshold = float(threshold)
+    if np.isnan(threshold):
+        raise ValueError("threshold must not be NaN (None: no threshold)")
+    return (binding.STE_RASTER_BELOW if below else 0, threshold,
+            int(np.rint(min_hours * float(binding.STE_GRID_TICKS_PER_HOUR))))
+
+
+def raster_statistics(hb_or_db, raster: TrackRaster, nsamples: int, seed: int = 0, chunk: int = 16, threshold=None,
+                      below: bool = False, min_hours: float = 0.0, quantiles=(0.05, 0.5, 0.95), device="cuda:0"):
+    """The values of a gridded field along the ships' tracks with the uncertainty of the smoothing posterior, per track:
+    ``nsamples`` posterior tracks are drawn (``DeviceBatch.sample_smoothed``), held against the raster
+    (``DeviceBatch.raster_metrics``) and discarded, ``chunk`` samples at a time, with the generator discipline of
+    ``grid_statistics``: one draw buffer refilled from one generator, so the draws depend on ``(seed, chunk)`` and with
+    ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  What stays is (nsamples, B) columns: memory
+    does not otherwise grow with ``nsamples``.  Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother
+    first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``threshold``, ``below`` and
+    ``min_hours`` as in ``raster_metrics``.
+
+    Returns a dict of NumPy arrays in the batch's slot order: every output of ``raster_metrics`` for the smoothed track
+    ``sm_mean`` under ``*_smoothed`` names, (B,) each; ``mean`` (nsamples, B) and ``mean_quantiles`` (len(quantiles), B) over
+    the samples that have a mean, NaN where none has; with ``threshold`` ``hit_hours`` (nsamples, B), ``hit_hours_mean`` (B,),
+    ``hit_hours_quantiles``, ``p_hit``, the share of samples with an excursion, and ``p_hit_long``, with one of at least
+    ``min_hours``; ``nbroken`` (nsamples, B) int32; and ``status`` (B,), the sampler's STE_STATUS_* bits."""
+    import warnings
+
+    if not isinstance(raster, TrackRaster):
+        raise ValueError("raster must be a TrackRaster (track_estimators.batch.track_raster makes one)")
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "raster_statistics")
+    torch = db.torch
+    B = db.ntracks
+    kw = dict(threshold=threshold, below=below, min_hours=min_hours)
+    smoothed = db.raster_metrics(db.sm_mean, raster, **kw)
+    names = ("mean", "nbroken") + (("hit_hours", "nhit", "nhit_long") if threshold is not None else ())
+    kept = {k: torch.empty((nsamples, B), dtype=smoothed[k].dtype, device=db.device) for k in names}
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for i, n, samples in chunks:
+        m = db.raster_metrics(samples, raster, **kw)
+        for k, ten in kept.items():
+            ten[i:i + n] = m[k]
+    status = chunks.status
+    out = {k + "_smoothed": v[0].cpu().numpy() for k, v in smoothed.items()}
+    q = np.asarray(quantiles, dtype=np.float64)
+    host = {k: v.cpu().numpy() for k, v in kept.items()}
+    out["mean"] = host["mean"]
+    with warnings.catch_warnings():  # a track no sample takes onto the data: all-NaN column, NaN quantiles
+        warnings.simplefilter("ignore", RuntimeWarning)
+        out["mean_quantiles"] = np.nanquantile(host["mean"], q, axis=0)
+    if threshold is not None:
+        out["hit_hours"] = host["hit_hours"]
+        out["hit_hours_mean"] = host["hit_hours"].mean(axis=0)
+        out["hit_hours_quantiles"] = np.quantile(host["hit_hours"], q, axis=0)
+        out["p_hit"] = (host["nhit"] > 0).mean(axis=0)
+        out["p_hit_long"] = (host["nhit_long"] > 0).mean(axis=0)
+    out["nbroken"] = host["nbroken"]
+    out["status"] = status.cpu().numpy()
     return out
 
 

@@ -372,6 +372,45 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return out["hours_mean"]
 
+    def raster_along_track(self, raster, threshold=None, below: bool = False, min_hours: float = 0.0, n_samples: int = 0,
+                           random_state: int = 0):
+        """The values of a gridded field -- a land mask, a depth, a density -- along the track ``run`` filtered
+        (``DeviceBatch.raster_metrics`` and ``track_estimators.batch.raster_statistics``; no counterpart in the reference).
+        ``raster``: a ``track_estimators.batch.TrackRaster`` (``track_estimators.batch.track_raster`` makes one);
+        ``threshold``, ``below`` and ``min_hours`` as in ``raster_metrics``.  Returns a dict of the smoothed track's values,
+        every output of ``raster_metrics`` as a scalar, and ``row_value`` (N+1,), the field at every row.  With ``n_samples``
+        also ``posterior``, a dict of what ``raster_statistics`` gives over that many tracks drawn from the joint smoothing
+        posterior, those of ``sample_smoothed(n_samples, random_state)``: ``mean`` (n_samples,), ``mean_quantiles``,
+        ``nbroken`` and, with ``threshold``, ``hit_hours``, ``hit_hours_mean``, ``hit_hours_quantiles``, ``p_hit``,
+        ``p_hit_long``.  The track is packed as ``run``
+        packed it, as for ``time_on_grid``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("raster_along_track() measures the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("raster_along_track() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        if not isinstance(raster, _batch.TrackRaster):
+            raise ValueError("raster must be a TrackRaster (track_estimators.batch.track_raster makes one)")
+        kw = dict(threshold=threshold, below=below, min_hours=min_hours)
+        db = _batch.DeviceBatch(hb)
+        db.run()
+        if int(db.status_host()[0]) & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        got = db.raster_metrics(db.sm_mean, raster, rows=True, **kw)
+        res = {k: v[0, ..., 0].cpu().numpy() for k, v in got.items()}
+        if n_samples == 0:
+            return res
+        out = _batch.raster_statistics(db, raster, n_samples, seed=int(random_state), chunk=n_samples, **kw)
+        self._status_sampler = int(out["status"][0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        res["posterior"] = {k: v[..., 0] for k, v in out.items() if not k.endswith("_smoothed") and k != "status"}
+        return res
+
     def position_at(self, times, n_samples: int = 0, random_state: int = 0):
         """Where the track ``run`` filtered was at ``times``, hours from its first row
         (``track_estimators.batch.position_statistics``; no counterpart in the reference, whose callers search and interpolate
