@@ -16,6 +16,8 @@
  *   ste_sigma_points_f64     UnscentedKalmanFilter.compute_sigma_points  unscented.py:76-107
  *   ste_track_prep_f64       ShipTrack.calculate_sog / _cog / _sog_rate / _cog_rate / get_measurements
  *                            src/track_estimators/ship_track.py:197-338 (distance / heading: utils.py:9-147)
+ *   ste_track_prep_smooth_f64  the same with SOG / COG smoothed first: utils.smooth (utils.py:150-172, cli/main_cli.py:99-104)
+ *                            or scipy's savgol_filter (examples/example_ukf_rts_smoother_savgol.py), as one table-driven filter
  *   ste_path_metrics_f64     distance sailed and line-crossing times of tracks that stay on the device (smoothed, filtered or
  *                            sampled): per-leg utils.haversine_formula / geographiclib_distance (utils.py:9-113), summed
  *   ste_region_metrics_f64   time inside a polygon, first entry, entries, distance inside and per-row flags of such tracks (no
@@ -81,7 +83,8 @@ extern "C" {
                            (ste_route_metrics_f64).  Unnumbered addition: speed made good, speed bands and stops of tracks on
                            the device (ste_speed_metrics_f64).  Unnumbered addition: errors of tracks on the device against
                            truth positions (ste_track_errors_f64).  Unnumbered addition: the values of a gridded field along
-                           tracks on the device (ste_raster_metrics_f64).
+                           tracks on the device (ste_raster_metrics_f64).  Unnumbered addition: observation preparation with
+                           SOG / COG smoothed first (ste_track_prep_smooth_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1457,6 +1460,45 @@ typedef struct ste_prep_batch_f64 {
 } ste_prep_batch_f64;
 
 int ste_track_prep_f64(const ste_prep_batch_f64* b, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Pre-smoothing: the same preparation with SOG and / or COG smoothed BEFORE the rates and z are formed,
+ * the device counterpart of utils.smooth in the reference's CLI (cli/main_cli.py:99-104: "smooth": k of input.json) and of
+ * scipy.signal.savgol_filter in examples/example_ukf_rts_smoother_savgol.py.  Both are linear filters, and the device has
+ * one form that covers them; the tables are made on the host (track_estimators.batch.box_filter, savgol_filter_table).
+ *   interior    out[i] = sum_k taps[k] y[i - left + k], k < window; samples outside [0, nobs) count as 0
+ *   edges       with nedge = h > 0, row i < h is sum_k edge[i][k] y[k] over the first `window` samples and row
+ *               nobs - 1 - r (r < h) its mirror image over the last: sum_k edge[r][window - 1 - k] y[nobs - window + k].
+ *               h <= window / 2, so with nobs >= window the two edges never meet.
+ *   circular    (for courses) the filter runs on differences from the row's own value, wrapped into [-180, 180]:
+ *               d_k = delta - 360 rint(delta / 360) with delta = y[j] - y[i] (d_k = 0 for a sample outside [0, nobs)),
+ *               out[i] = (y[i] + sum_k c_k d_k) mod 360 in [0, 360).  With circular = 0 courses are averaged as plain
+ *               numbers, as the reference does (359 and 1 give 180).
+ * Every tap is multiplied and added in order of k without contraction, none is skipped for a zero weight: a non-finite raw
+ * value (gap = 0) makes exactly the outputs whose window holds it non-finite.
+ *
+ * ste_track_prep_smooth_f64 computes the raw series as ste_track_prep_f64 does (the same kernel) into raw_sog / raw_cog
+ * [Tmax][B] (required workspace that doubles as output; must not overlap each other, any output or any input of the batch), filters each
+ * over [0, nobs[t]) into b->sog / b->cog, and builds sog_rate, cog_rate and z from the FILTERED series by the rules above
+ * (backward difference over gap[i-1], 0 for i = 0; rows >= nobs[t] are 0).  A NULL descriptor leaves that series unsmoothed:
+ * its values and rates are then those of ste_track_prep_f64 bit for bit.  b->status is reset as there.
+ * STE_EINVAL before any launch: NULL workspace, NULL b->sog or b->cog, aliasing, window outside 2..128, left outside 0..window-1, nedge outside
+ * 0..window/2, NULL taps, NULL edge with nedge > 0, circular not 0 or 1, and whatever ste_track_prep_f64 refuses.
+ * With nedge > 0 every track needs nobs >= window.  THE CALLER GUARANTEES THIS: nobs is device memory and the call stays
+ * asynchronous, so it is not checked here (track_estimators.batch.prepare_observations checks it on the host and raises).
+ * A shorter track is safe for memory -- no read or write leaves [0, nobs) of its columns -- but its values are unspecified.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct ste_fir_f64 {
+    int32_t window;      /* w taps, 2..128 */
+    int32_t left;        /* tap k of interior row i reads y[i - left + k]; 0..w-1 */
+    int32_t nedge;       /* h edge rows at either end, 0..w/2; 0 = zero padding */
+    int32_t circular;    /* 1: filter wrapped differences (courses in degrees); 0: plain numbers */
+    const double* taps;  /* DEVICE [w] */
+    const double* edge;  /* DEVICE [h][w], may be NULL when h = 0 */
+} ste_fir_f64;
+
+int ste_track_prep_smooth_f64(const ste_prep_batch_f64* b, const ste_fir_f64* fir_sog, const ste_fir_f64* fir_cog,
+                              double* raw_sog, double* raw_cog, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Stream partitioning for pipelined batches.  At the batch sizes of BASELINE configs[1..2] the forward kernel is a few

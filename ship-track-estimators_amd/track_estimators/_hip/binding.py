@@ -548,6 +548,19 @@ class StePrepBatchF64(C.Structure):
     ]
 
 
+class SteFirF64(C.Structure):
+    """Mirror of ``struct ste_fir_f64`` (include/ste.h)."""
+
+    _fields_ = [
+        ("window", C.c_int32),
+        ("left", C.c_int32),
+        ("nedge", C.c_int32),
+        ("circular", C.c_int32),
+        ("taps", _dp),
+        ("edge", _dp),
+    ]
+
+
 STE_GP_INVERSE_AUTO, STE_GP_INVERSE_ROWS, STE_GP_INVERSE_COLS = 0, 1, 2
 STE_GP_KERNEL_RBF, STE_GP_KERNEL_MATERN12, STE_GP_KERNEL_MATERN32, STE_GP_KERNEL_MATERN52 = 0, 1, 2, 3
 STE_PREP_SPHERE = 0
@@ -601,6 +614,8 @@ SYMBOLS = {
     "ste_sigma_points_f64": (C.c_int, [C.c_int64, _dp, _dp, C.c_double, _dp, C.c_void_p]),
     "ste_sigma_points_generic_f64": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, C.c_double, _dp, C.c_void_p]),
     "ste_track_prep_f64": (C.c_int, [C.POINTER(StePrepBatchF64), C.c_void_p]),
+    "ste_track_prep_smooth_f64": (C.c_int, [C.POINTER(StePrepBatchF64), C.POINTER(SteFirF64), C.POINTER(SteFirF64), _dp, _dp,
+                                            C.c_void_p]),
     "ste_gp_last_error": (C.c_char_p, []),
     "ste_gp_rbf_kmatrix_f64": (C.c_int, [C.POINTER(SteGpBatchF64), C.c_void_p]),
     "ste_gp_potrf_f64": (C.c_int, [C.POINTER(SteGpBatchF64), C.c_void_p]),

@@ -2402,7 +2402,94 @@ def _register_atexit():
         _atexit_registered = True
 
 
-def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: str = "wgs84", device="cuda:0"):
+FIR_MAX_WINDOW, SAVGOL_MAX_ORDER = 128, 8  # include/ste.h: ste_fir_f64.window; the order is a limit of the host tables
+
+
+@dataclasses.dataclass(frozen=True)
+class FirFilter:
+    """A linear smoother in the form of ``struct ste_fir_f64`` (include/ste.h): interior row i is
+    ``sum_k taps[k] y[i - left + k]`` with zeros outside the series; with ``nedge = h > 0`` row i < h is
+    ``sum_k edge[i][k] y[k]`` over the first ``window`` samples and row n - 1 - r its mirror image over the last."""
+
+    window: int
+    left: int
+    nedge: int
+    taps: np.ndarray  # (window,)
+    edge: np.ndarray  # (nedge, window)
+
+
+def _check_window(w, who):
+    if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 2 <= w <= FIR_MAX_WINDOW:
+        raise ValueError(f"{who}: the window must be an integer in 2..{FIR_MAX_WINDOW}, got {w!r}")
+    return int(w)
+
+
+def box_filter(w: int) -> FirFilter:
+    """The centred moving average of the reference's ``utils.smooth``: ``np.convolve(y, ones(w) / w, "same")``, zero padded at
+    both ends (utils.py:150-172).  Output i of "same" is element i + (w - 1) // 2 of the full convolution, the sum over
+    y[i - w // 2 .. i + (w - 1) // 2]: ``left = w // 2``, for even w too."""
+    w = _check_window(w, "box_filter")
+    return FirFilter(window=w, left=w // 2, nedge=0, taps=np.full(w, 1.0 / w), edge=np.zeros((0, w)))
+
+
+def _polyfit_weights(w: int, p: int, x0):
+    """Weights c with ``sum_k c[k] y[k]`` = the least-squares polynomial of degree p through (k, y[k]), k < w, evaluated at
+    x0 -- in exact rational arithmetic by the normal equations, each weight rounded once to double."""
+    from fractions import Fraction
+
+    x0 = Fraction(x0)
+    G = [[Fraction(sum(k ** (a + b) for k in range(w))) for b in range(p + 1)] + [x0 ** a] for a in range(p + 1)]
+    for c in range(p + 1):  # Gauss-Jordan on [A^T A | x0^a]; A^T A is positive definite for p < w, so no pivot is zero
+        piv = G[c][c]
+        G[c] = [v / piv for v in G[c]]
+        for r in range(p + 1):
+            if r != c and G[r][c] != 0:
+                f = G[r][c]
+                G[r] = [vr - f * vc for vr, vc in zip(G[r], G[c])]
+    u = [G[a][p + 1] for a in range(p + 1)]
+    return np.array([float(sum(u[a] * Fraction(k) ** a for a in range(p + 1))) for k in range(w)])
+
+
+def savgol_filter_table(w: int, p: int) -> FirFilter:
+    """``scipy.signal.savgol_filter(y, w, p)`` (``deriv=0``, ``mode="interp"``) as a table.  Edge rows (h = w // 2 at either
+    end): the polynomial of degree p fitted to the first (last) w samples, evaluated at the row.  Interior rows: the fit over
+    the window evaluated at its centre node for odd w (``left = h``); for even w scipy's output is the fit over
+    y[i - h + 1 .. i + h] evaluated at h - 1/2 in window coordinates, half a sample before row i (``left = h - 1``), and this
+    reproduces it.  The weights are exact rationals rounded once, so the table depends on no LAPACK."""
+    from fractions import Fraction
+
+    w = _check_window(w, "savgol_filter_table")
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= p <= SAVGOL_MAX_ORDER or p >= w:
+        raise ValueError(f"savgol_filter_table: the order must be an integer in 0..{SAVGOL_MAX_ORDER} and below the window, got {p!r}")
+    p, h = int(p), w // 2
+    centre, left = (Fraction(h), h) if w % 2 else (Fraction(2 * h - 1, 2), h - 1)
+    return FirFilter(window=w, left=left, nedge=h, taps=_polyfit_weights(w, p, centre),
+                     edge=np.stack([_polyfit_weights(w, p, i) for i in range(h)]))
+
+
+def _fir_struct(f: FirFilter, circular: bool, dev, keep: list):
+    """``ste_fir_f64`` of a FirFilter with its tables uploaded to ``dev``; ``keep`` holds the tensors alive."""
+    import torch
+
+    taps = np.ascontiguousarray(f.taps, dtype=np.float64)
+    edge = np.ascontiguousarray(f.edge, dtype=np.float64).reshape(-1, f.window)
+    if taps.shape != (f.window,) or edge.shape[0] != f.nedge:
+        raise ValueError("filter: taps must have `window` entries and edge `nedge` rows of `window`")
+    s = binding.SteFirF64()
+    s.window, s.left, s.nedge, s.circular = int(f.window), int(f.left), int(f.nedge), int(bool(circular))
+    t_taps = torch.from_numpy(taps).to(dev)
+    keep.append(t_taps)
+    s.taps = t_taps.data_ptr()
+    if f.nedge > 0:
+        t_edge = torch.from_numpy(edge).to(dev)
+        keep.append(t_edge)
+        s.edge = t_edge.data_ptr()
+    return s
+
+
+def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: str = "wgs84", device="cuda:0", *,
+                         smooth_sog: Optional[FirFilter] = None, smooth_cog: Optional[FirFilter] = None,
+                         cog_circular: bool = False):
     """Speed / course over ground and their rates for many tracks in one launch (``ste_track_prep_f64``).
 
     ``lons[b]``, ``lats[b]`` (length T_b, degrees) and ``gaps[b]`` (length T_b - 1, hours) are what ``ShipTrack.read_csv``
@@ -2410,9 +2497,18 @@ def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: 
     (haversine_formula / heading).  Returns one dict per track with ``sog, cog, sog_rate, cog_rate`` (length T_b),
     ``z`` (4, T_b) = the result of ``get_measurements(include_sog=True, include_cog=True)`` (ship_track.py:197-338) and
     ``status`` (always 0 since 0.3.1: the WGS84 model is Karney's solver, which converges on every leg).
+
+    ``smooth_sog`` / ``smooth_cog`` (a ``FirFilter``: ``box_filter(k)`` is the reference CLI's ``"smooth": k``,
+    ``savgol_filter_table(w, p)`` scipy's ``savgol_filter``) smooth that series on the device BEFORE the rates and ``z`` are
+    formed (``ste_track_prep_smooth_f64``); the dicts then also hold the unsmoothed ``raw_sog`` and ``raw_cog``.
+    ``cog_circular`` makes the course filter work on differences wrapped into [-180, 180], so that a course through north is
+    not averaged through south; off, courses are plain numbers as in the reference.  A track shorter than a filter's window
+    raises ``ValueError``.
     """
     import torch
 
+    if cog_circular and smooth_cog is None:
+        raise ValueError("cog_circular needs smooth_cog")
     lib = binding.require_gpu()
     models = {"sphere": binding.STE_PREP_SPHERE, "wgs84": binding.STE_PREP_WGS84}
     if model not in models:
@@ -2426,6 +2522,10 @@ def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: 
             raise ValueError(f"track {b}: need len(lat) == len(lon) and len(gaps) == len(lon) - 1")
         if nobs[b] < 2:
             raise IndexError(f"track {b} has fewer than 2 observations (ship_track.py:220 indexes sog[-1])")
+    for name, f in (("smooth_sog", smooth_sog), ("smooth_cog", smooth_cog)):
+        if f is not None and nobs.min() < f.window:
+            b = int(np.argmax(nobs < f.window))
+            raise ValueError(f"track {b} has {nobs[b]} observations, fewer than the window of {name} ({f.window})")
     T = int(nobs.max())
     lon = np.zeros((T, B))
     lat = np.zeros((T, B))
@@ -2447,7 +2547,18 @@ def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: 
     st = torch.zeros((B,), dtype=torch.int32, device=dev)
     s.status = st.data_ptr()
     stream = torch.cuda.current_stream(dev)
-    binding.check(lib.ste_track_prep_f64(C.byref(s), C.c_void_p(stream.cuda_stream)), "ste_track_prep_f64")
+    raw = None
+    if smooth_sog is None and smooth_cog is None:
+        binding.check(lib.ste_track_prep_f64(C.byref(s), C.c_void_p(stream.cuda_stream)), "ste_track_prep_f64")
+    else:
+        keep = []
+        firs = [None if f is None else C.byref(_fir_struct(f, circ, dev, keep))
+                for f, circ in ((smooth_sog, False), (smooth_cog, cog_circular))]
+        raw = torch.empty((2, T, B), dtype=torch.float64, device=dev)
+        binding.check(lib.ste_track_prep_smooth_f64(C.byref(s), firs[0], firs[1], raw[0].data_ptr(), raw[1].data_ptr(),
+                                                    C.c_void_p(stream.cuda_stream)), "ste_track_prep_smooth_f64")
+        raw = raw.cpu().numpy()  # synchronises: the tables in `keep` have been read
+        del keep
     h = outs.cpu().numpy()
     zh = z.cpu().numpy()
     sth = st.cpu().numpy()
@@ -2461,14 +2572,19 @@ def prepare_observations(lons: Sequence, lats: Sequence, gaps: Sequence, model: 
         n = nobs[b]
         res.append({"sog": h[0, :n, b].copy(), "cog": h[1, :n, b].copy(), "sog_rate": h[2, :n, b].copy(),
                     "cog_rate": h[3, :n, b].copy(), "z": np.ascontiguousarray(zh[:n, :, b].T), "status": int(sth[b])})
+        if raw is not None:
+            res[-1].update(raw_sog=raw[0, :n, b].copy(), raw_cog=raw[1, :n, b].copy())
     return res
 
 
-def prepare_ship_tracks(ship_tracks: Sequence, device="cuda:0"):
+def prepare_ship_tracks(ship_tracks: Sequence, device="cuda:0", *, smooth_sog: Optional[FirFilter] = None,
+                        smooth_cog: Optional[FirFilter] = None, cog_circular: bool = False):
     """Fill ``sog, cog, sog_rate, cog_rate, z`` of every ShipTrack (already ``read_csv``'d) in one launch -- what the
     reference does per ship with calculate_cog / calculate_sog / calculate_*_rate / get_measurements(True, True)
     (examples/example_ukf_rts_smoother_batch.py:33-40).  The distance / heading pair configured on each ShipTrack
-    selects the model; anything but the two pairs the reference ships raises."""
+    selects the model; anything but the two pairs the reference ships raises.  ``smooth_sog``, ``smooth_cog`` and
+    ``cog_circular`` are those of ``prepare_observations``: the fields then hold the smoothed series and what is built on
+    them, as after the reference CLI's ``"smooth"`` step (cli/main_cli.py:99-109)."""
     from . import utils
 
     pairs = {(utils.geographiclib_distance, utils.geographiclib_heading): "wgs84",
@@ -2482,7 +2598,8 @@ def prepare_ship_tracks(ship_tracks: Sequence, device="cuda:0"):
         groups.setdefault(key, []).append(i)
     for model, idx in groups.items():
         res = prepare_observations([ship_tracks[i].lon for i in idx], [ship_tracks[i].lat for i in idx],
-                                   [ship_tracks[i].dts for i in idx], model=model, device=device)
+                                   [ship_tracks[i].dts for i in idx], model=model, device=device, smooth_sog=smooth_sog,
+                                   smooth_cog=smooth_cog, cog_circular=cog_circular)
         for i, r in zip(idx, res):
             st = ship_tracks[i]
             st.sog, st.cog, st.sog_rate, st.cog_rate, st.z = r["sog"], r["cog"], r["sog_rate"], r["cog_rate"], r["z"]

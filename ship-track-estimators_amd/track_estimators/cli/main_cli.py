@@ -16,6 +16,10 @@ Opt-in keys of ``input.json`` beyond the reference's (absent = the reference's b
   ``"drop_duplicate_times": true``  rows whose (hour-resolution) timestamp repeats the row before are dropped on reading
                           (``ShipTrack.read_csv(drop_duplicate_times=True)``): five of the seven data/modern_ships ids carry
                           such rows and end non-finite without it, in the reference (LinAlgError) as here (status NaN)
+  ``"device_prep": true``  in the batched run (several ship ids, or ``robust``) SOG, COG, their rates and the measurements
+                          of all ships come from one launch on the GPU (``batch.prepare_ship_tracks``) instead of a host loop
+                          per ship; ``"smooth": k`` is then a box filter of k on the device (``batch.box_filter``), under the
+                          reference's rule that -1, 0, 1 and a missing key mean none.  The single-ship run is as without it
 """
 from __future__ import annotations
 
@@ -100,14 +104,27 @@ def get_optional_settings(settings: dict) -> Tuple[bool, float, str, bool]:
     return robust, chi_alpha, geodesy, dedup
 
 
-def _prepare_track(args, ship_id, smooth_control, geodesy="wgs84", dedup=False):
-    """ShipTrack -> measurements, rates and prior exactly as main_cli.py:89-109 does."""
+def get_device_prep(settings: dict) -> bool:
+    """The opt-in key ``device_prep`` (module docstring); absent = false."""
+    device_prep = settings.get("device_prep", False)
+    if not isinstance(device_prep, bool):
+        raise ValueError(f"'device_prep' must be true or false, got {device_prep!r}")
+    return device_prep
+
+
+def _read_track(args, ship_id, geodesy="wgs84", dedup=False):
     if geodesy == "sphere":
         ship_track = ShipTrack(calc_distance_func=haversine_formula, calc_heading_func=heading)
     else:
         ship_track = ShipTrack(calc_distance_func=geographiclib_distance, calc_heading_func=geographiclib_heading)
     ship_track.read_csv(args.track_file, ship_id=ship_id, id_col=args.id_col, lat_col=args.lat_id, lon_col=args.lon_id,
                         reverse=bool(args.reverse), drop_duplicate_times=dedup)
+    return ship_track
+
+
+def _prepare_track(args, ship_id, smooth_control, geodesy="wgs84", dedup=False):
+    """ShipTrack -> measurements, rates and prior exactly as main_cli.py:89-109 does."""
+    ship_track = _read_track(args, ship_id, geodesy, dedup)
     if smooth_control not in [-1, 0, 1, None]:
         logger.info(f"Smoothing SOG and COG by {smooth_control}.")
         ship_track.calculate_cog()
@@ -118,6 +135,17 @@ def _prepare_track(args, ship_id, smooth_control, geodesy="wgs84", dedup=False):
     ship_track.calculate_cog_rate()
     ship_track.calculate_sog_rate()
     return ship_track, z[:, 0].reshape(-1, 1).copy()
+
+
+def _prepare_tracks_on_device(batch, args, ship_ids, smooth_control, geodesy="wgs84", dedup=False):
+    """What ``_prepare_track`` does for every ship id, with one launch for all of them: [(ShipTrack, prior)]."""
+    tracks = [_read_track(args, sid, geodesy, dedup) for sid in ship_ids]
+    fir = None
+    if smooth_control not in [-1, 0, 1, None]:
+        logger.info(f"Smoothing SOG and COG by {smooth_control}.")
+        fir = batch.box_filter(smooth_control)
+    batch.prepare_ship_tracks(tracks, smooth_sog=fir, smooth_cog=fir)
+    return [(st, st.z[:, 0].reshape(-1, 1).copy()) for st in tracks]
 
 
 def _write_outputs(prefix, ship_id, ship_track, dt_array, predictions, estimate_vars, smoothed=None):
@@ -148,6 +176,7 @@ def track_estimator(argv=None):
     settings = load_input_json(args.input_file)
     dim, dt, nsteps, H, Q, R, P, smooth_control = get_input_settings(settings)
     robust, chi_alpha, geodesy, dedup = get_optional_settings(settings)
+    device_prep = get_device_prep(settings)
     substeps = nsteps if dt in [-1, 0, None] else 1  # a positive constant dt is ignored, like main_cli.py:114-120
 
     ship_ids = [s for s in str(args.ship_id).split(",") if s] if "," in str(args.ship_id) else [args.ship_id]
@@ -167,8 +196,11 @@ def track_estimator(argv=None):
         from .. import batch
 
         tracks, x0s, dts = [], [], []
-        for sid in ship_ids:
-            st, x0 = _prepare_track(args, sid, smooth_control, geodesy, dedup)
+        if device_prep:
+            prepared = _prepare_tracks_on_device(batch, args, ship_ids, smooth_control, geodesy, dedup)
+        else:
+            prepared = (_prepare_track(args, sid, smooth_control, geodesy, dedup) for sid in ship_ids)
+        for st, x0 in prepared:
             tracks.append(st)
             x0s.append(x0[:, 0])
             dts.append(generate_dts(st.dts, substeps))
