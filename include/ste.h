@@ -41,6 +41,9 @@
  *   ste_raster_metrics_f64   the values of a gridded field (land mask, depth, density) along such tracks: time with and without
  *                            data, the time-weighted sum, extremes and when, and excursions past a threshold, in exact integer
  *                            ticks (no counterpart in the reference: a download and a host loop)
+ *   ste_track_simplify_f64   such tracks made smaller within a tolerance: the time-aware Douglas-Peucker rule (or the classic one
+ *                            on shape alone), keep flags and the kept rows compacted into a fleet of their own (no counterpart in
+ *                            the reference, whose callers download every row of every history)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -84,7 +87,8 @@ extern "C" {
                            the device (ste_speed_metrics_f64).  Unnumbered addition: errors of tracks on the device against
                            truth positions (ste_track_errors_f64).  Unnumbered addition: the values of a gridded field along
                            tracks on the device (ste_raster_metrics_f64).  Unnumbered addition: observation preparation with
-                           SOG / COG smoothed first (ste_track_prep_smooth_f64).
+                           SOG / COG smoothed first (ste_track_prep_smooth_f64).  Unnumbered addition: tracks on the device
+                           simplified within a tolerance (ste_track_simplify_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1171,6 +1175,90 @@ typedef struct ste_raster_f64 {
 } ste_raster_f64;          /* 216 bytes */
 
 int ste_raster_metrics_f64(const ste_ukf_batch_f64* b, const ste_raster_f64* r, void* stream);
+
+/*
+ * SIMPLIFICATION: tracks that stay on the device made SMALLER within a tolerance (an unnumbered addition, like ste_raster_f64):
+ * the time-aware Douglas-Peucker rule (TD-TR, "synchronised Euclidean distance"), which drops a row when the position
+ * interpolated AT THAT ROW'S OWN TIME on the chord between the surviving neighbours is within the tolerance of the row, so that
+ * ste_track_positions_f64 on the simplified track stays within the tolerance of the original at every row time; and, with
+ * STE_SIMPLIFY_SHAPE, the classic rule on the perpendicular distance, for questions without a clock (routes, lines).  `states` is
+ * that of ste_path_f64; components 0 and 1 are read.  Every expression below is evaluated as written, left to right,
+ * without contraction, and no transcendental function appears in any decision: a restatement in IEEE doubles (tests/simplify_cases.py)
+ * reproduces every output bit for bit.  For track t of sample s let ns = nsteps[t] (NULL = Nmax), rows 0 .. ns.
+ *   - Clock.  T_0 = 0, T_{k+1} = T_k + dt_k, summed in order.  The clock is bad when some dt_k, k < ns, is not finite or is
+ *     negative (STE_SIMPLIFY_BAD_TIME).  With STE_SIMPLIFY_SHAPE there is no clock: no T is formed and the bit is never set.
+ *   - Unwrapped longitude.  X_0 = lon_0, X_{k+1} = X_k + wrap180(lon_{k+1} - lon_k), summed in order, wrap180 that of
+ *     ste_path_f64; Y_k = lat_k.  The track is BROKEN when for some k < ns |wrap180(lon_{k+1} - lon_k)| < 90 is false, or when a
+ *     latitude of rows 0 .. ns is not finite (STE_SIMPLIFY_BROKEN; it depends on the sample, the other two bits do not).
+ *   - Metric.  c = lon_scale[t], or lon_scale_all where lon_scale is NULL; tol = tolerance[t], or tolerance_all where tolerance
+ *     is NULL, in degrees of a great circle.  A per-track c or tol that is not finite or is negative sets
+ *     STE_SIMPLIFY_BAD_LIMIT; a scalar with that defect is refused.  tol2 = tol * tol.
+ *   - Deviation of row k from the chord (i, j), i < k < j.  xk = (X_k - X_i) * c, yk = Y_k - Y_i, xj = (X_j - X_i) * c,
+ *     yj = Y_j - Y_i.  With the clock (the default): den = T_j - T_i and u = den > 0 ? (T_k - T_i) / den : 0.  With
+ *     STE_SIMPLIFY_SHAPE: den = xj * xj + yj * yj and u = den > 0 ? clamp01((xk * xj + yk * yj) / den) : 0, clamp01(x) =
+ *     x < 0 ? 0 : (x > 1 ? 1 : x).  Then ex = xk - u * xj, ey = yk - u * yj, d2 = ex * ex + ey * ey.
+ *   - Rule.  Rows 0 and ns are kept.  A range (i, j) with j > i + 1 takes best = -1; its winner is the SMALLEST k with
+ *     d2 > best, scanning k upwards (strict: the first of equal rows wins and a NaN never wins).  If best > tol2 (strict), row k
+ *     is kept and (i, k) and (k, j) are ranges.  Otherwise no row inside the range is kept, and if best > worst_sq then
+ *     worst_sq = best; worst_sq starts at 0.0.  The result does not depend on the order in which ranges are taken.
+ *   - A (sample, track) with any of the three bits keeps every row 0 .. ns (the identity, lossless): nkeep = ns + 1 and
+ *     worst_sq = NaN.  ns = 0: row 0 is kept, nkeep = 1, worst_sq = 0.
+ *   - Outputs, each may be NULL but not all of them.  keep is 1 or 0 for rows 0 .. ns, keep[(s * (Nmax + 1) + k) * track_stride
+ *     + t]; rows past ns are untouched.  nkeep, worst_sq (deg^2 in the scaled plane) and status are out[s * track_stride + t].
+ *   - Compaction.  cap is the number of rows the three arrays rows, out_states and out_dt hold, 1 <= cap <= Nmax + 1, read only
+ *     when one of them is given.  rows[(s * cap + m) * track_stride + t] is the m-th kept row r_m; out_states[((s * cap + m) * 4
+ *     + c) * track_stride + t] holds the four components of that row, its bits; out_dt[(s * (cap - 1) + m) * track_stride + t]
+ *     is dt_{r_m} + dt_{r_m + 1} + ... + dt_{r_{m+1} - 1}, summed in order STARTING FROM THE FIRST TERM, so adjacent kept rows
+ *     give dt's own bits and the identity reproduces the batch.  Entries at and past nkeep (out_dt: nkeep - 1) are untouched.
+ *     When nkeep > cap the first cap kept rows are written, STE_SIMPLIFY_TRUNCATED is set and nkeep stays the true count.  A
+ *     compacted block is itself a resident fleet: a batch struct with B, Nmax = cap - 1, nsteps = nkeep - 1 and dt = out_dt is
+ *     all a ste_*_metrics_f64 call reads of a batch.
+ *   - Every value's bits depend on the track's rows, its dt, c, tol and the flag alone: not on S, the window, which outputs
+ *     were asked for, or whether `work` was used.
+ *   - The call reads only B, Nmax, track_stride, nsteps and dt of the batch and writes nothing of the batch; windows and
+ *     addressing are those of ste_path_metrics_f64, tolerance and lon_scale like nsteps.  Rows past nsteps[t] of states are not
+ *     read.  b->dt is required unless STE_SIMPLIFY_SHAPE is set and out_dt is NULL.
+ *   - Work.  A track with more than ste_track_simplify_lds_rows() rows keeps X, Y, T and its flags in `work`;
+ *     ste_track_simplify_workspace(Nmax, nstates, B) is the number of bytes these sizes need, 0 while Nmax + 1 <=
+ *     ste_track_simplify_lds_rows().
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or sf NULL; states NULL; nstates < 1 or
+ *     > 65535; flags with any other bit than STE_SIMPLIFY_SHAPE; reserved != 0; tolerance NULL and tolerance_all not finite or
+ *     negative; lon_scale NULL and lon_scale_all not finite or negative; rows, out_states or out_dt given with cap == 0, or with
+ *     cap outside 1 .. Nmax + 1; b->dt NULL where it is read; work NULL or work_bytes below ste_track_simplify_workspace(Nmax,
+ *     nstates, B) when that is non-zero; every output NULL; B <= 0, Nmax < 0 or Nmax > 2^31 - 257, or track_stride non-zero and
+ *     below B.
+ */
+#define STE_SIMPLIFY_SHAPE 0x1u       /* flags: the perpendicular distance to the chord, no clock (default: at the row's own time) */
+#define STE_SIMPLIFY_BAD_TIME 0x1     /* status: a dt below nsteps that is not finite and >= 0 (clock mode) */
+#define STE_SIMPLIFY_BAD_LIMIT 0x2    /* status: the track's tolerance or lon_scale is not finite or is < 0 */
+#define STE_SIMPLIFY_BROKEN 0x4       /* status: a step of 90 degrees of longitude or more, or a latitude that is not finite */
+#define STE_SIMPLIFY_TRUNCATED 0x8    /* status: nkeep > cap: the first cap kept rows were written */
+typedef struct ste_simplify_f64 {
+    int32_t nstates;         /* S >= 1 tracks per ship in `states` (<= 65535) */
+    uint32_t flags;          /* STE_SIMPLIFY_SHAPE or 0 */
+    int32_t cap;             /* rows of `rows`, `out_states` and `out_dt` (cap - 1); 1 .. Nmax + 1; read with one of them only */
+    int32_t reserved;        /* must be 0 */
+    const double* states;    /* DEVICE [S][Nmax+1][4][track_stride], as ste_path_f64; components 0 and 1 decide */
+    const double* tolerance; /* DEVICE [track_stride]: degrees per track, or NULL: tolerance_all for every track */
+    double tolerance_all;    /* degrees of a great circle, finite, >= 0 */
+    const double* lon_scale; /* DEVICE [track_stride]: c per track, or NULL: lon_scale_all for every track */
+    double lon_scale_all;    /* finite, >= 0; 1 = plain degrees, cos(lat) = a local equirectangular plane */
+    double* work;            /* DEVICE scratch of work_bytes, see ste_track_simplify_workspace; may be NULL when that is 0 */
+    int64_t work_bytes;
+    uint8_t* keep;           /* DEVICE [S][Nmax+1][track_stride] or NULL: 1 / 0 for rows 0 .. nsteps[t] */
+    int32_t* nkeep;          /* DEVICE [S][track_stride] or NULL: kept rows (the true count, also when truncated) */
+    double* worst_sq;        /* DEVICE [S][track_stride] or NULL: the largest d2 of a range that was closed; NaN = identity */
+    int32_t* status;         /* DEVICE [S][track_stride] or NULL: STE_SIMPLIFY_* bits */
+    int32_t* rows;           /* DEVICE [S][cap][track_stride] or NULL: the m-th kept row */
+    double* out_states;      /* DEVICE [S][cap][4][track_stride] or NULL: that row of states */
+    double* out_dt;          /* DEVICE [S][cap-1][track_stride] or NULL: hours from kept row m to kept row m + 1 */
+} ste_simplify_f64;          /* 128 bytes */
+
+int ste_track_simplify_f64(const ste_ukf_batch_f64* b, const ste_simplify_f64* sf, void* stream);
+/* bytes of `work` these sizes need; may be 0 */
+size_t ste_track_simplify_workspace(int32_t Nmax, int32_t nstates, int32_t B);
+/* rows of a track the kernel keeps in LDS; a track with more goes through `work` */
+int ste_track_simplify_lds_rows(void);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -463,6 +463,38 @@ class SteErrorsF64(C.Structure):
     ]
 
 
+STE_SIMPLIFY_SHAPE = 0x1
+STE_SIMPLIFY_BAD_TIME = 0x1
+STE_SIMPLIFY_BAD_LIMIT = 0x2
+STE_SIMPLIFY_BROKEN = 0x4
+STE_SIMPLIFY_TRUNCATED = 0x8
+
+
+class SteSimplifyF64(C.Structure):
+    """Mirror of ``struct ste_simplify_f64`` (include/ste.h): tracks on the device simplified within a tolerance."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("flags", C.c_uint32),
+        ("cap", C.c_int32),
+        ("reserved", C.c_int32),
+        ("states", _dp),
+        ("tolerance", _dp),
+        ("tolerance_all", C.c_double),
+        ("lon_scale", _dp),
+        ("lon_scale_all", C.c_double),
+        ("work", _dp),
+        ("work_bytes", C.c_int64),
+        ("keep", _dp),
+        ("nkeep", _dp),
+        ("worst_sq", _dp),
+        ("status", _dp),
+        ("rows", _dp),
+        ("out_states", _dp),
+        ("out_dt", _dp),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -598,6 +630,9 @@ SYMBOLS = {
     "ste_speed_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSpeedF64), C.c_void_p]),
     "ste_track_errors_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteErrorsF64), C.c_void_p]),
     "ste_raster_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRasterF64), C.c_void_p]),
+    "ste_track_simplify_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSimplifyF64), C.c_void_p]),
+    "ste_track_simplify_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ste_track_simplify_lds_rows": (C.c_int, []),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1537,6 +1537,102 @@ class DeviceBatch:
                 out["mean_nees"], out["coverage"] = out["sum_nees"] / out["nscored"], out["ninside"].double() / out["nscored"]
             return self._finish(st, keep, out)
 
+    # -- simplification -------------------------------------------------------------------------------------------
+    def _track_limit(self, x, name: str, width, col, keep):
+        """A limit of a metric call given as a scalar or one value per track, (B,), as (the pointer the kernel takes or None,
+        the scalar it takes beside it).  Inside the stream context."""
+        torch, B = self.torch, self.ntracks
+        tv = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+        tv = tv.to(torch.float64)
+        if tv.dim() == 0:
+            return None, float(tv)
+        if tuple(tv.shape) != (B,):
+            raise ValueError(f"{name} must be a scalar or have shape ({B},), got {tuple(tv.shape)}")
+        wide = torch.zeros((width,), dtype=torch.float64, device=self.device)
+        wide[col:col + B] = tv.to(self.device)
+        keep.append(wide)
+        return wide.data_ptr() + 8 * col, 0.0
+
+    def track_lon_scale(self, states):
+        """cos of the smallest |latitude| over the rows <= nsteps of all samples of each track, (B,) on the device: the
+        ``lon_scale="track"`` of ``simplify_tracks``.  It never measures an east-west extent of the track short."""
+        torch = self.torch
+        states, _ = self._metric_states(states)
+        N, B = int(self.struct.Nmax), self.ntracks
+        ns = self.t["nsteps"][self.lo:self.lo + B]
+        past = torch.arange(N + 1, device=self.device)[:, None] > ns[None, :]  # (N+1, B)
+        lat = states[:, :, 1, :].abs().masked_fill(past[None], float("inf"))
+        return torch.cos(torch.deg2rad(lat.amin(dim=(0, 1))))
+
+    def simplify_tracks(self, states, tolerance_km, shape: bool = False, lon_scale="track", compact: bool = True, max_rows=None,
+                        stream=None):
+        """Tracks that are on the device made smaller within a tolerance (include/ste.h: ste_track_simplify_f64; DESIGN.md,
+        "Simplification"): the time-aware Douglas-Peucker rule, which drops a row when the position interpolated at that row's
+        own time between the surviving neighbours is within ``tolerance_km`` of it, so that ``positions_at`` on the result stays
+        within the tolerance at every row time; with ``shape`` the classic rule on the perpendicular distance, without a clock
+        (what ``route_metrics`` and ``line_metrics`` ask about).  ``states`` as in ``path_metrics``.  ``tolerance_km``: a scalar
+        or one value per track, km, divided by ``KM_PER_DEG``.  ``lon_scale``: what a degree of longitude counts against a
+        degree of latitude: "track" (``track_lon_scale``: the tolerance is honoured in the local equirectangular sense), a
+        float (1.0 = plain degrees) or one value per track.
+
+        Returns a dict of device tensors: ``keep`` (S, Nmax+1, B) uint8, 1 for a kept row, 0 otherwise and past ``nsteps[b]``;
+        ``nkeep`` (S, B) int32; ``worst_km`` (S, B), the largest deviation of a dropped row from its chord (NaN for a track
+        kept whole because of a status bit); ``status`` (S, B) int32, STE_SIMPLIFY_BAD_TIME / BAD_LIMIT / BROKEN (the track is
+        kept whole) and TRUNCATED; ``lon_scale`` (B,), as given to the kernel (absent for a float); and with ``compact`` the
+        kept rows as a fleet of their own, narrowed to the largest ``nkeep`` (one small read-back, no second launch) or to
+        ``max_rows``: ``rows`` (S, M, B) int32, -1 past ``nkeep``; ``states`` (S, M, 4, B), NaN past ``nkeep``; ``dt``
+        (S, M-1, B), the hours between kept rows, 0 past ``nkeep``.  Windows, in-place views and ``stream`` as in
+        ``path_metrics``; every value depends on its own track's rows, ``dt``, tolerance and scale alone."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        states, S = self._metric_states(states)
+        cap = N + 1 if max_rows is None else int(max_rows)
+        if compact and not 1 <= cap <= N + 1:
+            raise ValueError(f"max_rows must be None or between 1 and Nmax + 1 = {N + 1}, got {max_rows!r}")
+        st = self._ordered_stream(stream)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            keep = []
+            scale_t = None
+            if isinstance(lon_scale, str):
+                if lon_scale != "track":
+                    raise ValueError(f"lon_scale must be 'track', a float or have shape ({B},), got {lon_scale!r}")
+                lon_scale = scale_t = self.track_lon_scale(states)
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=not shape or compact)
+            sf = binding.SteSimplifyF64()
+            sf.nstates, sf.flags, sf.reserved, sf.states = S, (binding.STE_SIMPLIFY_SHAPE if shape else 0), 0, states.data_ptr()
+            tol = tolerance_km / KM_PER_DEG if isinstance(tolerance_km, torch.Tensor) else np.asarray(tolerance_km, dtype=np.float64) / KM_PER_DEG
+            sf.tolerance, sf.tolerance_all = self._track_limit(tol, "tolerance_km", width, col, keep)
+            sf.lon_scale, sf.lon_scale_all = self._track_limit(lon_scale, "lon_scale", width, col, keep)
+            if sf.lon_scale and scale_t is None:
+                scale_t = keep[-1][col:col + B]
+            need = int(self.lib.ste_track_simplify_workspace(N, S, B))
+            if need:
+                work = torch.empty(((need + 7) // 8,), **f64)
+                keep.append(work)
+                sf.work, sf.work_bytes = work.data_ptr(), need
+            # rows as wide as the states': the window's columns are what the call writes and what is returned
+            full = {"keep": torch.zeros((S, N + 1, width), dtype=torch.uint8, device=self.device),
+                    "nkeep": torch.empty((S, width), **i32), "worst_sq": torch.empty((S, width), **f64),
+                    "status": torch.empty((S, width), **i32)}
+            if compact:
+                sf.cap = cap
+                full["rows"] = torch.full((S, cap, width), -1, **i32)
+                full["out_states"] = torch.full((S, cap, 4, width), float("nan"), **f64)
+                full["out_dt"] = torch.zeros((S, max(cap - 1, 0), width), **f64)
+            for k, ten in full.items():
+                setattr(sf, k, ten.data_ptr() + ten.element_size() * col)
+            binding.check(self.lib.ste_track_simplify_f64(C.byref(s), C.byref(sf), self._stream(st)), "ste_track_simplify_f64")
+            out = {k: ten[..., col:col + B] for k, ten in full.items()}
+            out["worst_km"] = torch.sqrt(out.pop("worst_sq")) * KM_PER_DEG
+            if scale_t is not None:
+                out["lon_scale"] = scale_t
+            if compact:
+                m = min(int(out["nkeep"].max()), cap)  # the read-back: how many rows the longest simplified track keeps
+                out["rows"], out["states"], out["dt"] = out["rows"][:, :m], out.pop("out_states")[:, :m], out.pop("out_dt")[:, :m - 1]
+            return self._finish(st, keep, out)
+
     # -- results ------------------------------------------------------------------------------------------------
     _OUT = {"means": ("fwd_mean", 4), "covs": ("fwd_cov", 16), "means_smoothed": ("sm_mean", 4),
             "covs_smoothed": ("sm_cov", 16)}
@@ -3860,6 +3956,85 @@ def curve_distance(curves_a, curves_b, dtw: bool = False, band: int = 0, reverse
 
 
 KM_PER_DEG = 6378.137 * np.pi / 180.0  # Kd: km per degree of a great circle on the sphere of the leg functions
+
+
+class SimplifiedTrack(dict):
+    """The kept rows of one ship (``simplified_tracks``): ``rows``, ``lon``, ``lat``, ``speed``, ``heading``, ``time`` as (n,)
+    arrays, and ``worst_km`` and ``status`` of the simplification."""
+
+    def curve(self) -> np.ndarray:
+        """(n, 2) lon / lat: what ``curve_distance`` and ``track_lines`` take."""
+        return np.column_stack([self["lon"], self["lat"]])
+
+    def curves(self):
+        return [self.curve()]
+
+
+class SimplifiedTracks:
+    """The kept rows of every ship of a batch (``simplified_tracks``), in the batch's slot order: a sequence of
+    ``SimplifiedTrack``, made on access as views of the flat arrays that came from the device (``rows``, ``lon``, ``lat``,
+    ``speed``, ``heading``, ship after ship; ship b owns ``offsets[b]:offsets[b + 1]``); a ship's ``time`` is summed from the
+    host batch's ``dt`` (Nmax, B) when the ship is asked for."""
+
+    FIELDS = ("rows", "lon", "lat", "speed", "heading")
+
+    def __init__(self, flat: dict, offsets: np.ndarray, worst_km: np.ndarray, status: np.ndarray, dt: np.ndarray):
+        self.flat, self.offsets, self.worst_km, self.status, self.dt = flat, offsets, worst_km, status, dt
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def __getitem__(self, b: int) -> SimplifiedTrack:
+        n = len(self)
+        if not -n <= b < n:
+            raise IndexError(f"ship {b} of {n}")
+        b %= n
+        sl = slice(int(self.offsets[b]), int(self.offsets[b + 1]))
+        clock = np.concatenate([[0.0], np.cumsum(self.dt[:, b])])  # T_0 = 0, T_{k+1} = T_k + dt_k, in order: the kernel's clock
+        return SimplifiedTrack({k: self.flat[k][sl] for k in self.FIELDS}, time=clock[self.flat["rows"][sl]],
+                               worst_km=float(self.worst_km[b]), status=int(self.status[b]))
+
+    def __iter__(self):
+        return (self[b] for b in range(len(self)))
+
+    def curves(self):
+        """A list of (n, 2) lon / lat arrays, one per ship: what ``curve_distance`` and ``track_lines`` take."""
+        return [t.curve() for t in self]
+
+
+def simplified_tracks(hb_or_db, tolerance_km, which: str = "smoothed", shape: bool = False, lon_scale="track",
+                      device="cuda:0") -> SimplifiedTracks:
+    """The smoothed (``which="smoothed"``) or filtered (``"filtered"``) tracks of a batch, simplified within ``tolerance_km``
+    on the device (``DeviceBatch.simplify_tracks``), kept rows only: per ship a ``SimplifiedTrack`` with ``rows`` (the
+    indices of the kept rows), ``lon``, ``lat``, ``speed``, ``heading`` (the kept rows of the history, their bits) and ``time``
+    (hours from row 0, ``dt`` summed in order).  A ``HostBatch`` is uploaded and ``run()``; a ``DeviceBatch`` (or a window of
+    one) is taken to hold its histories.  The gather is a masked select on the device, and one copy of the kept rows crosses
+    PCIe where ``download`` ships every row of every history."""
+    import torch
+
+    if which not in ("smoothed", "filtered"):
+        raise ValueError(f"which must be 'smoothed' or 'filtered', got {which!r}")
+    if isinstance(hb_or_db, DeviceBatch):
+        db = hb_or_db
+    else:
+        db = DeviceBatch(hb_or_db, device=device, alloc_smoothed=which == "smoothed")
+        db.run() if which == "smoothed" else db.forward()
+    mean = db.sm_mean if which == "smoothed" else db.fwd_mean
+    if mean is None:
+        raise ValueError(f"this batch holds no {which} history")
+    out = db.simplify_tracks(mean, tolerance_km, shape=shape, lon_scale=lon_scale, compact=False)
+    B, lo = db.ntracks, db.lo
+    flags = out["keep"][0].T.bool()  # (B, Nmax+1)
+    kept = mean.permute(2, 0, 1)[flags]  # (K, 4), ship after ship
+    row = flags.nonzero()[:, 1]
+    packed = torch.cat([kept, row.to(torch.float64)[:, None]], dim=1).cpu().numpy()  # the one copy of the kept rows
+    small = torch.stack([out["nkeep"][0].double(), out["status"][0].double(), out["worst_km"][0]]).cpu().numpy()
+    counts = small[0].astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    lon, lat, speed, heading, rowf = np.ascontiguousarray(packed.T)
+    rows = rowf.astype(np.int64)
+    return SimplifiedTracks(dict(rows=rows, lon=lon, lat=lat, speed=speed, heading=heading), offsets, small[2], small[1],
+                            db.hb.dt[:, lo:lo + B])
 
 
 def position_ellipse(count, moments, anchor_lat, prob: float = 0.95):

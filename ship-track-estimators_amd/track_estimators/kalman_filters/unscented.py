@@ -529,6 +529,22 @@ class UnscentedKalmanFilter(KalmanFilterBase):
             raise np.linalg.LinAlgError("SVD did not converge")
         return {k: v[..., 0] for k, v in out.items() if k not in ("status", "track_status", "mean_speed", "vmax")}
 
+    def simplified_track(self, tolerance_km, which: str = "smoothed", shape: bool = False, lon_scale="track"):
+        """The track ``run`` filtered, simplified within ``tolerance_km`` on the device
+        (``track_estimators.batch.simplified_tracks``; no counterpart in the reference): a ``SimplifiedTrack``, a dict of
+        the kept rows only, ``rows``, ``lon``, ``lat``, ``speed``, ``heading`` and ``time`` (hours from the first row), with
+        ``worst_km`` and ``status``; its ``curves()`` gives the (n, 2) lon / lat arrays that ``curve_distance`` and
+        ``track_lines`` take.  ``which``: "smoothed" or "filtered".  The default rule keeps ``positions_at`` within the
+        tolerance at every row time; ``shape`` asks about the curve alone.  The track is packed as ``run`` packed it, as for
+        ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("simplified_track() simplifies the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("simplified_track() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        return _batch.simplified_tracks(hb, tolerance_km, which=which, shape=shape, lon_scale=lon_scale)[0]
+
     def track_error(self, truth=None, n_samples: int = 0, course=None, coverage: float = 0.95, within_km=None,
                     quantiles=None, model: str = "sphere", random_state: int = 0):
         """How far the track ``run`` filtered is from truth positions (``DeviceBatch.track_errors`` and
