@@ -44,6 +44,9 @@
  *   ste_track_simplify_f64   such tracks made smaller within a tolerance: the time-aware Douglas-Peucker rule (or the classic one
  *                            on shape alone), keep flags and the kept rows compacted into a fleet of their own (no counterpart in
  *                            the reference, whose callers download every row of every history)
+ *   ste_ukf_noise_moments_f64 / ste_ukf_noise_mstep_f64   the measurement noise R of a track or a group of tracks fitted to the
+ *                            data by EM, from the smoothed marginals on the device (no counterpart in the reference, where R is
+ *                            an argument of UnscentedKalmanFilter, unscented.py:55-61)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -88,7 +91,8 @@ extern "C" {
                            truth positions (ste_track_errors_f64).  Unnumbered addition: the values of a gridded field along
                            tracks on the device (ste_raster_metrics_f64).  Unnumbered addition: observation preparation with
                            SOG / COG smoothed first (ste_track_prep_smooth_f64).  Unnumbered addition: tracks on the device
-                           simplified within a tolerance (ste_track_simplify_f64).
+                           simplified within a tolerance (ste_track_simplify_f64).  Unnumbered addition: measurement noise fitted
+                           by EM on the device (ste_ukf_noise_moments_f64, ste_ukf_noise_mstep_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1259,6 +1263,98 @@ int ste_track_simplify_f64(const ste_ukf_batch_f64* b, const ste_simplify_f64* s
 size_t ste_track_simplify_workspace(int32_t Nmax, int32_t nstates, int32_t B);
 /* rows of a track the kernel keeps in LDS; a track with more goes through `work` */
 int ste_track_simplify_lds_rows(void);
+
+/*
+ * NOISE FIT: the measurement noise R of a track, or of a group of tracks, estimated from the data by EM (an unnumbered
+ * addition, like ste_ukf_noise_f64, whose R stack it fills).  The E-step is a forward pass and a smoother; the M-step is
+ *      R_new = 1/n sum_u [ (z_u - H m^s)(z_u - H m^s)^T + H P^s H^T ]
+ * over the updates u of the track (group), m^s, P^s the smoothed row the update produced, followed by a projection onto the
+ * structure R may have.  Two calls: the per-track sums of the terms, and the deterministic sum over a group with the projection.
+ *
+ * ste_ukf_noise_moments_f64 -- per-track sums, from a completed forward pass and smoother of the batch.
+ *   - Updates.  An update is a step k < nsteps[t] with 0 <= upd_idx[k] < Tmax; its row is k + 1 and its observation column
+ *     upd_idx[k] of z.  The initial update never counts: row 0 of the histories is the prior (kalman_filter.py:76), not the
+ *     state that update produced.
+ *   - Term of an update, every expression evaluated as written, left to right, without contraction (no fma):
+ *         (Hm)_r = ((H_r0 m_0 + H_r1 m_1) + H_r2 m_2) + H_r3 m_3,   v = z - Hm,   v_3 = wrap180(v_3) (that of ste_path_f64)
+ *         G_rc   = ((H_r0 P_0c + H_r1 P_1c) + H_r2 P_2c) + H_r3 P_3c,   P_ic the stored entry (min(i, c), max(i, c)) of sm_cov
+ *         (GH)_rc = ((G_r0 H_c0 + G_r1 H_c1) + G_r2 H_c2) + G_r3 H_c3   for r <= c
+ *         term_rc = v_r v_c + (GH)_rc                                    for r <= c, the ten entries in the order of STE_FLAG_PACKED_COV
+ *     moments holds the sums of the terms, vsum the sums of v (the bias of the observations against the smoothed track), both
+ *     starting from 0.0 and adding in ascending step order; count the number of updates summed.  A track's bits depend on
+ *     its own rows only.
+ *   - Unusable tracks have count 0 and zero sums: a track whose b->status carries STE_STATUS_NAN (STE_NOISE_TRACK_NAN; its
+ *     rows are not read; b->status NULL = no track does), and a track with a non-finite term (STE_NOISE_TRACK_NOT_FINITE).
+ *   - The call reads B, Nmax, Tmax, track_stride, flags (STE_FLAG_PACKED_COV), H (HOST, read at call time), nsteps (NULL =
+ *     Nmax for every track), upd_idx, z, sm_mean, sm_cov and status of the batch and writes nothing of it.  Per-track arrays
+ *     are addressed a[row * track_stride + t] with the pointers naming the window's first track; track_status is [B].
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or nm NULL; moments or count NULL; H, sm_mean,
+ *     sm_cov, z or upd_idx NULL; STE_FLAG_ROBUST (the filter rescales R per update, and the M-step above is not defined);
+ *     recorded noise (noise_upd non-NULL: the update saw z + noise); a time slice (step_begin != 0 or step_end not 0 or Nmax);
+ *     nm->flags or nm->reserved non-zero; B <= 0, Nmax < 0, Tmax < 1, or track_stride non-zero and below B.
+ */
+#define STE_NOISE_TRACK_NAN 0x1        /* track_status: the batch's status carries STE_STATUS_NAN for this track */
+#define STE_NOISE_TRACK_NOT_FINITE 0x2 /* track_status: a term of this track was not finite */
+typedef struct ste_noise_moments_f64 {
+    double* moments;       /* DEVICE [10][track_stride] out, required */
+    int32_t* count;        /* DEVICE [track_stride] out, required: updates summed */
+    double* vsum;          /* DEVICE [4][track_stride] out or NULL: sum of v */
+    int32_t* track_status; /* DEVICE [B] out or NULL: STE_NOISE_TRACK_* bits (overwritten) */
+    uint32_t flags;        /* must be 0 */
+    uint32_t reserved;     /* must be 0 */
+} ste_noise_moments_f64;   /* 40 bytes */
+
+int ste_ukf_noise_moments_f64(const ste_ukf_batch_f64* b, const ste_noise_moments_f64* nm, void* stream);
+
+/*
+ * ste_ukf_noise_mstep_f64 -- the sums of a group's tracks, divided by the group's count and projected.  The order of the
+ * additions is part of the definition, so R has the same bits in every run (an atomic sum over tracks would not).
+ *   - Groups come as CSR: group g has the members group_members[group_offsets[g] .. group_offsets[g + 1]), indices of tracks
+ *     in [0, ntracks); a track is a member of at most one group (the caller's promise; a track that is a member of none keeps
+ *     its R).  nmembers is group_offsets[ngroups] as the host knows it; offsets are clamped to [0, nmembers], and a member
+ *     outside [0, ntracks) is skipped and sets STE_NOISE_GROUP_BAD_MEMBER.  Both pointers NULL: every track is a group of its
+ *     own (ngroups == ntracks, nmembers == 0).
+ *   - Sums, for entries 00, 01 and 11 of moments (the others enter no structure and are not summed) and for count: a wave per
+ *     group; lane l starts from 0.0 (0) and adds members l, l + 64, l + 128, ... of the group in that order; then for
+ *     off = 32, 16, 8, 4, 2, 1 lane l < off adds lane l + off's value to its own; lane 0 holds the sums M and n.  With NULL
+ *     groups a lane per track: 0.0 + the track's value.
+ *   - Projection, with M_e = sum_e / (double)n.  Every structure confines R to the leading 2 x 2 block, so
+ *     STE_NOISE_R_BLOCK2 holds for the result:
+ *         STE_NOISE_FIT_SCALAR   r diag(1, 1, 0, 0), r = (M_00 + M_11) / 2.0
+ *         STE_NOISE_FIT_DIAG2    diag(M_00, M_11, 0, 0)
+ *         STE_NOISE_FIT_BLOCK2   entries 00, 01, 11 = M_00, M_01, M_11, the rest 0
+ *   - Outputs.  R_group holds the projected triangle and n_group the count of every group, whatever its status (n = 0 gives
+ *     NaN).  R_tracks receives the group's triangle for every member -- unless the group is EMPTY (n = 0) or has a BAD_VARIANCE
+ *     (entry 00 or 11 of the projection not finite or <= 0, or entry 01 not finite): then group_status says so and the
+ *     members' R_tracks keep their values.  Every output has one writer: plain vector stores.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: ms NULL; moments, count, R_group, n_group,
+ *     group_status or R_tracks NULL; exactly one of group_offsets / group_members NULL; an unknown structure; reserved != 0;
+ *     ntracks <= 0, ngroups <= 0 or nmembers < 0; ld non-zero and below ntracks; NULL groups with ngroups != ntracks.
+ */
+#define STE_NOISE_FIT_SCALAR 0
+#define STE_NOISE_FIT_DIAG2 1
+#define STE_NOISE_FIT_BLOCK2 2
+#define STE_NOISE_GROUP_EMPTY 0x1        /* group_status: n = 0, nothing to divide by */
+#define STE_NOISE_GROUP_BAD_VARIANCE 0x2 /* group_status: the projection is not a usable R */
+#define STE_NOISE_GROUP_BAD_MEMBER 0x4   /* group_status: a member index outside [0, ntracks) was skipped */
+typedef struct ste_noise_mstep_f64 {
+    int32_t ntracks;              /* tracks in a row of moments / count / R_tracks */
+    int32_t ngroups;              /* G */
+    int32_t nmembers;             /* group_offsets[G]; 0 with NULL groups */
+    int32_t structure;            /* STE_NOISE_FIT_* */
+    int64_t ld;                   /* tracks per row of moments and R_tracks (the track_stride of call 1); 0 = ntracks */
+    const double* moments;        /* DEVICE [10][ld], from ste_ukf_noise_moments_f64 */
+    const int32_t* count;         /* DEVICE [ld] */
+    const int32_t* group_offsets; /* DEVICE [G + 1] or NULL */
+    const int32_t* group_members; /* DEVICE [nmembers] or NULL */
+    double* R_group;              /* DEVICE [10][G] out */
+    int32_t* n_group;             /* DEVICE [G] out */
+    int32_t* group_status;        /* DEVICE [G] out: STE_NOISE_GROUP_* bits (overwritten) */
+    double* R_tracks;             /* DEVICE [10][ld] in / out: ste_ukf_noise_f64.R of the batch */
+    int64_t reserved;             /* must be 0 */
+} ste_noise_mstep_f64;            /* 96 bytes */
+
+int ste_ukf_noise_mstep_f64(const ste_noise_mstep_f64* ms, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -495,6 +495,48 @@ class SteSimplifyF64(C.Structure):
     ]
 
 
+STE_NOISE_TRACK_NAN = 0x1
+STE_NOISE_TRACK_NOT_FINITE = 0x2
+STE_NOISE_FIT_SCALAR, STE_NOISE_FIT_DIAG2, STE_NOISE_FIT_BLOCK2 = 0, 1, 2
+STE_NOISE_GROUP_EMPTY = 0x1
+STE_NOISE_GROUP_BAD_VARIANCE = 0x2
+STE_NOISE_GROUP_BAD_MEMBER = 0x4
+
+
+class SteNoiseMomentsF64(C.Structure):
+    """Mirror of ``struct ste_noise_moments_f64`` (include/ste.h): per-track sums of the M-step for R."""
+
+    _fields_ = [
+        ("moments", _dp),
+        ("count", _dp),
+        ("vsum", _dp),
+        ("track_status", _dp),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SteNoiseMstepF64(C.Structure):
+    """Mirror of ``struct ste_noise_mstep_f64`` (include/ste.h): group sums and the projection of the M-step for R."""
+
+    _fields_ = [
+        ("ntracks", C.c_int32),
+        ("ngroups", C.c_int32),
+        ("nmembers", C.c_int32),
+        ("structure", C.c_int32),
+        ("ld", C.c_int64),
+        ("moments", _dp),
+        ("count", _dp),
+        ("group_offsets", _dp),
+        ("group_members", _dp),
+        ("R_group", _dp),
+        ("n_group", _dp),
+        ("group_status", _dp),
+        ("R_tracks", _dp),
+        ("reserved", C.c_int64),
+    ]
+
+
 class SteFwdSchedF64(C.Structure):
     """Mirror of ``struct ste_fwd_sched_f64`` (include/ste.h)."""
 
@@ -633,6 +675,8 @@ SYMBOLS = {
     "ste_track_simplify_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSimplifyF64), C.c_void_p]),
     "ste_track_simplify_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ste_track_simplify_lds_rows": (C.c_int, []),
+    "ste_ukf_noise_moments_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteNoiseMomentsF64), C.c_void_p]),
+    "ste_ukf_noise_mstep_f64": (C.c_int, [C.POINTER(SteNoiseMstepF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

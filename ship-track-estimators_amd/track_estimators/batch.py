@@ -804,6 +804,86 @@ class DeviceBatch:
                                  status=self.status.cpu().numpy(),
                                  nis=None if nis_t is None else nis_t[:, col:col + B].T.cpu().numpy())
 
+    # -- measurement noise fitted to the data ("Noise fit") -------------------------------------------
+    _NOISE_STRUCTURES = {"scalar": binding.STE_NOISE_FIT_SCALAR, "diag2": binding.STE_NOISE_FIT_DIAG2,
+                         "block2": binding.STE_NOISE_FIT_BLOCK2}
+
+    def measurement_moments(self, stream=None):
+        """Per-track sums of the M-step for R (include/ste.h: ste_ukf_noise_moments_f64), from the forward pass and the
+        smoother this batch holds: over a track's updates, the residual of the observation against the smoothed row the
+        update produced, as v v^T + H P^s H^T.  Returns device tensors: ``moments`` (10, B) upper triangles, ``count`` (B,)
+        int32, ``vsum`` (4, B) the summed residuals, ``track_status`` (B,) int32 STE_NOISE_TRACK_* bits; an unusable track
+        (a NaN status, a non-finite term) has count 0 and zero sums.  For a window the tensors are views of rows as wide as
+        the fleet's, which is what ``update_measurement_noise`` takes."""
+        if self.sm_mean is None:
+            raise ValueError("measurement_moments() needs the smoothed track, and this batch was built with alloc_smoothed=False")
+        torch = self.torch
+        st = self._ordered_stream(stream)
+        B, ld, col = self.ntracks, int(self.struct.track_stride or self.struct.B), self.lo
+        with torch.cuda.stream(st):
+            mom = torch.zeros((10, ld), dtype=torch.float64, device=self.device)
+            vsum = torch.zeros((4, ld), dtype=torch.float64, device=self.device)
+            count = torch.zeros((ld,), dtype=torch.int32, device=self.device)
+            tstat = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            nm = binding.SteNoiseMomentsF64(mom.data_ptr() + 8 * col, count.data_ptr() + 4 * col, vsum.data_ptr() + 8 * col,
+                                            tstat.data_ptr(), 0, 0)
+            binding.check(self.lib.ste_ukf_noise_moments_f64(C.byref(self.struct), C.byref(nm), self._stream(st)),
+                          "ste_ukf_noise_moments_f64")
+            out = dict(moments=mom[:, col:col + B], count=count[col:col + B], vsum=vsum[:, col:col + B], track_status=tstat)
+            return self._finish(st, [], out)
+
+    def update_measurement_noise(self, moments, groups=None, structure: str = "scalar", stream=None):
+        """The M-step for R (include/ste.h: ste_ukf_noise_mstep_f64) into this batch's own per-track R: the sums of
+        ``moments`` (what ``measurement_moments`` returned) over every group, in a fixed order, divided by the group's count,
+        projected onto ``structure`` ("scalar", "diag2" or "block2") and stored for every member.  ``groups``: None -- every
+        track a group of its own -- or ``(offsets, members)``, int32 CSR over this batch's slots (offsets (G + 1,), members
+        (offsets[G],)), each slot in at most one group.  A group without updates or with an unusable variance keeps its R.
+        The batch must carry an R stack (``with_track_noise``).  Returns device tensors ``R_group`` (10, G), ``n_group`` (G,),
+        ``group_status`` (G,) STE_NOISE_GROUP_* bits.  The next ``forward`` / ``run`` / ``log_likelihood`` filters with the new R."""
+        torch = self.torch
+        if self.noise is None or not self.noise.R:
+            raise ValueError("update_measurement_noise() writes the batch's per-track R: build the batch from "
+                             "with_track_noise(hb, R=...) so that it carries one")
+        if structure not in self._NOISE_STRUCTURES:
+            raise ValueError(f"structure must be one of {sorted(self._NOISE_STRUCTURES)}, got {structure!r}")
+        B, ld = self.ntracks, int(self.struct.track_stride or self.struct.B)
+        mom, count = moments["moments"], moments["count"]
+        if tuple(mom.shape) != (10, B) or tuple(count.shape) != (B,) or mom.stride() != (ld, 1) or mom.dtype != torch.float64 \
+                or count.dtype != torch.int32 or count.stride() != (1,):
+            raise ValueError(f"moments must be what measurement_moments() of this batch returned: moments (10, {B}) float64 in "
+                             f"rows of {ld}, count ({B},) int32")
+        st = self._ordered_stream(stream)
+        with torch.cuda.stream(st):
+            keep = [mom, count]
+            if groups is None:
+                G, nmem, off_p, mem_p = B, 0, None, None
+            else:
+                off, mem = (np.asarray(g) for g in groups)
+                if off.dtype.kind not in "iu" or (mem.size and mem.dtype.kind not in "iu"):
+                    raise ValueError("groups must be (offsets, members), two integer arrays")
+                off, mem = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(mem, dtype=np.int32)
+                if off.ndim != 1 or mem.ndim != 1 or off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != mem.size:
+                    raise ValueError("groups must be (offsets, members): offsets (G + 1,) ascending from 0 to len(members)")
+                if mem.size and (mem.min() < 0 or mem.max() >= B or np.unique(mem).size != mem.size):
+                    raise ValueError(f"groups: members must be distinct slots in [0, {B})")
+                G, nmem = off.size - 1, int(mem.size)
+                off_t = torch.from_numpy(off).to(self.device)
+                mem_t = torch.from_numpy(mem if mem.size else np.zeros(1, dtype=np.int32)).to(self.device)
+                keep += [off_t, mem_t]
+                off_p, mem_p = off_t.data_ptr(), mem_t.data_ptr()
+            Rg = torch.empty((10, G), dtype=torch.float64, device=self.device)
+            ng = torch.empty((G,), dtype=torch.int32, device=self.device)
+            gs = torch.empty((G,), dtype=torch.int32, device=self.device)
+            ms = binding.SteNoiseMstepF64(B, G, nmem, self._NOISE_STRUCTURES[structure], ld, mom.data_ptr(), count.data_ptr(),
+                                          off_p, mem_p, Rg.data_ptr(), ng.data_ptr(), gs.data_ptr(), self.noise.R, 0)
+            binding.check(self.lib.ste_ukf_noise_mstep_f64(C.byref(ms), self._stream(st)), "ste_ukf_noise_mstep_f64")
+            if not self.noise.flags & binding.STE_NOISE_R_BLOCK2:
+                # the promise covers every track, and a group that failed (or a slot in no group) keeps the R it had: look
+                Rt = self.t["R_tracks"][:, self.lo:self.lo + B].cpu().numpy()
+                if r_tracks_block2(Rt):
+                    self.noise.flags |= binding.STE_NOISE_R_BLOCK2
+            return self._finish(st, keep, dict(R_group=Rg, n_group=ng, group_status=gs))
+
     # -- posterior tracks ----------------------------------------------------------------------------------------
     def _sample_struct(self, samples, nsamples: int):
         """The ``ste_ukf_sample_f64`` of this batch (or window) for ``samples`` [S][N+1][4][ld], with a coefficient workspace
@@ -4218,6 +4298,156 @@ def best_noise(grid: LogLikelihood, per_track: bool = False) -> NoiseChoice:
         return NoiseChoice(index=-1, loglik=np.full(ll.shape[0], np.nan), excluded=int(keep.size))
     sums = np.where(keep[None, :], ll, 0.0).sum(axis=1)
     return NoiseChoice(index=int(np.argmax(sums)), loglik=sums, excluded=int((~keep).sum()))
+
+
+@dataclasses.dataclass
+class NoiseFit:
+    """``fit_measurement_noise``'s answer, G groups.  ``R`` (G, 4, 4): the winning iterate's R of every group (for a group
+    whose winner is iterate 0, the R its first member started with); ``R_trace`` (iterations + 1, G, 4, 4): every iterate, a
+    stopped group repeating its last.  ``groups`` (B,): the group of every SLOT of
+    ``host_batch`` (``host_batch.order`` maps slots to the caller's tracks); ``labels`` (G,): the caller's label of every
+    group.  ``loglik`` (iterations + 1, G): the group's log-likelihood under every iterate, iterate 0 being the R the batch
+    came with, summed over the tracks that were usable under every iterate.  ``best_iter``, ``converged``, ``nobs`` (G,): the
+    winning iterate, whether the group's R settled within ``rtol`` before ``max_iter``, and the updates the group's last
+    M-step summed.  ``excluded``: slots left out of every sum (a NaN log-likelihood or an unusable status under some
+    iterate).  ``host_batch``: the batch with the fitted ``R_tracks``; ``device_batch``: the resident batch after a ``run()``
+    with them."""
+
+    R: np.ndarray
+    R_trace: np.ndarray
+    groups: np.ndarray
+    labels: np.ndarray
+    loglik: np.ndarray
+    best_iter: np.ndarray
+    converged: np.ndarray
+    nobs: np.ndarray
+    excluded: np.ndarray
+    host_batch: HostBatch
+    device_batch: "DeviceBatch"
+
+
+def _noise_fit_groups(hb: HostBatch, groups):
+    """``groups`` of ``fit_measurement_noise`` as (group of every slot (B,), the caller's label of every group (G,))."""
+    B = hb.B
+    order = np.arange(B) if hb.order is None else np.asarray(hb.order)
+    if groups is None:
+        return np.zeros(B, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    if isinstance(groups, str):
+        if groups != "track":
+            raise ValueError(f"groups must be None (one group), 'track' or an integer array ({B},), got {groups!r}")
+        return order.astype(np.int64), np.arange(B)
+    lab = np.asarray(groups)
+    if lab.shape != (B,) or lab.dtype.kind not in "iu":
+        raise ValueError(f"groups must be None (one group), 'track' or an integer array of one label per track, ({B},); got "
+                         f"shape {lab.shape}, dtype {lab.dtype}")
+    labels, index = np.unique(lab, return_inverse=True)
+    return index.reshape(B)[order].astype(np.int64), labels
+
+
+def _ordered_sum(x) -> float:
+    """x[0] + x[1] + ... in that order (np.sum adds pairwise)."""
+    return float(np.cumsum(np.asarray(x, dtype=np.float64))[-1]) if len(x) else 0.0
+
+
+def fit_measurement_noise(hb: HostBatch, groups=None, structure: str = "scalar", max_iter: int = 20, rtol: float = 1e-3,
+                          device="cuda:0") -> NoiseFit:
+    """
+    Fit the measurement noise R to the data by EM on the device ("Noise fit"), one R per group of tracks.
+
+    ``groups``: None (the whole batch is one group), ``"track"`` (every track its own) or an integer array (B,) of labels in
+    the caller's track order.  ``structure``: what R may be -- ``"scalar"`` r diag(1, 1, 0, 0), ``"diag2"``
+    diag(r0, r1, 0, 0) or ``"block2"`` a full leading 2 x 2 block.  Q, H and P0 stay the batch's.
+
+    Every iteration is an E-step (``log_likelihood`` + ``backward``: the smoothed track under the current R, and the
+    log-likelihood of that R), ``measurement_moments`` and ``update_measurement_noise``.  A group stops when the largest
+    relative change of the non-zero entries of its R falls below ``rtol`` (or its M-step fails); the loop ends when every
+    group has stopped or after ``max_iter`` M-steps, and one more E-step scores the last iterate.  EM with an unscented
+    smoother is not strictly monotone, so per group the iterate with the highest log-likelihood is returned, not the last
+    one; iterate 0 is the R the batch came with and can win.  The batch ends holding the histories of the returned R.
+
+    Raises ValueError, before the device is touched, for a robust batch (R is rescaled per update), for recorded noise, for
+    ``lanes=4`` (per-track noise has no quad kernel) and for an initial R outside the leading 2 x 2 block.
+    """
+    if hb.robust:
+        raise ValueError("fit_measurement_noise: a robust batch rescales R at every update; the M-step is not defined for it")
+    if hb.noise_pred is not None or hb.noise_upd is not None or hb.noise_rts is not None:
+        raise ValueError("fit_measurement_noise: recorded noise is refused (the residuals are taken from z, the update saw z + noise)")
+    if (default_lanes if hb.lanes is None else hb.lanes) == 4:
+        raise ValueError("fit_measurement_noise: per-track noise runs the lane-per-track mapping only, lanes=4 is refused")
+    if structure not in DeviceBatch._NOISE_STRUCTURES:
+        raise ValueError(f"structure must be one of {sorted(DeviceBatch._NOISE_STRUCTURES)}, got {structure!r}")
+    max_iter = int(max_iter)
+    if max_iter < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter!r}")
+    gslot, labels = _noise_fit_groups(hb, groups)
+    G, B = len(labels), hb.B
+    hbt = with_track_noise(hb, R=track_matrices(hb)[1])
+    R_start = hbt.R_tracks.copy()  # (10, B)
+    if not r_tracks_block2(R_start):
+        raise ValueError("fit_measurement_noise: the batch's R must be zero outside its leading 2 x 2 block (the structures "
+                         "the fit knows are confined to it)")
+    members = [np.flatnonzero(gslot == g).astype(np.int32) for g in range(G)]  # ascending slots: the order of every sum
+    first = np.array([m[0] if len(m) else 0 for m in members])
+
+    import torch
+
+    db = DeviceBatch(hbt, device=device)
+    active = np.array([len(m) > 0 for m in members])
+    converged = np.zeros(G, dtype=bool)
+    nobs = np.zeros(G, dtype=np.int64)
+    R_iter = [R_start[:, first]]  # iterate i as (10, G)
+    ll_tracks, ok_tracks = [], []
+
+    def e_step():
+        lk = db.log_likelihood()
+        db.backward()
+        ll_tracks.append(lk.loglik)
+        ok_tracks.append(np.isfinite(lk.loglik) & ((lk.status & binding.STE_STATUS_NAN) == 0))
+
+    for _ in range(max_iter):
+        e_step()
+        mom = db.measurement_moments()
+        bad = ~np.logical_and.reduce(ok_tracks)
+        if bad.any():  # a track some iterate could not score stays out of the moments too
+            idx = torch.from_numpy(np.flatnonzero(bad)).to(db.device)
+            mom["moments"][:, idx] = 0.0
+            mom["count"][idx] = 0
+        act = [members[g] if active[g] else members[g][:0] for g in range(G)]  # a stopped group has no members: its R stays
+        offsets = np.concatenate([[0], np.cumsum([len(m) for m in act])]).astype(np.int32)
+        res = db.update_measurement_noise(mom, groups=(offsets, np.concatenate(act)), structure=structure)
+        Rg, ng, gs = (res[k].cpu().numpy() for k in ("R_group", "n_group", "group_status"))
+        new = R_iter[-1].copy()
+        for g in np.flatnonzero(active):
+            if gs[g]:
+                active[g] = False  # nothing to fit from, or no usable variance: the group keeps the R it has
+                continue
+            old, new[:, g], nobs[g] = new[:, g].copy(), Rg[:, g], ng[g]
+            nz = Rg[:, g] != 0.0
+            if np.max(np.abs(Rg[nz, g] - old[nz]) / np.abs(Rg[nz, g])) < rtol:
+                active[g], converged[g] = False, True
+        R_iter.append(new)
+        if not active.any():
+            break
+    e_step()  # the last iterate's score
+
+    keep = np.logical_and.reduce(ok_tracks)
+    loglik = np.array([[_ordered_sum(ll[members[g]][keep[members[g]]]) for g in range(G)] for ll in ll_tracks])
+    best = np.argmax(np.where(np.isfinite(loglik), loglik, -np.inf), axis=0)
+    final = R_start.copy()
+    for g in range(G):
+        if best[g] > 0:
+            final[:, members[g]] = R_iter[best[g]][:, g:g + 1]
+    fitted = dataclasses.replace(hbt, R_tracks=final)
+    db.hb = fitted
+    db.t["R_tracks"].copy_(torch.from_numpy(final))
+    db.noise.flags |= binding.STE_NOISE_R_BLOCK2  # every iterate is confined to the block, the start was checked
+    db.run()
+    full = np.zeros((4, 4), dtype=np.intp)
+    full[_TRI] = np.arange(10)
+    full = np.maximum(full, full.T)
+    trace = np.stack(R_iter).transpose(0, 2, 1)[:, :, full]  # (iterations + 1, G, 4, 4)
+    return NoiseFit(R=trace[best, np.arange(G)], R_trace=trace, groups=gslot, labels=labels, loglik=loglik, best_iter=best,
+                    converged=converged, nobs=nobs, excluded=np.flatnonzero(~keep), host_batch=fitted, device_batch=db)
 
 
 def fleet_windows(ntracks: int, chunk: int):

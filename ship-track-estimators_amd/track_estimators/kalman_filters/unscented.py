@@ -14,6 +14,7 @@ attribute) to feed zeros instead.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import logging
 import types
 from typing import Callable, Optional
@@ -287,6 +288,19 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         if self._status_sampler & 0x1:
             raise np.linalg.LinAlgError("SVD did not converge")
         return samples[:, 0]
+
+    def fit_measurement_noise(self, structure: str = "scalar", max_iter: int = 20, rtol: float = 1e-3):
+        """The measurement noise R that fits the track ``run`` filtered, by EM on the device
+        (``track_estimators.batch.fit_measurement_noise``; no counterpart in the reference, where R is an argument).  The
+        track is packed as ``run`` packed it but without the noise ``run`` drew: the fit is that of the deterministic filter.
+        Returns ``(R (4, 4), loglik (iterations + 1,))``: the iterate with the highest log-likelihood and the trace, iterate 0
+        being this filter's own R, which is left as it is."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("fit_measurement_noise() fits the track of the last run(): call run() first")
+        hb = dataclasses.replace(hb, noise_pred=None, noise_upd=None, noise_rts=None)
+        fit = _batch.fit_measurement_noise(hb, structure=structure, max_iter=max_iter, rtol=rtol)
+        return fit.R[0], fit.loglik[:, 0]
 
     def distance_sailed(self, n_samples: int = 0, random_state: int = 0, model: str = "sphere"):
         """Distance in km along the track ``run`` filtered (``track_estimators.batch.path_statistics``; no counterpart in the
