@@ -47,6 +47,9 @@
  *   ste_ukf_noise_moments_f64 / ste_ukf_noise_mstep_f64   the measurement noise R of a track or a group of tracks fitted to the
  *                            data by EM, from the smoothed marginals on the device (no counterpart in the reference, where R is
  *                            an argument of UnscentedKalmanFilter, unscented.py:55-61)
+ *   ste_field_values_f64     the values of a space-time gridded field (SST, pressure, wind, ice) where such tracks were at given
+ *                            clock times, trilinear with no-data handling or nearest-node, and their count, moments and extremes
+ *                            over the samples (no counterpart in the reference: a download of S x Q positions and a host loop)
  *
  * Conventions
  *   - plain C, no torch / HIP types in signatures; `stream` is a hipStream_t passed as void* (NULL = default stream).
@@ -92,7 +95,9 @@ extern "C" {
                            tracks on the device (ste_raster_metrics_f64).  Unnumbered addition: observation preparation with
                            SOG / COG smoothed first (ste_track_prep_smooth_f64).  Unnumbered addition: tracks on the device
                            simplified within a tolerance (ste_track_simplify_f64).  Unnumbered addition: measurement noise fitted
-                           by EM on the device (ste_ukf_noise_moments_f64, ste_ukf_noise_mstep_f64).
+                           by EM on the device (ste_ukf_noise_moments_f64, ste_ukf_noise_mstep_f64).  Unnumbered addition: the
+                           values of a space-time gridded field where tracks on the device were at given clock times
+                           (ste_field_values_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1355,6 +1360,92 @@ typedef struct ste_noise_mstep_f64 {
 } ste_noise_mstep_f64;            /* 96 bytes */
 
 int ste_ukf_noise_mstep_f64(const ste_noise_mstep_f64* ms, void* stream);
+
+/*
+ * FIELDS: the values of a SPACE-TIME GRIDDED FIELD (SST, pressure, wind, ice: [nt][ny][nx]) where tracks that stay on the
+ * device were AT GIVEN CLOCK TIMES (an unnumbered addition, like ste_positions_f64): per (sample, query) the position of
+ * POSITIONS is formed and the field is read there, trilinear in (time, lat, lon) with no-data handling or at the nearest node,
+ * and the count, the moments and the extremes of the value OVER THE SAMPLES about an anchor are continued from call to call.
+ * `states`, `nqueries`, `qtrack`, `qtime` and `t0` are those of ste_positions_f64.  wrap180, clamp01 and % are those of
+ * POSITIONS, floor is the floor of a double, and every expression is evaluated as written, left to right, without contraction and
+ * without transcendentals: the library and a NumPy restatement agree bit for bit.
+ *   - Knots.  `knots` is what a previous ste_track_positions_f64 on this batch left in its workspace ([Nmax+1][track_stride]);
+ *     it is read only, and this call never reads b->dt.  knots[0][t] = NaN marks a bad clock, as there.
+ *   - Locate.  POSITIONS word for word: Bad index, Bad time, Locate, Knot hit, Interior and the BROKEN step, which give (lon, lat)
+ *     per sample -- wrap180(lon_j), lat_j on a knot hit; wrap180(lon_k + u * delta), lat_k + u * (lat_{k+1} - lat_k) inside a
+ *     sound step; NaN, NaN inside a broken one -- and the STE_POS_* bits of status[q] with their meaning.  A query that is not
+ *     located gives NaN in value and cover of every sample and adds nothing to any accumulator.
+ *   - Time, with tq = qtime[q].  Slab j of the field is valid at time0 + j * dtime.  With nt == 1 the field is static: it0 = it1 =
+ *     0, ft = 0, and time is never outside.  Otherwise gt = (tq - time0) / dtime, and a located query for which
+ *     gt >= 0 && gt <= nt - 1 is false gets STE_FLD_TIME_OUTSIDE: value and cover of every sample are NaN and nothing is
+ *     counted; there is no extrapolation in time.  it = floor(gt); if it >= nt - 1 then it0 = it1 = nt - 1 and ft = 0, otherwise
+ *     it0 = it, it1 = it + 1 and ft = gt - it.
+ *   - Space.  Values sit at CELL CENTRES of the grid of ste_grid_f64 (GRIDS: Grid.): node (ix, iy) of slab j lies at
+ *     (lon0 + (ix + 0.5) dlon, lat0 + (iy + 0.5) dlat) and is stored at values[(j * ny + iy) * nx + ix].  x = lon_ref +
+ *     wrap180(lon - lon_ref), gx = (x - lon0) / dlon, gy = (lat - lat0) / dlat.  A sample whose lon or lat is not finite counts
+ *     NOWHERE: value and cover are NaN.  A finite sample is ON THE GRID by the raster's cell test, 0 <= gy < ny and without
+ *     STE_GRID_PERIODIC_LON also 0 <= gx < nx; a finite sample OFF THE GRID gives value NaN and cover 0 and adds 1 to count[2].
+ *     On the grid hx = gx - 0.5, ix = floor(hx), fx = hx - ix.  Not periodic: ix < 0 puts both columns at 0 with fx = 0, and
+ *     ix >= nx - 1 puts both at nx - 1 with fx = 0 (the outer half cell is a constant continuation).  Periodic: the columns are
+ *     ix and ix + 1 modulo nx (floored).  Rows: hy = gy - 0.5, iy = floor(hy), fy = hy - iy, always by the non-periodic rule.
+ *   - Value.  Corner c = 4 e + 2 b + a (e: slab it0 / it1, b: row, a: column) has the weight w = (wt_e * wy_b) * wx_a with
+ *     wx_0 = 1 - fx, wx_1 = fx, wy_0 = 1 - fy, wy_1 = fy, wt_0 = 1 - ft, wt_1 = ft.  A corner with w == 0, or whose value is NaN, is
+ *     skipped; for the others, in corner order from num = den = 0.0: num = num + w * v, den = den + w.  cover = den, and
+ *     value = (den > 0 && den >= min_cover) ? num / den : NaN.  +-inf are values.  A sample on the grid whose value comes out NaN
+ *     adds 1 to count[1].  A float field (STE_FLD_VALUES_F32) is converted to double, exactly, when it is read.
+ *   - Nearest.  With STE_FLD_NEAREST the value is that of one node: the node of the cell (floor gx, floor gy) the sample lies in
+ *     (the column modulo nx where periodic), exactly the cell of ste_raster_f64's row_value, in slab min(floor(gt + 0.5), nt - 1)
+ *     (slab 0 when nt == 1).  cover is 1, or 0 where the node is NaN; min_cover is not consulted.
+ *   - Moments.  For query q, for s = 0 .. S - 1 in order: if value is finite and d = value - vanchor[q] is finite, then
+ *     count[0][q] += 1, moments[0][q] += d, moments[1][q] += d * d, if (!(vmin[q] <= value)) vmin[q] = value and
+ *     if (!(vmax[q] >= value)) vmax[q] = value.  count, moments, vmin and vmax START FROM THE STORED VALUES and are stored once
+ *     at the end: the caller zeroes the sums and puts NaN into vmin and vmax before the first call, and a call with S samples
+ *     equals a call with the first S1 and a call with the other S - S1 on the same accumulators, bit for bit.
+ *   - Every value's bits depend on its own track's rows, the knots, t0, the query, the field and (the accumulators) the stored
+ *     values alone: not on Q, the place of the query in the list, S, the window, or which outputs were asked for.
+ *   - The call reads only B, Nmax, track_stride and nsteps (NULL = Nmax for every track) of the batch and writes nothing of it;
+ *     windows and addressing are those of ste_track_positions_f64.  Rows past nsteps[t] of states are not read.  Outputs per
+ *     sample are out[s * Q + q]; count is [3][Q] (valid, nodata, off) and moments [2][Q].
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or f NULL; B <= 0, Nmax < 0, or track_stride
+ *     non-zero and below B; states, qtrack, qtime, knots or values NULL; nstates < 1 or > 65535; nqueries < 1 or >
+ *     STE_POSITIONS_MAX_QUERIES; unknown flag bits; the reserved word not 0; the grid refusals of ste_grid_metrics_f64 (nx, ny,
+ *     the cells, lon0, lat0, lon_ref, dlon, dlat, the periodic and the non-periodic condition); nt < 1 or > STE_FIELD_MAX_SLABS;
+ *     a non-finite time0; dtime not finite or <= 0 when nt > 1; min_cover not in [0, 1]; any of count, moments, vmin, vmax without
+ *     vanchor; every output NULL.
+ */
+#define STE_FIELD_MAX_SLABS 65536
+#define STE_FLD_NEAREST 0x2u       /* the value of the nearest node instead of the trilinear one */
+#define STE_FLD_VALUES_F32 0x4u    /* `values` is float[nt][ny][nx] instead of double */
+#define STE_FLD_TIME_OUTSIDE 0x8   /* status: the query is located but its time lies off the field's time axis */
+typedef struct ste_field_f64 {
+    int32_t nstates;        /* S >= 1 tracks per ship in `states` (<= 65535) */
+    uint32_t flags;         /* STE_GRID_PERIODIC_LON | STE_FLD_NEAREST | STE_FLD_VALUES_F32; unknown bits refused */
+    const double* states;   /* DEVICE [S][Nmax+1][4][track_stride], as ste_positions_f64 */
+    int64_t nqueries;       /* Q, 1 .. STE_POSITIONS_MAX_QUERIES */
+    const int32_t* qtrack;  /* DEVICE [Q]: track of the window, 0 <= t < B */
+    const double* qtime;    /* DEVICE [Q]: clock time, hours */
+    const double* t0;       /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track */
+    const double* knots;    /* DEVICE [Nmax+1][track_stride], read only: what ste_track_positions_f64 left there */
+    int32_t nx, ny;         /* columns (lon) and rows (lat), >= 1, nx * ny <= STE_GRID_MAX_CELLS */
+    int32_t nt;             /* slabs, 1 .. STE_FIELD_MAX_SLABS; 1 = a static field */
+    uint32_t reserved;      /* must be 0 */
+    double lon0, lat0;      /* HOST: west and south edge of cell (0, 0), degrees, as ste_grid_f64 */
+    double dlon, dlat;      /* HOST: cell size, finite, >= 1e-6 */
+    double lon_ref;         /* HOST: meridian the longitudes are unwrapped about */
+    double time0, dtime;    /* HOST: slab j is valid at time0 + j * dtime hours on the queries' clock; dtime > 0 when nt > 1 */
+    double min_cover;       /* HOST: in [0, 1]: the least weight of valid corners a value needs */
+    const void* values;     /* DEVICE [nt][ny][nx]: double, or float with STE_FLD_VALUES_F32; NaN = no data */
+    const double* vanchor;  /* DEVICE [Q]: required with count, moments, vmin or vmax */
+    double* value;          /* DEVICE [S][Q] or NULL */
+    double* cover;          /* DEVICE [S][Q] or NULL: the weight of the valid corners, 0 off the grid */
+    int32_t* status;        /* DEVICE [Q] or NULL: STE_POS_* bits and STE_FLD_TIME_OUTSIDE */
+    int32_t* count;         /* DEVICE [3][Q], ACCUMULATED (+=), or NULL: samples that are valid, nodata, off the grid */
+    double* moments;        /* DEVICE [2][Q], ACCUMULATED, or NULL: sums of d and d * d, d = value - vanchor */
+    double* vmin;           /* DEVICE [Q], continued from the stored value (NaN = none yet), or NULL */
+    double* vmax;           /* DEVICE [Q], continued likewise, or NULL */
+} ste_field_f64;            /* 208 bytes */
+
+int ste_field_values_f64(const ste_ukf_batch_f64* b, const ste_field_f64* f, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

@@ -293,6 +293,49 @@ class StePositionsF64(C.Structure):
     ]
 
 
+STE_FIELD_MAX_SLABS = 65536
+STE_FLD_NEAREST = 0x2
+STE_FLD_VALUES_F32 = 0x4
+STE_FLD_TIME_OUTSIDE = 0x8
+
+
+class SteFieldF64(C.Structure):
+    """Mirror of ``struct ste_field_f64`` (include/ste.h): a space-time gridded field where tracks on the device were at given
+    clock times."""
+
+    _fields_ = [
+        ("nstates", C.c_int32),
+        ("flags", C.c_uint32),
+        ("states", _dp),
+        ("nqueries", C.c_int64),
+        ("qtrack", _dp),
+        ("qtime", _dp),
+        ("t0", _dp),
+        ("knots", _dp),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("nt", C.c_int32),
+        ("reserved", C.c_uint32),
+        ("lon0", C.c_double),
+        ("lat0", C.c_double),
+        ("dlon", C.c_double),
+        ("dlat", C.c_double),
+        ("lon_ref", C.c_double),
+        ("time0", C.c_double),
+        ("dtime", C.c_double),
+        ("min_cover", C.c_double),
+        ("values", _dp),
+        ("vanchor", _dp),
+        ("value", _dp),
+        ("cover", _dp),
+        ("status", _dp),
+        ("count", _dp),
+        ("moments", _dp),
+        ("vmin", _dp),
+        ("vmax", _dp),
+    ]
+
+
 STE_SITES_MAX = 65536
 STE_SITE_BAD_TIME = 0x1
 STE_SITE_BAD_SITE = 0x1
@@ -677,6 +720,7 @@ SYMBOLS = {
     "ste_track_simplify_lds_rows": (C.c_int, []),
     "ste_ukf_noise_moments_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteNoiseMomentsF64), C.c_void_p]),
     "ste_ukf_noise_mstep_f64": (C.c_int, [C.POINTER(SteNoiseMstepF64), C.c_void_p]),
+    "ste_field_values_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteFieldF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -1305,6 +1305,152 @@ class DeviceBatch:
             out["knots"] = kn
             return self._finish(st, keep, out)
 
+    # -- a space-time gridded field at query times ----------------------------------------------------------------
+    def track_knots(self, stream=None):
+        """The knot times of this batch's tracks, (Nmax+1, B) on the device: the in-order sums of ``dt`` that
+        ``positions_at`` returns as ``knots``, from one positions call with a single query that reads no track (its index is
+        -1) and ``status`` as the only output.  Row 0 holds 0, or NaN for a track with a ``dt`` that is not finite and >= 0;
+        rows past ``nsteps[b]`` are NaN.  ``field_at`` and ``positions_at`` take it as ``knots=``."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        ld = int(self.struct.track_stride or self.struct.B)
+        st = self._ordered_stream(stream)
+        with torch.cuda.stream(st):
+            s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
+            ws = torch.full((N + 1, ld), float("nan"), dtype=torch.float64, device=self.device)
+            qt = torch.full((1,), -1, dtype=torch.int32, device=self.device)
+            tq = torch.zeros((1,), dtype=torch.float64, device=self.device)  # also stands in for `states`: nothing reads it
+            status = torch.empty((1,), dtype=torch.int32, device=self.device)
+            po = binding.StePositionsF64()
+            po.nstates, po.flags, po.states = 1, 0, tq.data_ptr()
+            po.nqueries, po.qtrack, po.qtime = 1, qt.data_ptr(), tq.data_ptr()
+            po.knots, po.status = ws.data_ptr() + 8 * self.lo, status.data_ptr()
+            binding.check(self.lib.ste_track_positions_f64(C.byref(s), C.byref(po), self._stream(st)), "ste_track_positions_f64")
+            return self._finish(st, [ws, qt, tq, status], {"knots": ws[:, self.lo:self.lo + B]})["knots"]
+
+    def field_at(self, states, field, qtrack, qtime, t0=None, nearest: bool = False, min_cover: float = 0.0, vanchor=None,
+                 accumulate=None, knots=None, per_sample: bool = True, stream=None, sort: bool = True):
+        """The values of a space-time gridded field where tracks that are on the device were at given clock times
+        (include/ste.h: ste_field_values_f64; DESIGN.md, "Fields").  ``states``, ``qtrack``, ``qtime``, ``t0``, ``sort`` and
+        ``stream`` as in ``positions_at``; ``field`` a ``TrackField`` (``track_field`` makes one) on this batch's device.  Per
+        (sample, query) the position of ``positions_at`` is formed and the field is read there: trilinear in (time, lat, lon)
+        between the nodes at the cell centres, NaN nodes left out and the weights of the others renormalised, the value NaN
+        where their weight ``cover`` is 0 or below ``min_cover``; with ``nearest`` the value of the node of the cell the
+        position lies in, in the slab nearest in time (categorical fields).  Nothing is extrapolated in time: a located query
+        off the field's time axis has STE_FLD_TIME_OUTSIDE in ``status`` and NaN values.  ``knots``: the tensor
+        ``track_knots()`` or a previous call returned; None sums them once more.  Returns a dict of device tensors: with
+        ``per_sample`` ``value`` and ``cover`` (S, Q); ``status`` (Q,) int32; ``knots``.  With ``vanchor``, a (Q,) array or
+        tensor, also ``count`` (3, Q) int32 -- the samples with a finite value, those on the grid without one, those off the
+        grid --, ``moments`` (2, Q), the sums over the samples of d and d d, d = value - vanchor, and ``vmin``, ``vmax`` (Q,),
+        NaN where no sample has a value.  They start from zero and NaN, or with ``accumulate=(count, moments, vmin, vmax)``
+        from those tensors, which are updated in place and returned: S samples in one call and the same samples in several
+        calls give the same bits."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        states, S = self._metric_states(states)
+        if not isinstance(field, TrackField):
+            raise ValueError("field must be a TrackField (track_estimators.batch.track_field makes one)")
+        if field.values.device != self.device:
+            raise ValueError(f"the field's values are on {field.values.device}, this batch is on {self.device}")
+        min_cover = float(min_cover)
+        if not 0.0 <= min_cover <= 1.0:
+            raise ValueError(f"min_cover must lie in [0, 1], got {min_cover!r}")
+        qtrack = _index_tensor(qtrack, "qtrack", (), binding.STE_POSITIONS_MAX_QUERIES)
+        Q = int(qtrack.shape[0])
+        qtime = torch.as_tensor(qtime, dtype=torch.float64)
+        if tuple(qtime.shape) != (Q,):
+            raise ValueError(f"qtime must have shape ({Q},) like qtrack, got {tuple(qtime.shape)}")
+        if vanchor is not None:
+            vanchor = torch.as_tensor(vanchor, dtype=torch.float64)
+            if tuple(vanchor.shape) != (Q,):
+                raise ValueError(f"vanchor must have shape ({Q},): one value per query, got {tuple(vanchor.shape)}")
+        acc_shapes = (("count", torch.int32, (3, Q)), ("moments", torch.float64, (2, Q)), ("vmin", torch.float64, (Q,)),
+                      ("vmax", torch.float64, (Q,)))
+        if accumulate is not None:
+            if vanchor is None:
+                raise ValueError("accumulate continues the moments about an anchor: give the vanchor they were started with")
+            ok = len(accumulate) == 4 and all(isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == dt
+                                              and tuple(a.shape) == shape for a, (_, dt, shape) in zip(accumulate, acc_shapes))
+            if not ok:
+                raise ValueError(f"accumulate must be (count, moments, vmin, vmax): an int32 (3, {Q}), a float64 (2, {Q}) and two "
+                                 f"float64 ({Q},) tensors on {self.device}")
+        if knots is not None and not (isinstance(knots, torch.Tensor) and knots.dtype == torch.float64 and knots.device == self.device
+                                      and tuple(knots.shape) == (N + 1, B)):
+            raise ValueError(f"knots must be the float64 ({N + 1}, {B}) tensor a previous call on this batch returned")
+        if knots is None:
+            knots = self.track_knots(stream=stream)
+        grid = field.grid
+        st = self._ordered_stream(stream)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            qt = _index_int32(qtrack.to(self.device))
+            tq = qtime.to(self.device).contiguous()
+            perm = None
+            if sort and Q > 1:
+                by_time = torch.sort(tq, stable=True).indices
+                perm = by_time[torch.sort(qt[by_time], stable=True).indices]
+                qt, tq = qt[perm].contiguous(), tq[perm].contiguous()
+            keep = [qt, tq, field.values]
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=False)  # the knots stand in for dt
+            f = binding.SteFieldF64()
+            f.nstates, f.states = S, states.data_ptr()
+            f.flags = ((binding.STE_GRID_PERIODIC_LON if grid.periodic else 0) | (binding.STE_FLD_NEAREST if nearest else 0)
+                       | (binding.STE_FLD_VALUES_F32 if field.values.dtype == torch.float32 else 0))
+            f.nqueries, f.qtrack, f.qtime = Q, qt.data_ptr(), tq.data_ptr()
+            f.t0 = self._track_clock(t0, width, col, keep)
+            if knots.stride() == (width, 1):
+                kn = knots  # the view a call on this layout returned: read where it lies
+                f.knots = kn.data_ptr()
+            else:
+                ws = torch.empty((N + 1, width), **f64)
+                kn = ws[:, col:col + B]
+                kn.copy_(knots)
+                f.knots = ws.data_ptr() + 8 * col
+                keep.append(ws)
+            keep.append(kn)
+            f.nx, f.ny, f.nt, f.reserved = grid.nx, grid.ny, field.nt, 0
+            f.lon0, f.lat0, f.dlon, f.dlat, f.lon_ref = grid.lon0, grid.lat0, grid.dlon, grid.dlat, grid.lon_ref
+            f.time0, f.dtime, f.min_cover = field.time0, field.dtime, min_cover
+            f.values = field.values.data_ptr()
+            out = {k: torch.empty((S, Q), **f64) for k in (("value", "cover") if per_sample else ())}
+            out["status"] = torch.empty((Q,), **i32)
+            for k, ten in out.items():
+                setattr(f, k, ten.data_ptr())
+            acc = None
+            if vanchor is not None:
+                an = vanchor.to(self.device)
+                an = (an if perm is None else an[perm]).contiguous()
+                if accumulate is None:
+                    acc = [torch.zeros((3, Q), **i32), torch.zeros((2, Q), **f64), torch.full((Q,), float("nan"), **f64),
+                           torch.full((Q,), float("nan"), **f64)]
+                elif perm is None:
+                    acc = [a.contiguous() for a in accumulate]
+                else:
+                    acc = [a[..., perm].contiguous() for a in accumulate]
+                f.vanchor = an.data_ptr()
+                for (k, _, _), a in zip(acc_shapes, acc):
+                    setattr(f, k, a.data_ptr())
+                keep += [an] + acc
+            binding.check(self.lib.ste_field_values_f64(C.byref(s), C.byref(f), self._stream(st)), "ste_field_values_f64")
+            if perm is not None:  # back to the caller's order
+                inv = torch.empty_like(perm)
+                inv[perm] = torch.arange(Q, device=self.device)
+                out = {k: v[..., inv].contiguous() for k, v in out.items()}
+                if acc is not None:
+                    acc = [a[..., inv].contiguous() for a in acc]
+                keep += [perm, inv]
+            if acc is not None:
+                if accumulate is not None:
+                    for a, given in zip(acc, accumulate):
+                        if a.data_ptr() != given.data_ptr():
+                            given.copy_(a)
+                    acc = list(accumulate)
+                for (k, _, _), a in zip(acc_shapes, acc):
+                    out[k] = a
+            out["knots"] = kn
+            return self._finish(st, keep, out)
+
     # -- fixed sites ----------------------------------------------------------------------------------------------
     _SITE_OUT3 = ("min_dist", "min_time", "time_within", "first_within", "longest")
 
@@ -3363,6 +3509,58 @@ def track_raster(grid: TrackGrid, values, device="cuda:0") -> TrackRaster:
     return TrackRaster(grid=grid, values=ten)
 
 
+@dataclasses.dataclass(frozen=True)
+class TrackField:
+    """A space-time gridded field as ``ste_field_values_f64`` wants it (``track_field`` makes one): ``grid``, a ``TrackGrid``
+    whose cell centres are the field's nodes; ``values``, a contiguous float64 or float32 device tensor (nt, ny, nx), NaN = no
+    data; slab j is valid at ``time0 + j * dtime`` hours on the clock of the queries."""
+
+    grid: TrackGrid
+    values: object
+    time0: float
+    dtime: float
+
+    @property
+    def nt(self) -> int:
+        return int(self.values.shape[0])
+
+
+def track_field(grid: TrackGrid, values, time0: float = 0.0, dtime: float = 1.0, device="cuda:0") -> TrackField:
+    """A field on ``grid`` for ``DeviceBatch.field_at``: ``values`` (ny, nx), a static field, or (nt, ny, nx), an array or a
+    tensor, one value per cell centre, row iy at latitude lat0 + (iy + 0.5) dlat, slab j valid at ``time0 + j * dtime`` hours,
+    NaN = no data.  float32 stays float32 (half the bytes of every read); every other real, integer or bool dtype becomes
+    float64.  A contiguous tensor of one of the two types that already is on a GPU is used where it lies.  ``ValueError``:
+    ``grid`` is no ``TrackGrid``; a shape other than those two; more than 65536 slabs; a dtype that is not real; a non-finite
+    ``time0``; ``dtime`` not finite or <= 0 with more than one slab."""
+    import torch
+
+    if not isinstance(grid, TrackGrid):
+        raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
+    if isinstance(values, torch.Tensor):
+        ten = values
+        if ten.is_complex():
+            raise ValueError(f"a field's values must be real numbers, got a tensor of {ten.dtype}")
+    else:
+        a = np.asarray(values)
+        if a.dtype.kind not in "fiub":
+            raise ValueError(f"a field's values must be real numbers, got an array of dtype {a.dtype}")
+        ten = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+    if ten.dim() == 2:
+        ten = ten.unsqueeze(0)
+    if ten.dim() != 3 or tuple(ten.shape[1:]) != (grid.ny, grid.nx) or not 1 <= ten.shape[0] <= binding.STE_FIELD_MAX_SLABS:
+        raise ValueError(f"a field's values must have shape (ny, nx) = ({grid.ny}, {grid.nx}) or (nt, ny, nx) with 1 <= nt <= "
+                         f"{binding.STE_FIELD_MAX_SLABS}, got {tuple(ten.shape)}")
+    time0, dtime = float(time0), float(dtime)
+    if not np.isfinite(time0):
+        raise ValueError(f"time0 must be finite, got {time0!r}")
+    if ten.shape[0] > 1 and not (np.isfinite(dtime) and dtime > 0.0):
+        raise ValueError(f"dtime must be finite and > 0 for a field of more than one slab, got {dtime!r}")
+    dtype = torch.float32 if ten.dtype == torch.float32 else torch.float64
+    if not (ten.is_cuda and ten.dtype == dtype and ten.is_contiguous()):
+        ten = ten.to(device=ten.device if ten.is_cuda else device, dtype=dtype).contiguous()
+    return TrackField(grid=grid, values=ten, time0=time0, dtime=dtime)
+
+
 def _raster_threshold(threshold, below, min_hours):
     """(flags, threshold, min_ticks) of ``ste_raster_f64`` for the arguments of ``raster_metrics``."""
     min_hours = float(min_hours)
@@ -4194,6 +4392,57 @@ def position_statistics(hb_or_db, qtrack, qtime, nsamples: int, seed: int = 0, c
     out.update(position_ellipse(count, moments, out["lat"], prob))
     out["sample_status"] = status.cpu().numpy()
     return out
+
+
+def field_statistics(hb_or_db, field: "TrackField", qtrack, qtime, nsamples: int, seed: int = 0, chunk: int = 16, t0=None,
+                     nearest: bool = False, min_cover: float = 0.0, device="cuda:0"):
+    """The value of a space-time gridded field at given clock times with the uncertainty of the smoothing posterior, per query
+    (an observation hour of a ship): ``nsamples`` posterior tracks are drawn (``DeviceBatch.sample_smoothed``), the field is
+    read where each was (``DeviceBatch.field_at``) and they are discarded, ``chunk`` samples at a time, with the generator
+    discipline of ``position_statistics``: the draws depend on ``(seed, chunk)`` and with ``chunk >= nsamples`` they are those
+    of ``sample_smoothed(nsamples, seed)``.  Only the counts, the two moments and the extremes per query survive a chunk,
+    continued on the device with the bits of one pass: no (nsamples, Q) array exists anywhere and memory is of order Q.  The
+    anchor of the moments is the value at the smoothed track, ``field_at(db.sm_mean, ...)``, 0.0 where that is NaN; the knot
+    times are summed once and the queries sorted once.  Given a ``HostBatch`` it uploads it and runs the forward pass and the
+    smoother first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``field``, ``qtrack``,
+    ``qtime``, ``t0``, ``nearest`` and ``min_cover`` as in ``field_at``.
+
+    Returns a dict of NumPy arrays per query: ``anchor``, the value at the smoothed track (NaN where it has none); ``mean`` and
+    ``std`` (ddof 1, NaN below two) of the samples' values; ``min``, ``max``; ``n``, the samples with a value; ``p_nodata`` and
+    ``p_off``, the shares of the samples on the grid without a value and off the grid; ``status``, the STE_POS_* bits and
+    STE_FLD_TIME_OUTSIDE; and ``sample_status`` (B,), the sampler's STE_STATUS_* bits per track."""
+    db, nsamples, chunk = _posterior_batch(hb_or_db, nsamples, chunk, device, "field_statistics")
+    torch = db.torch
+    knots = db.track_knots()
+    kw = dict(t0=t0, nearest=nearest, min_cover=min_cover, knots=knots)
+    smoothed = db.field_at(db.sm_mean, field, qtrack, qtime, **kw)
+    Q = int(smoothed["status"].shape[0])
+    # the kernel's order once, for every chunk: by (track, time)
+    qt = torch.as_tensor(np.asarray(qtrack) if not isinstance(qtrack, torch.Tensor) else qtrack).to(db.device)
+    tq = torch.as_tensor(qtime, dtype=torch.float64).to(db.device)
+    by_time = torch.sort(tq, stable=True).indices
+    perm = by_time[torch.sort(qt[by_time], stable=True).indices]
+    qt, tq = qt[perm], tq[perm]
+    anchor = smoothed["value"][0]
+    vanchor = torch.where(torch.isnan(anchor), torch.zeros_like(anchor), anchor)[perm].contiguous()
+    f64 = dict(dtype=torch.float64, device=db.device)
+    acc = (torch.zeros((3, Q), dtype=torch.int32, device=db.device), torch.zeros((2, Q), **f64),
+           torch.full((Q,), float("nan"), **f64), torch.full((Q,), float("nan"), **f64))
+    chunks = _PosteriorChunks(db, nsamples, seed, chunk)
+    for _, _, samples in chunks:
+        db.field_at(samples, field, qt, tq, vanchor=vanchor, accumulate=acc, per_sample=False, sort=False, **kw)
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(Q, device=db.device)
+    count, moments, vmin, vmax = (a[..., inv].cpu().numpy() for a in acc)
+    van = vanchor[inv].cpu().numpy()
+    n = count[0].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        md = moments[0] / n
+        var = (moments[1] - moments[0] * md) / np.where(n >= 2, n - 1.0, np.nan)
+        std = np.sqrt(np.maximum(var, 0.0))
+    return {"anchor": anchor.cpu().numpy(), "mean": van + md, "std": std, "min": vmin, "max": vmax, "n": count[0],
+            "p_nodata": count[1] / float(nsamples), "p_off": count[2] / float(nsamples), "status": smoothed["status"].cpu().numpy(),
+            "sample_status": chunks.status.cpu().numpy()}
 
 
 @dataclasses.dataclass

@@ -463,6 +463,39 @@ class UnscentedKalmanFilter(KalmanFilterBase):
                                         "orientation_deg")})
         return res
 
+    def field_at(self, field, times, n_samples: int = 0, random_state: int = 0):
+        """The value of a space-time gridded field where the track ``run`` filtered was at ``times``, hours from its first
+        row (``DeviceBatch.field_at`` and ``track_estimators.batch.field_statistics``; no counterpart in the reference).
+        ``field``: a ``track_estimators.batch.TrackField`` whose time axis runs on the same clock.  ``n_samples == 0``: a
+        ``(len(times),)`` array, the field at the smoothed track, trilinear, NaN where the track or the field has nothing.
+        Otherwise the dict of ``field_statistics`` from that many tracks drawn from the joint smoothing posterior, those of
+        ``sample_smoothed(n_samples, random_state)``: ``anchor`` (that array), ``mean``, ``std``, ``min``, ``max``, ``n``,
+        ``p_nodata``, ``p_off``, ``status``.  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        hb = getattr(self, "_sample_hb", None)
+        if hb is None:
+            raise RuntimeError("field_at() reads the track of the last run(): call run() first")
+        if len(self.means) != hb.Nmax + 1:
+            raise NotImplementedError("field_at() covers a history filtered by ONE run() call; this filter has "
+                                      f"{len(self.means)} stored rows and its last run() made {hb.Nmax + 1}")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples must be >= 0, got {n_samples!r}")
+        times = np.atleast_1d(np.asarray(times, dtype=np.float64))
+        if times.ndim != 1 or times.size < 1:
+            raise ValueError(f"times must be a scalar or a one-dimensional array of hours, got shape {times.shape}")
+        track = np.zeros(times.size, dtype=np.int32)
+        if n_samples == 0:
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            return db.field_at(db.sm_mean, field, track, times)["value"][0].cpu().numpy()
+        out = _batch.field_statistics(hb, field, track, times, n_samples, seed=int(random_state), chunk=n_samples)
+        self._status_sampler = int(out.pop("sample_status")[0])
+        if self._status_sampler & 0x1:
+            raise np.linalg.LinAlgError("SVD did not converge")
+        return out
+
     def site_visits(self, sites, radius_km, nsamples: int = 0, min_stay_h: float = 0.0, model: str = "sphere",
                     random_state: int = 0):
         """The track ``run`` filtered against fixed sites -- ports, anchorages, buoys -- (``DeviceBatch.site_metrics`` and
