@@ -97,7 +97,8 @@ extern "C" {
                            simplified within a tolerance (ste_track_simplify_f64).  Unnumbered addition: measurement noise fitted
                            by EM on the device (ste_ukf_noise_moments_f64, ste_ukf_noise_mstep_f64).  Unnumbered addition: the
                            values of a space-time gridded field where tracks on the device were at given clock times
-                           (ste_field_values_f64).
+                           (ste_field_values_f64).  Unnumbered addition: the lag-one cross-covariance of the smoother and the
+                           exact covariance of a position at a query time (ste_urtss_lag_one_f64, ste_track_position_cov_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -1446,6 +1447,91 @@ typedef struct ste_field_f64 {
 } ste_field_f64;            /* 208 bytes */
 
 int ste_field_values_f64(const ste_ukf_batch_f64* b, const ste_field_f64* f, void* stream);
+
+/*
+ * LAG-ONE COVARIANCE of the unscented smoother (an unnumbered addition, like ste_ukf_sample_f64).  sm_mean / sm_cov are the
+ * marginals of every row; what two NEIGHBOURING rows have in common is the third output of an RTS smoother (Shumway-Stoffer):
+ *      L_k = Cov(x_k, x_{k+1} | all data) = K_k P^s_{k+1},      k = 0 .. nsteps - 1
+ * with K_k = D pinv(P_b) the gain of step k exactly as the smoother forms it and P^s_{k+1} row k + 1 of sm_cov.  Under the
+ * sampler's recursion x_k = (m_k + K y) + T xi this is the cross-covariance of rows k and k + 1 of the sampled tracks.  The
+ * product is formed entry by entry, L[r][c]: acc = K[r][0] * P[0][c]; acc = fma(K[r][i], P[i][c], acc) for i = 1, 2, 3, with
+ * P[i][c] read from the upper triangle of the stored row; nothing else is contracted.
+ *   - lag1: entry 4 r + c of row k holds L_k[r][c] (L is not symmetric: all 16).  With STE_LAG1_POSITION a row has 4 entries,
+ *     L[0][0], L[0][1], L[1][0], L[1][1] -- all the covariance of a position needs, a quarter of the memory -- with the bits of the
+ *     same entries of the full form.  Rows k >= nsteps[t] are left as they were.
+ *   - Precondition: a completed forward pass of this batch WITH rts_work, and a completed smoother (sm_cov holds the smoothed
+ *     covariances), in either of its forms.  The call only reads the batch: rts_work, the histories and b->status are not written.
+ *     nz: the per-track Q the forward pass ran with (NULL, or nz->Q NULL: the shared b->Q); nz->R and nz->flags are not read.
+ *   - Ordering: the call reads rts_work.  A two-kernel smoother (ste_urtss_backward_f64 on a small batch) REWRITES the work rows
+ *     into gains; when it runs on another stream the caller orders this call before or after it, never beside it -- and after
+ *     whatever writes sm_cov.
+ *   - Windows: track_stride works like for every other per-track array -- lag1 has rows of track_stride tracks and the pointer
+ *     names the window's first track; status is [B] and points at the window's first entry.
+ *   - Refused with STE_EINVAL and a message before any launch: b, lg or lg->lag1 NULL; unknown flag bits; reserved != 0; rts_work,
+ *     fwd_mean or fwd_cov NULL; step_begin / step_end naming a slice; and whatever ste_urtss_backward_f64 refuses (sm_mean /
+ *     sm_cov NULL among it).  STE_FLAG_LANES_1 / _4 are ignored.
+ */
+#define STE_LAG1_POSITION 0x1u /* lag1 rows hold the 4 entries of the lon / lat block instead of all 16 */
+typedef struct ste_lag_one_f64 {
+    double* lag1;      /* DEVICE [Nmax][16][track_stride] out; [Nmax][4][track_stride] with STE_LAG1_POSITION */
+    int32_t* status;   /* DEVICE [B] out or NULL: cleared, then STE_STATUS_NAN (a non-finite entry of L) and what the gain solve
+                          reports (STE_STATUS_NOCONV) are ORed in */
+    uint32_t flags;    /* STE_LAG1_POSITION; unknown bits refused */
+    uint32_t reserved; /* must be 0 */
+} ste_lag_one_f64;     /* 24 bytes */
+
+int ste_urtss_lag_one_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_lag_one_f64* lg, void* stream);
+
+/*
+ * POSITION COVARIANCE: how well the position of ste_track_positions_f64 is known, WITHOUT SAMPLES (an unnumbered addition, like
+ * ste_lag_one_f64).  POSITIONS interpolates linearly inside a step, so the covariance of the interpolated state at fraction u of
+ * step k follows from rows k and k + 1 of the smoothed covariance and the lag-one block between them:
+ *      P(u) = (1 - u)^2 P^s_k + u^2 P^s_{k+1} + (1 - u) u (L_k + L_k^T)
+ * `nqueries`, `qtrack`, `qtime`, `t0` are those of ste_positions_f64 and `knots` is that of ste_field_f64: what a previous
+ * ste_track_positions_f64 on this batch left in its workspace, read only.  The call reads no states.
+ *   - Locate.  POSITIONS word for word: Bad index, Bad time, Locate; the same step[q], frac[q] and STE_POS_* bits of status[q].
+ *     The call never extrapolates.
+ *   - cov has the layout of the batch's histories: [Nmax+1][16][track_stride], or upper triangles [Nmax+1][10][track_stride] with
+ *     STE_FLAG_PACKED_COV in b->flags; of a full matrix the entries with r <= c are read.  sm_cov is what a caller passes.
+ *     lag1 is what ste_urtss_lag_one_f64 wrote, in either form; STE_PCOV_LAG1_POSITION says it is the 4-entry one.
+ *   - Interior, with w1 = u, w0 = 1 - u, A row step[q] of cov, B row step[q] + 1 and L row step[q] of lag1:
+ *          P_rc = ((w0 * w0) * A_rc + (w1 * w1) * B_rc) + (w0 * w1) * (L_rc + L_cr)
+ *     evaluated as written, without contraction: the library and a NumPy restatement agree bit for bit.
+ *   - Knot hit on row j: P_rc = A_rc of row j, copied; the neighbouring row and lag1 are not read.
+ *   - Not located (a bad index, a bad time, outside): NaN in every entry.  A broken step (POSITIONS: Interior) is a property of
+ *     the states, which this call does not read: the caller masks with the position's own NaN.
+ *   - pcov is [3][Q]: lon-lon, lon-lat, lat-lat in degrees squared, pcov[e * Q + q].  With STE_PCOV_FULL it is [10][Q], the upper
+ *     triangle of the 4 x 4 in the order of STE_FLAG_PACKED_COV; that needs the 16-entry lag1.  The three entries the two forms
+ *     share (0 / 0, 1 / 1, 2 / 4) have the same bits.
+ *   - Every value's bits depend on the track's rows of cov and lag1, the knots, t0 and the query alone: not on Q, the place of the
+ *     query in the list, the window, the layout of cov or lag1, or which outputs were asked for.  Every output word has one
+ *     writer; there are no atomics.
+ *   - The call reads only B, Nmax, track_stride, flags (STE_FLAG_PACKED_COV) and nsteps (NULL = Nmax for every track) of the
+ *     batch and writes nothing of it; windows and addressing are those of ste_track_positions_f64, with cov and lag1 in rows of
+ *     track_stride tracks and their pointers at the window's first track.  Rows past nsteps[t] of cov and lag1 are not read.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or pc NULL; B <= 0, Nmax < 0, or track_stride
+ *     non-zero and below B; qtrack, qtime or knots NULL; nqueries < 1 or > STE_POSITIONS_MAX_QUERIES; unknown flag bits; reserved
+ *     != 0; STE_PCOV_FULL together with STE_PCOV_LAG1_POSITION; every output NULL; pcov without cov, or without lag1 when Nmax > 0.
+ */
+#define STE_PCOV_FULL 0x1u          /* pcov is [10][Q], the whole 4 x 4 (upper triangle); needs the 16-entry lag1 */
+#define STE_PCOV_LAG1_POSITION 0x2u /* lag1 is the 4-entry form (STE_LAG1_POSITION) */
+typedef struct ste_position_cov_f64 {
+    uint32_t flags;         /* STE_PCOV_FULL | STE_PCOV_LAG1_POSITION; unknown bits refused */
+    uint32_t reserved;      /* must be 0 */
+    int64_t nqueries;       /* Q, 1 .. STE_POSITIONS_MAX_QUERIES */
+    const int32_t* qtrack;  /* DEVICE [Q]: track of the window, 0 <= t < B */
+    const double* qtime;    /* DEVICE [Q]: clock time, hours */
+    const double* t0;       /* DEVICE [track_stride] or NULL (= 0): clock time of row 0 of each track */
+    const double* knots;    /* DEVICE [Nmax+1][track_stride], read only: what ste_track_positions_f64 left there */
+    const double* cov;      /* DEVICE [Nmax+1][16 or 10][track_stride]: sm_cov, in the layout b->flags names; required with pcov */
+    const double* lag1;     /* DEVICE [Nmax][16 or 4][track_stride]: what ste_urtss_lag_one_f64 wrote; required with pcov */
+    double* pcov;           /* DEVICE [3][Q] or NULL; [10][Q] with STE_PCOV_FULL: degrees squared (and the other units) */
+    int32_t* step;          /* DEVICE [Q] or NULL: row of a knot hit, or k; -1 = not located */
+    double* frac;           /* DEVICE [Q] or NULL: 0 on a knot hit, or u; NaN = not located */
+    int32_t* status;        /* DEVICE [Q] or NULL: STE_POS_* bits */
+} ste_position_cov_f64;     /* 96 bytes */
+
+int ste_track_position_cov_f64(const ste_ukf_batch_f64* b, const ste_position_cov_f64* pc, void* stream);
 
 /* ---- 0.3.2 -------------------------------------------------------------------------------------------------------
  * The forward passes of MANY windows (or batches) as ONE launch.  The reference's batch dimension is its per-ship loop

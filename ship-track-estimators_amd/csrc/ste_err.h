@@ -1,6 +1,6 @@
 // ste_err.h — what the translation units of the UKF ABI share on the host: the thread-local error string behind
 // ste_last_error() (one copy, in ste_kernels.hip), with_bool (a run-time flag as a template argument of a launch), and the
-// functions of ste_forward_quad.hip, ste_smooth.hip and ste_sample.hip that ste_kernels.hip calls.
+// functions of ste_forward_quad.hip, ste_smooth.hip, ste_sample.hip and ste_lagone.hip that ste_kernels.hip calls.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,8 @@ int launch_recur_sched(bool shift, int nitems, const SmoothSchedParams& sp, hipS
 // ste_sample.hip
 int launch_sample_coef(const KParams& kp, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64& sm, hipStream_t s);
 int launch_sample_recur(const KParams& kp, const ste_ukf_sample_f64& sm, hipStream_t s);
+// ste_lagone.hip
+int launch_lag_one(const KParams& kp, const ste_ukf_noise_f64* nz, const ste_lag_one_f64& lg, hipStream_t s);
 
 // A run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{})
 template <class F>

@@ -1975,6 +1975,25 @@ int ste_urtss_sample_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz
     return ste::launch_sample_recur(kp, *sm, (hipStream_t)stream);
 }
 
+// ---- lag-one cross-covariance of the smoother (ste_lag_one_f64; the kernel is in ste_lagone.hip) ---------------------------
+int ste_urtss_lag_one_f64(const ste_ukf_batch_f64* b, const ste_ukf_noise_f64* nz, const ste_lag_one_f64* lg, void* stream) {
+    const char* fn = "ste_urtss_lag_one_f64";
+    if (!b) return fail(STE_EINVAL, "batch pointer is NULL");
+    if (!lg) return fail(STE_EINVAL, "%s: the lag-one arguments (lg) are NULL", fn);
+    if (!lg->lag1) return fail(STE_EINVAL, "%s: lg->lag1 is required", fn);
+    if (lg->flags & ~STE_LAG1_POSITION) return fail(STE_EINVAL, "%s: lg->flags has unknown bits (STE_LAG1_POSITION is the only one)", fn);
+    if (lg->reserved != 0) return fail(STE_EINVAL, "%s: lg->reserved must be 0", fn);
+    if (!b->rts_work || !b->fwd_mean || !b->fwd_cov)
+        return fail(STE_EINVAL, "%s forms the gains from a completed forward pass with rts_work: rts_work, fwd_mean and fwd_cov "
+                                "are required", fn);
+    int rc = whole_passes(fn, b, "the lag-one covariance covers every row of a track, so time slices (step_begin / step_end) are refused");
+    if (rc) return rc;
+    ste::KParams kp;
+    rc = make_params(b, true, &kp);  // sm_mean and sm_cov among it: row k + 1 of sm_cov is the second factor
+    if (rc) return rc;
+    return ste::launch_lag_one(kp, nz, *lg, (hipStream_t)stream);
+}
+
 int ste_geodetic_dynamics_f64(int64_t count, const double* x, const double* dt, const double* sog_rate,
                               const double* cog_rate, double* out, void* stream) {
     if (count < 0) return fail(STE_EINVAL, "count must be >= 0");

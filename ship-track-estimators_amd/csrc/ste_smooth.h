@@ -1,4 +1,5 @@
-// ste_smooth.h — what the work-row smoothers (ste_smooth.hip) and the posterior-track sampler (ste_sample.hip) share on the
+// ste_smooth.h — what the work-row smoothers (ste_smooth.hip), the posterior-track sampler (ste_sample.hip) and the lag-one
+// covariance (ste_lagone.hip) share on the
 // device: how a row that the forward pass left in rts_work is read, and the gain K = D pinv(P_b) formed from it -- one
 // function for the one-kernel smoother, the gains pass of the two-kernel form and the sampler's coefficients: same code, same
 // bits.  The row layout itself (kWorkD ...) is in ste_ukf.h.  Everything here is inlined into its callers.

@@ -336,6 +336,45 @@ class SteFieldF64(C.Structure):
     ]
 
 
+STE_LAG1_POSITION = 0x1
+STE_LAG1_ROWS, STE_LAG1_POSITION_ROWS = 16, 4  # doubles per (step, track) of ste_lag_one_f64.lag1 in its two forms
+
+
+class SteLagOneF64(C.Structure):
+    """Mirror of ``struct ste_lag_one_f64`` (include/ste.h): the lag-one cross-covariance of the smoother."""
+
+    _fields_ = [
+        ("lag1", _dp),
+        ("status", _dp),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+STE_PCOV_FULL = 0x1
+STE_PCOV_LAG1_POSITION = 0x2
+
+
+class StePositionCovF64(C.Structure):
+    """Mirror of ``struct ste_position_cov_f64`` (include/ste.h): the covariance of tracks on the device at given clock times."""
+
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("nqueries", C.c_int64),
+        ("qtrack", _dp),
+        ("qtime", _dp),
+        ("t0", _dp),
+        ("knots", _dp),
+        ("cov", _dp),
+        ("lag1", _dp),
+        ("pcov", _dp),
+        ("step", _dp),
+        ("frac", _dp),
+        ("status", _dp),
+    ]
+
+
 STE_SITES_MAX = 65536
 STE_SITE_BAD_TIME = 0x1
 STE_SITE_BAD_SITE = 0x1
@@ -721,6 +760,8 @@ SYMBOLS = {
     "ste_ukf_noise_moments_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteNoiseMomentsF64), C.c_void_p]),
     "ste_ukf_noise_mstep_f64": (C.c_int, [C.POINTER(SteNoiseMstepF64), C.c_void_p]),
     "ste_field_values_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteFieldF64), C.c_void_p]),
+    "ste_urtss_lag_one_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteUkfNoiseF64), C.POINTER(SteLagOneF64), C.c_void_p]),
+    "ste_track_position_cov_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePositionCovF64), C.c_void_p]),
     "ste_urtss_backward_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_urtss_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.c_void_p]),
     "ste_ukf_forward_sched_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),

@@ -942,6 +942,126 @@ class DeviceBatch:
             self._mark_use(st)
         return out
 
+    # -- lag-one covariance ---------------------------------------------------------------------------------------
+    def lag_one_covariance(self, position_only: bool = False, stream=None):
+        """The lag-one cross-covariance of the smoother, L_k = Cov(x_k, x_{k+1} | all data) = K_k P^s_{k+1} (include/ste.h:
+        ste_urtss_lag_one_f64; DESIGN.md, "Lag-one covariance"), as a device tensor (Nmax, 16, B): entry 4 r + c of row k is
+        L_k[r][c].  ``position_only``: (Nmax, 4, B), the entries L[0][0], L[0][1], L[1][0], L[1][1] -- what the covariance of a
+        position needs, with the same bits.  Rows k >= ``nsteps[b]`` hold zeros.  Needs a completed ``run()`` of this batch (the
+        forward pass's work rows and the smoothed covariances); the batch is only read.  Returns ``(lag1, status)``, status
+        (B,) int32 on the device: STE_STATUS_* bits of the gain solve and STE_STATUS_NAN for a non-finite entry.  A window of a
+        resident batch computes its own tracks."""
+        torch = self.torch
+        if self.rts_work is None:
+            raise ValueError("lag_one_covariance() forms the smoother gains from the work rows the forward pass leaves for the "
+                             "smoother (rts_work), and this batch has none: it was built with fuse_gains=False, "
+                             "histories=False or alloc_smoothed=False")
+        N, B = int(self.struct.Nmax), self.ntracks
+        ld = int(self.struct.track_stride or self.struct.B)
+        rows = binding.STE_LAG1_POSITION_ROWS if position_only else binding.STE_LAG1_ROWS
+        st = self._ordered_stream(stream)
+        with torch.cuda.stream(st):
+            full = torch.zeros((N, rows, ld), dtype=torch.float64, device=self.device)
+            status = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            lg = binding.SteLagOneF64(full.data_ptr() + 8 * self.lo, status.data_ptr(),
+                                      binding.STE_LAG1_POSITION if position_only else 0, 0)
+            noise = None if self.noise is None else C.byref(self.noise)
+            binding.check(self.lib.ste_urtss_lag_one_f64(C.byref(self.struct), noise, C.byref(lg), self._stream(st)),
+                          "ste_urtss_lag_one_f64")
+            out = self._finish(st, [full], {"lag1": full[..., self.lo:self.lo + B] if ld != B else full, "status": status})
+        return out["lag1"], out["status"]
+
+    def position_covariance_at(self, qtrack, qtime, t0=None, lag_one=None, knots=None, full: bool = False, sort: bool = True,
+                               stream=None):
+        """The exact covariance of the smoothed position at given clock times, without samples (include/ste.h:
+        ste_track_position_cov_f64; DESIGN.md, "Lag-one covariance"): ``positions_at`` interpolates linearly inside a step, so
+        at fraction u of step k the covariance is (1-u)^2 P^s_k + u^2 P^s_{k+1} + (1-u) u (L_k + L_k^T), with P^s this batch's
+        ``sm_cov`` and L its lag-one covariance.  ``qtrack``, ``qtime``, ``t0``, ``sort`` and ``stream`` as in ``positions_at``.
+        ``lag_one``: what ``lag_one_covariance`` returned, in either form (``full`` needs the 16-entry one); None computes it
+        (the position form unless ``full``).  ``knots``: what ``positions_at`` or ``track_knots`` returned; None sums them.
+        Returns a dict of device tensors: ``pcov`` (3, Q) -- lon-lon, lon-lat, lat-lat in degrees squared -- or with ``full``
+        (10, Q), the upper triangle of the 4 x 4 (00 01 02 03 11 12 13 22 23 33); a knot hit gives that row of ``sm_cov``, a
+        query that is not located NaN.  ``step``, ``frac``, ``status`` as in ``positions_at``; ``lag_one`` and ``knots`` to pass
+        back in; ``lag_status`` (B,) when the lag-one covariance was computed here.  Where the sampler clamps a negative
+        eigenvalue of a conditional covariance (STE_STATUS_CLAMPED) its ensemble departs from ``sm_cov``; this follows
+        ``sm_cov``."""
+        torch = self.torch
+        N, B = int(self.struct.Nmax), self.ntracks
+        if self.sm_cov is None:
+            raise ValueError("position_covariance_at() reads the smoothed covariances, and this batch was built with "
+                             "alloc_smoothed=False")
+        qtrack = _index_tensor(qtrack, "qtrack", (), binding.STE_POSITIONS_MAX_QUERIES)
+        Q = int(qtrack.shape[0])
+        qtime = torch.as_tensor(qtime, dtype=torch.float64)
+        if tuple(qtime.shape) != (Q,):
+            raise ValueError(f"qtime must have shape ({Q},) like qtrack, got {tuple(qtime.shape)}")
+        if knots is not None and not (isinstance(knots, torch.Tensor) and knots.dtype == torch.float64 and knots.device == self.device
+                                      and tuple(knots.shape) == (N + 1, B)):
+            raise ValueError(f"knots must be the float64 ({N + 1}, {B}) tensor a previous call on this batch returned")
+        lag_rows = (binding.STE_LAG1_ROWS, binding.STE_LAG1_POSITION_ROWS)
+        if lag_one is not None and not (isinstance(lag_one, torch.Tensor) and lag_one.dtype == torch.float64
+                                        and lag_one.device == self.device and lag_one.dim() == 3
+                                        and (lag_one.shape[0], lag_one.shape[2]) == (N, B) and lag_one.shape[1] in lag_rows):
+            raise ValueError(f"lag_one must be the float64 ({N}, 16 or 4, {B}) tensor lag_one_covariance() returned")
+        if full and lag_one is not None and lag_one.shape[1] != binding.STE_LAG1_ROWS:
+            raise ValueError("full=True needs the 16-entry lag-one covariance (lag_one_covariance(position_only=False))")
+        ld = int(self.struct.track_stride or self.struct.B)
+        lag_status = None
+        if lag_one is None:
+            lag_one, lag_status = self.lag_one_covariance(position_only=not full, stream=stream)
+        if knots is None:
+            knots = self.track_knots(stream=stream)
+        st = self._ordered_stream(stream)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            qt = _index_int32(qtrack.to(self.device))
+            tq = qtime.to(self.device).contiguous()
+            perm = None
+            if sort and Q > 1:
+                by_time = torch.sort(tq, stable=True).indices
+                perm = by_time[torch.sort(qt[by_time], stable=True).indices]
+                qt, tq = qt[perm].contiguous(), tq[perm].contiguous()
+            keep = [qt, tq, self.sm_cov]
+            pc = binding.StePositionCovF64()
+            rows = int(lag_one.shape[1])
+            pc.flags = (binding.STE_PCOV_FULL if full else 0) | (binding.STE_PCOV_LAG1_POSITION if rows == lag_rows[1] else 0)
+            pc.nqueries, pc.qtrack, pc.qtime = Q, qt.data_ptr(), tq.data_ptr()
+            pc.t0 = self._track_clock(t0, ld, self.lo, keep)
+            # knots and lag1 are read in rows of this batch's track_stride, at the window's first column: in place when that
+            # is how the tensor lies (what track_knots / lag_one_covariance return), else through a copy of that shape
+            if knots.stride() == (ld, 1):
+                pc.knots = knots.data_ptr()
+            else:
+                ws = torch.empty((N + 1, ld), **f64)
+                ws[:, self.lo:self.lo + B].copy_(knots)
+                pc.knots = ws.data_ptr() + 8 * self.lo
+                keep.append(ws)
+            if N == 0 or lag_one.stride() == (rows * ld, ld, 1):
+                pc.lag1 = lag_one.data_ptr() if N > 0 else None
+            else:
+                lw = torch.empty((N, rows, ld), **f64)
+                lw[..., self.lo:self.lo + B].copy_(lag_one)
+                pc.lag1 = lw.data_ptr() + 8 * self.lo
+                keep.append(lw)
+            keep += [knots, lag_one]
+            pc.cov = self.struct.sm_cov
+            out = {"pcov": torch.empty((10 if full else 3, Q), **f64), "step": torch.empty((Q,), **i32),
+                   "frac": torch.empty((Q,), **f64), "status": torch.empty((Q,), **i32)}
+            for k, ten in out.items():
+                setattr(pc, k, ten.data_ptr())
+            binding.check(self.lib.ste_track_position_cov_f64(C.byref(self.struct), C.byref(pc), self._stream(st)),
+                          "ste_track_position_cov_f64")
+            if perm is not None:  # back to the caller's order
+                inv = torch.empty_like(perm)
+                inv[perm] = torch.arange(Q, device=self.device)
+                out = {k: v[..., inv].contiguous() for k, v in out.items()}
+                keep += [perm, inv]
+            out["knots"], out["lag_one"] = knots, lag_one
+            if lag_status is not None:
+                out["lag_status"] = lag_status
+            return self._finish(st, keep, out)
+
     # -- path quantities ------------------------------------------------------------------------------------------
     def path_metrics(self, states, model: str = "sphere", cumulative: bool = False, line_axis=None, line_value=None,
                      stream=None):
@@ -4391,6 +4511,57 @@ def position_statistics(hb_or_db, qtrack, qtime, nsamples: int, seed: int = 0, c
     out["count"] = count
     out.update(position_ellipse(count, moments, out["lat"], prob))
     out["sample_status"] = status.cpu().numpy()
+    return out
+
+
+def covariance_ellipse(cxx, cxy, cyy, anchor_lat, prob: float = 0.95):
+    """Covariance and error ellipse in km from a position covariance in degrees squared (``DeviceBatch.position_covariance_at``:
+    lon-lon, lon-lat, lat-lat): NumPy on (Q,) arrays, with the km scaling, the ellipse and the orientation of
+    ``position_ellipse`` -- east is dx times Kd cos(anchor lat) and north dy times Kd, Kd = 6378.137 pi / 180.  Returns a dict:
+    ``cov_km`` (Q, 2, 2); ``semi_major_km``, ``semi_minor_km``, the square roots of its eigenvalues times
+    sqrt(-2 ln(1 - prob)); ``orientation_deg`` in [0, 180), the major axis clockwise from north.  NaN in, NaN out."""
+    prob = float(prob)
+    if not 0.0 < prob < 1.0:
+        raise ValueError(f"prob must lie strictly between 0 and 1, got {prob!r}")
+    cxx, cxy, cyy = (np.asarray(v, dtype=np.float64) for v in (cxx, cxy, cyy))
+    lat = np.asarray(anchor_lat, dtype=np.float64)
+    if not (cxx.shape == cxy.shape == cyy.shape == lat.shape) or cxx.ndim != 1:
+        raise ValueError(f"cxx, cxy, cyy and anchor_lat are wanted as (Q,) arrays, got {cxx.shape}, {cxy.shape}, {cyy.shape} and "
+                         f"{lat.shape}")
+    ke, kn = KM_PER_DEG * np.cos(np.radians(lat)), KM_PER_DEG
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a, b, c = cxx * ke * ke, cxy * ke * kn, cyy * kn * kn
+        half, mid = np.hypot(0.5 * (a - c), b), 0.5 * (a + c)
+        scale = np.sqrt(-2.0 * np.log1p(-prob))
+        major, minor = scale * np.sqrt(np.maximum(mid + half, 0.0)), scale * np.sqrt(np.maximum(mid - half, 0.0))
+        orient = np.where(np.isnan(half), np.nan, (90.0 - 0.5 * np.degrees(np.arctan2(2.0 * b, a - c))) % 180.0)
+    cov = np.stack([np.stack([a, b], axis=-1), np.stack([b, c], axis=-1)], axis=-2)
+    return {"cov_km": cov, "semi_major_km": major, "semi_minor_km": minor, "orientation_deg": orient}
+
+
+def position_covariance(hb_or_db, qtrack, qtime, t0=None, prob: float = 0.95, device="cuda:0"):
+    """Position at given clock times with its exact covariance under the smoothing posterior, per query, without samples: the
+    sample-free sibling of ``position_statistics`` ("Lag-one covariance").  The smoothed track is interpolated
+    (``DeviceBatch.positions_at``) and its covariance follows in closed form from ``sm_cov`` and the smoother's lag-one
+    covariance (``DeviceBatch.position_covariance_at``, in its position-only form: memory of order Nmax B 4 + Q).  Given a
+    ``HostBatch`` it uploads it and runs the forward pass and the smoother first; a ``DeviceBatch`` (or a window of one) is
+    taken to hold a completed ``run()``.  ``qtrack``, ``qtime`` and ``t0`` as in ``positions_at``.
+
+    Returns a dict of NumPy arrays per query: ``lon``, ``lat``, ``speed``, ``heading``, ``step``, ``frac``, ``status`` of the
+    smoothed track; what ``covariance_ellipse`` makes of the covariance: ``cov_km`` (Q, 2, 2), ``semi_major_km``,
+    ``semi_minor_km``, ``orientation_deg`` for ``prob``, NaN where the smoothed position is (a query that is not located, a
+    broken step); and ``lag_status`` (B,), the STE_STATUS_* bits of the lag-one call per track."""
+    if not 0.0 < float(prob) < 1.0:
+        raise ValueError(f"prob must lie strictly between 0 and 1, got {prob!r}")
+    db = _posterior_batch(hb_or_db, 1, 1, device, "position_covariance")[0]
+    smoothed = db.positions_at(db.sm_mean, qtrack, qtime, t0=t0, velocity=True)
+    pc = db.position_covariance_at(qtrack, qtime, t0=t0, knots=smoothed["knots"])
+    out = {k: smoothed[k][0].cpu().numpy() for k in ("lon", "lat", "speed", "heading")}
+    out.update({k: smoothed[k].cpu().numpy() for k in ("step", "frac", "status")})
+    pcov = pc["pcov"].cpu().numpy()
+    pcov[:, np.isnan(out["lon"]) | np.isnan(out["lat"])] = np.nan
+    out.update(covariance_ellipse(pcov[0], pcov[1], pcov[2], out["lat"], prob))
+    out["lag_status"] = pc["lag_status"].cpu().numpy()
     return out
 
 

@@ -425,7 +425,7 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         res["posterior"] = {k: v[..., 0] for k, v in out.items() if not k.endswith("_smoothed") and k != "status"}
         return res
 
-    def position_at(self, times, n_samples: int = 0, random_state: int = 0):
+    def position_at(self, times, n_samples: int = 0, random_state: int = 0, covariance: bool = False):
         """Where the track ``run`` filtered was at ``times``, hours from its first row
         (``track_estimators.batch.position_statistics``; no counterpart in the reference, whose callers search and interpolate
         the history themselves).  A position is linear in time inside a step, a time that is a step time returns that row, and
@@ -433,7 +433,10 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         ``(len(times), 4)`` array of lon, lat, speed, heading.  Otherwise a dict: ``position``, that array, and per time
         ``count``, ``mean_east_km``, ``mean_north_km``, ``cov_km``, ``semi_major_km``, ``semi_minor_km``, ``orientation_deg``
         (the 95 % ellipse) from that many tracks drawn from the joint smoothing posterior, those of
-        ``sample_smoothed(n_samples, random_state)``.  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
+        ``sample_smoothed(n_samples, random_state)``.  ``covariance=True`` (with ``n_samples == 0``): a dict with ``position`` and
+        the EXACT ``cov_km``, ``semi_major_km``, ``semi_minor_km``, ``orientation_deg`` of the smoothing posterior there, in
+        closed form from the smoothed covariances and the smoother's lag-one covariance, without samples
+        (``track_estimators.batch.position_covariance``).  The track is packed as ``run`` packed it, as for ``sample_smoothed``."""
         hb = getattr(self, "_sample_hb", None)
         if hb is None:
             raise RuntimeError("position_at() reads the track of the last run(): call run() first")
@@ -447,6 +450,20 @@ class UnscentedKalmanFilter(KalmanFilterBase):
         if times.ndim != 1 or times.size < 1:
             raise ValueError(f"times must be a scalar or a one-dimensional array of hours, got shape {times.shape}")
         track = np.zeros(times.size, dtype=np.int32)
+        if covariance:
+            if n_samples != 0:
+                raise ValueError("covariance=True gives the exact covariance and draws no samples: leave n_samples at 0")
+            db = _batch.DeviceBatch(hb)
+            db.run()
+            if int(db.status_host()[0]) & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            out = _batch.position_covariance(db, track, times)
+            self._status_lag_one = int(out["lag_status"][0])
+            if self._status_lag_one & 0x1:
+                raise np.linalg.LinAlgError("SVD did not converge")
+            res = {"position": np.stack([out[k] for k in ("lon", "lat", "speed", "heading")], axis=1)}
+            res.update({k: out[k] for k in ("cov_km", "semi_major_km", "semi_minor_km", "orientation_deg")})
+            return res
         if n_samples == 0:
             db = _batch.DeviceBatch(hb)
             db.run()
