@@ -812,6 +812,12 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
         cr_n = p.cog_rate[t];
         ui_n = p.upd_idx[t];
     }
+    // Consumed here, once: nothing pending from the prologue reaches the loop header, so the wait for a step's inputs (loaded
+    // a whole step ahead) does not also cover the history and work-row stores of the step before (in_vgpr, ste_math.h).
+    dt_n = in_vgpr(dt_n);
+    sr_n = in_vgpr(sr_n);
+    cr_n = in_vgpr(cr_n);
+    ui_n = in_vgpr(ui_n);
     for (int k = 0; k < p.Nmax; ++k) {
         const bool live = k < ns;
         if (!__any(live)) break;

@@ -256,6 +256,14 @@ __device__ __forceinline__ double in_vgpr(double v) {  // opaque to the optimise
     asm volatile("" : "+v"(v));
     return v;
 }
+// The same for a word.  Also what "consumes" a value loaded in front of a step loop for the loop's first step: the compiler
+// waits for the load here, once, instead of carrying "a load may be pending" into the loop header, where it would have to
+// merge with the back edge's state and wait for everything -- the previous step's stores included -- at the top of every
+// step ("Store drain").
+__device__ __forceinline__ int in_vgpr(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 __device__ __forceinline__ void trig_reg_init(TrigLit&) {}
 __device__ __forceinline__ void trig_reg_init(TrigReg& k) {
     k.s1 = in_vgpr(TrigLit::s1);

@@ -43,27 +43,58 @@ __device__ __forceinline__ void load_recur_row(const KParams& p, size_t k, size_
     load_cov_p(p.fwd_cov, (p.flags & STE_FLAG_PACKED_COV) != 0, k, B, t, g.Pk);
 }
 
+// Every value load_recur_row loads, consumed (in_vgpr): in front of a step loop whose rows are loaded a step ahead, so that
+// the loop is entered with nothing pending.  Without recorded noise rows 2-3 of D are neither loaded nor read.
+template <bool kShift>
+__device__ __forceinline__ void consume_recur_row(bool d_rows23, RecurRow& g) {
+    if (kShift) {
+        g.shift[0] = in_vgpr(g.shift[0]);
+        g.shift[1] = in_vgpr(g.shift[1]);
+    }
+    STE_UNROLL
+    for (int e = 0; e < 4; ++e) g.D2[e] = in_vgpr(g.D2[e]);
+    if (d_rows23) {
+        STE_UNROLL
+        for (int e = 4; e < 8; ++e) g.D2[e] = in_vgpr(g.D2[e]);
+    }
+    STE_UNROLL
+    for (int c = 0; c < 4; ++c) g.xk[c] = in_vgpr(g.xk[c]);
+    STE_UNROLL
+    for (int e = 0; e < 10; ++e) g.Pk[e] = in_vgpr(g.Pk[e]);
+}
+
+// x_b, P_b as the forward pass stored them in work row k (a full row, work_row_full)
+__device__ __forceinline__ void load_stored_xb_pb(const KParams& p, size_t k, size_t B, size_t t, double (&xb)[4], double (&Pb)[10]) {
+    const double* w = p.rts_work + (k * kWorkElems) * B + t;
+    STE_UNROLL
+    for (int c = 0; c < 4; ++c) xb[c] = w[(kWorkXb + c) * B];
+    STE_UNROLL
+    for (int e = 0; e < 10; ++e) Pb[e] = w[(kWorkPb + e) * B];
+}
+
 // What the smoother's step k needs besides the recurrence itself: x_b, P_b (stored, or rebuilt from history rows k and
 // k + 1) and the gain K = D pinv(P_b) (unscented.py:315-333).  `cur` = work-row / history data of step k, (xn, Pn) = filtered
 // row k + 1, `full` = work row k holds x_b and P_b.  Shared by the one-kernel smoother (urtss_recur_l1) and the two-kernel
 // form for small batches (urtss_gains_all + urtss_recur_lean): same code, same bits.
 // kTrackNoise: the four entries of Q it reads come from `q4` (Q[0][2], Q[0][3], Q[1][2], Q[1][3] of this track, see
 // track_q4) instead of from the kernel arguments.
-template <bool kShift, bool kTrackNoise = false>
+// kRowAhead (the step loop of smooth_tile_l1): on a full row `xb` / `Pb` come in holding the stored x_b, P_b, loaded by the
+// caller a row ahead (load_stored_xb_pb) -- in front of the previous row's stores, so that the step waits for neither the
+// loads' latency nor those stores' acknowledgements ("Store drain"); on other rows they are formed here.
+template <bool kShift, bool kTrackNoise = false, bool kRowAhead = false>
 __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_t B, size_t t, const RecurRow& cur,
                                                   const double (&xn)[4], const double (&Pn)[10], bool full, bool always_full,
                                                   bool all_eig, double kappa, double first_bad, double (&xb)[4],
                                                   double (&Pb)[10], double (&K)[4][4], const double* q4 = nullptr) {
-    // x_b, P_b: stored (a quarter of the steps of the bench batch: loaded here, not a row ahead, to keep the
-    // registers of a whole row free), or the prediction itself -- the step was not followed by an update, so row
-    // k + 1 of the filtered history is x^-, P^-, and P_b = P^- + b b^T with b = x^- - x_k
-    STE_UNROLL
-    for (int c = 0; c < 4; ++c) xb[c] = xn[c];
-    if (kShift) {  // the smoother's own rates (load_recur_row)
-        xb[2] += cur.shift[0];
-        xb[3] += cur.shift[1];
-    }
-    {
+    // x_b, P_b: stored (a quarter of the steps of the bench batch), or the prediction itself -- the step was not followed by
+    // an update, so row k + 1 of the filtered history is x^-, P^-, and P_b = P^- + b b^T with b = x^- - x_k
+    if (!kRowAhead || !full) {
+        STE_UNROLL
+        for (int c = 0; c < 4; ++c) xb[c] = xn[c];
+        if (kShift) {  // the smoother's own rates (load_recur_row)
+            xb[2] += cur.shift[0];
+            xb[3] += cur.shift[1];
+        }
         double bv[4];
         STE_UNROLL
         for (int c = 0; c < 4; ++c) bv[c] = xb[c] - cur.xk[c];
@@ -74,11 +105,7 @@ __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_
         }
     }
     if (full) {
-        const double* w = p.rts_work + ((size_t)k * kWorkElems) * B + t;
-        STE_UNROLL
-        for (int c = 0; c < 4; ++c) xb[c] = w[(kWorkXb + c) * B];
-        STE_UNROLL
-        for (int e = 0; e < 10; ++e) Pb[e] = w[(kWorkPb + e) * B];
+        if (!kRowAhead) load_stored_xb_pb(p, (size_t)k, B, t, xb, Pb);
         if (kShift) {
             // stored with the forward rates: P_b = C + b b^T with b = (weighted mean of the fan) - x_k, i.e. x_b - x_k
             // less the recorded noise that was added to x_b (unscented.py:319-325); now b' = b + s, s = (0, 0, shift):
@@ -139,6 +166,15 @@ __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_
             for (int r = 0; r < 4; ++r) {
                 D[r][2] = w[(kWorkD23 + r * 2 + 0) * B];
                 D[r][3] = w[(kWorkD23 + r * 2 + 1) * B];
+            }
+            // In the step loop, waited for in this cold branch: pending where it rejoins, these loads make every step wait
+            // for all the wave has in flight, the previous row's stores included, at the head of the solve.
+            if (kRowAhead) {
+                STE_UNROLL
+                for (int r = 0; r < 4; ++r) {
+                    D[r][2] = in_vgpr(D[r][2]);
+                    D[r][3] = in_vgpr(D[r][3]);
+                }
             }
         }
     }

@@ -70,31 +70,51 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
     STE_UNROLL
     for (int e = 0; e < 10; ++e) Pn[e] = Ps[e];
 
-    // the row of the first step this lane processes, and the update index of the one after it, in flight
+    // The row of the first step this lane processes and, where that row is full, its stored x_b, P_b: a full row's 14 words
+    // are loaded a row ahead too, into the registers x_b and P_b of the current step leave free -- so the update index that
+    // says whether a row is full is loaded two rows ahead.
     RecurRow nxt;
-    int ui_n = -1;
+    int ui_n = -1, ui_nn = -1;
+    double xb[4] = {0.0, 0.0, 0.0, 0.0}, Pb[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (ns > 0) {
         load_recur_row<kShift>(p, (size_t)(ns - 1), B, t, always_full, nxt);
         ui_n = p.upd_idx[(size_t)(ns - 1) * B + t];
+        ui_nn = p.upd_idx[(size_t)clampk(ns - 2) * B + t];
+        if (work_row_full(p, ns - 1, ui_n, always_full)) load_stored_xb_pb(p, (size_t)(ns - 1), B, t, xb, Pb);
     }
+    // Consumed here, once: nothing pending from the prologue reaches the loop header, so the waits of a step (whose loads are
+    // older than the stores of the row before) do not cover those stores (in_vgpr, ste_math.h).
+    consume_recur_row<kShift>(always_full, nxt);
+    ui_n = in_vgpr(ui_n);
+    ui_nn = in_vgpr(ui_nn);
+    STE_UNROLL
+    for (int c = 0; c < 4; ++c) xb[c] = in_vgpr(xb[c]);
+    STE_UNROLL
+    for (int e = 0; e < 10; ++e) Pb[e] = in_vgpr(Pb[e]);
     int st = 0;
     for (int k = p.Nmax - 1; k >= 0; --k) {
         if (!__any(k < ns)) continue;  // ragged batch: nobody in this wave has reached its last step yet
         if (k < ns) {
             const RecurRow cur = nxt;
             const bool full = work_row_full(p, k, ui_n, always_full);
-            double xb[4], Pb[10], K[4][4];
-            st |= smoother_step_gain<kShift, kTrackNoise>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
-            // the row of the next step: in flight during the recurrence arithmetic below (and across the loop edge)
-            {
-                const int kn = clampk(k - 1);
-                load_recur_row<kShift>(p, (size_t)kn, B, t, always_full, nxt);
-                ui_n = p.upd_idx[(size_t)kn * B + t];
-            }
+            double K[4][4];
+            st |= smoother_step_gain<kShift, kTrackNoise, true>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
+            // y = x^s_{k+1} - x_b and dP = P^s_{k+1} - P_b first: x_b, P_b of this step are done with, and their registers take
+            // the stored ones of the next step
             double y[4];
             STE_UNROLL
             for (int c = 0; c < 4; ++c) y[c] = xs[c] - xb[c];
             y[3] = wrap180(y[3]);
+            double dP[10];
+            STE_UNROLL
+            for (int e = 0; e < 10; ++e) dP[e] = Ps[e] - Pb[e];
+            // the row of the next step, and its stored x_b, P_b if it is full: in front of this row's stores, in flight during
+            // the recurrence arithmetic below and across the loop edge (row 0 again on the last step: in bounds, not used)
+            const int kn = clampk(k - 1);
+            load_recur_row<kShift>(p, (size_t)kn, B, t, always_full, nxt);
+            ui_n = ui_nn;
+            if (work_row_full(p, kn, ui_n, always_full)) load_stored_xb_pb(p, (size_t)kn, B, t, xb, Pb);
+            ui_nn = p.upd_idx[(size_t)clampk(k - 2) * B + t];
             STE_UNROLL
             for (int r = 0; r < 4; ++r) {
                 double acc = cur.xk[r];
@@ -104,9 +124,6 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
             }
             xs[3] = floored_mod(xs[3], 360.0);
             // P^s_k = P_k + K (P^s_{k+1} - P_b) K^T, symmetric operands packed
-            double dP[10];
-            STE_UNROLL
-            for (int e = 0; e < 10; ++e) dP[e] = Ps[e] - Pb[e];
             double KdP[4][4];
             STE_UNROLL
             for (int r = 0; r < 4; ++r) {
