@@ -99,6 +99,8 @@ extern "C" {
                            values of a space-time gridded field where tracks on the device were at given clock times
                            (ste_field_values_f64).  Unnumbered addition: the lag-one cross-covariance of the smoother and the
                            exact covariance of a position at a query time (ste_urtss_lag_one_f64, ste_track_position_cov_f64).
+                           Unnumbered addition: the pair list of the encounter call found on the device
+                           (ste_encounter_candidates_mask_f64, ste_encounter_candidates_list_f64).
                            0.3.3: Matern kernels (nu = 1/2, 3/2, 5/2) on the GP path (ste_gp_batch_f64.kernel, appended).
                            0.3.2: the forward passes of many windows as one scheduled launch (ste_ukf_forward_sched_f64,
                            ste_stream_wait_counter); 321: their smoothers as one launch too (ste_urtss_backward_sched_f64).  0.3.1: track_stride (windows of a resident fleet), sm_pos, forward pass in
@@ -621,6 +623,101 @@ typedef struct ste_encounter_f64 {
 } ste_encounter_f64;       /* 120 bytes */
 
 int ste_encounter_metrics_f64(const ste_ukf_batch_f64* b, const ste_encounter_f64* en, void* stream);
+
+/*
+ * CANDIDATES: the pair list of ste_encounter_f64, found on the device (an unnumbered addition, like ste_encounter_f64): which
+ * pairs (i, j), i < j, of the tracks of a batch can have been within reach_km of each other AT ONE INSTANT.  The clock is cut
+ * into windows; every track gets, per window it lives in, a box around the unit vectors of its rows; a pair is listed when
+ * the two boxes of some window are closer than the chord of the reach.  `states` is ONE state set, [Nmax+1][4][track_stride]
+ * (sm_mean, fwd_mean or one sample).  Below clamp(x, a, b) = x < a ? a : (x > b ? b : x), min and max as for ENCOUNTERS, and
+ * every expression is evaluated as written, left to right, without contraction.
+ *   - Clock.  As for ENCOUNTERS: tau_t[k] = t0[t] + T_k, T_0 = 0, T_{k+1} = T_k + dt_k summed in order; t0 NULL is 0.  A track
+ *     has a BAD CLOCK when t0 is not finite or when a dt among its first nsteps is not finite and >= 0, and gets
+ *     STE_CAND_BAD_TIME.  With a bad t0 it pairs with nothing (and gets no other clock bit).  A bad dt_k ENDS the track at
+ *     knot k for this call: steps k and later do not exist, everything below speaks of the steps before it.  (The walk of
+ *     ENCOUNTERS gives a pair nothing once it meets that dt, and a pair whose walk ends before it is met is served from the
+ *     steps before it: the guarantee below has to hold for those.)
+ *   - Windows.  time0, window_h = W > 0 and nwindows = NW are host values; window w covers [time0 + w W, time0 + (w + 1) W).
+ *     win(x) = clamp(floor((x - time0) / W), 0, NW - 1).  Clamping merges whatever lies outside the range into the edge
+ *     windows and never loses a pair; a track for which clamping changed an index of one of its knots 0 .. nsteps gets
+ *     STE_CAND_CLIPPED.  win is monotone in x: if two ships are both on a step at one instant, that instant's window lies in
+ *     the window ranges of both steps.
+ *   - Sound steps.  The rule of ENCOUNTERS: step k is BROKEN when |wrap180(lon_{k+1} - lon_k)| < 90 is false or either of
+ *     its latitudes is not finite.  Broken steps contribute nothing (a piece on one adds nothing to any within-R output of
+ *     ste_encounter_metrics_f64).  A track with a finite t0 and no sound step (nsteps 0, or a bad dt_0, included) gets
+ *     STE_CAND_EMPTY and pairs with nothing.
+ *   - Boxes.  For (track, window w), over the sound steps k with win(tau[k]) <= w <= win(tau[k+1]): lo[3] and hi[3] are the
+ *     componentwise min and max of the unit vectors (cos lat cos lon, cos lat sin lon, sin lat), angles times kDeg2Rad, of rows
+ *     k and k + 1; h is the max over those steps of 0.5 * kDeg2Rad * sqrt(delta * delta + dlat * dlat), delta and dlat those
+ *     of ENCOUNTERS: half the step's planar length in radians.  Every point of a step that is linear in (lon, lat) lies
+ *     within that great-circle angle of one of its two rows.  Without such a step the box is EMPTY: lo = +inf, hi = -inf,
+ *     h = 0.  sin and cos are the only operations whose bits may differ between implementations.
+ *   - Near.  Tracks i and j are NEAR in window w when both boxes are non-empty and g2 <= c * c, with
+ *     g_c = max(max(0, lo_i[c] - hi_j[c]), lo_j[c] - hi_i[c]) for c = 0, 1, 2, g2 = (g_0 * g_0 + g_1 * g_1) + g_2 * g_2,
+ *     theta = min(((((reach_km / 6378.137 + m_i) + m_j) + h_i) + h_j) + 1e-7, pi), c = 2 * sin(theta / 2), and
+ *     m_t = track_margin_km[t] / 6378.137 (0 when the array is NULL).  A track whose margin is negative or not finite gets
+ *     STE_CAND_BAD_MARGIN and pairs with nothing.  1e-7 rad is a slack of 0.6 m for the roundings of the corners.
+ *   - Output.  The pairs (i, j), i < j, that are near in at least one window, int32 [P][2] sorted by (i, j) (the order on
+ *     which ste_encounter_metrics_f64 is fastest); on request per pair wfirst, the first near window, and nwin, the number of
+ *     near windows: the pair can only be within reach inside those; track_status[B] with the STE_CAND_* bits.
+ *   - GUARANTEE.  If ste_encounter_metrics_f64 on these states finds a sound piece of (i, j) whose TRUE angular separation
+ *     at some instant is <= reach_km / 6378.137, then (i, j) is in the list: both ships are on sound steps at that instant,
+ *     its window is in both steps' window ranges, each position is within h of a row inside its box, and the chord between
+ *     two points is at least the gap between boxes that hold them.  Whole-track time overlap is implied and is no separate
+ *     test.  The caller puts into reach_km (or track_margin_km) what the tested track does not show: the posterior spread
+ *     when the list is used on samples, and the 0.2 % by which the planar distance of ENCOUNTERS may differ from the true one.
+ *   - Determinism.  The list depends on the tracks' rows, dt, t0, the window parameters, the margins and reach_km alone: not
+ *     on the fleet window it is read through, the stream, or an earlier call.  No atomics; every word has one writer.
+ *   - Two calls and a workspace; the library never allocates.  ste_encounter_candidates_mask_f64 writes track_status and, into
+ *     the workspace, the boxes, one bit per (i, j) and the number of pairs of every row.  The caller forms the exclusive
+ *     prefix of those counts (row_offset, int64 [B]) and their sum P, provides pairs [P][2] and then
+ *     ste_encounter_candidates_list_f64, with the same struct but for row_offset, npairs, pairs, wfirst and nwin, writes the
+ *     list.  With P = 0 there is nothing to list.  The workspace holds, in this order: double boxes[NW][7][B] (lo[3], hi[3], h;
+ *     only the windows wlo[t] .. whi[t] of track t are written and read), uint64 mask[B][ceil(B / 64)] (bit j % 64 of word
+ *     j / 64 of row i; only words j / 64 >= i / 64 are written and read), int32 wlo[B], whi[B] (wlo > whi: the track pairs with
+ *     nothing), count[B]; ste_encounter_candidates_workspace(B, nwindows) is its size in bytes, 0 for arguments out of range.
+ *   - The calls read only B, Nmax, track_stride, nsteps (NULL = Nmax for every track) and dt of the batch and write nothing of
+ *     it; windows and addressing are those of ste_encounter_metrics_f64, t0, track_margin_km and track_status like nsteps;
+ *     pair indices count from the window's first track.  Rows past nsteps[t] of states are not read.
+ *   - Refused with STE_EINVAL and a message naming the call, before any launch: b or c NULL; states NULL; b->dt NULL; window_h
+ *     not finite or <= 0; time0 not finite; nwindows < 1 or > STE_CANDIDATES_MAX_WINDOWS; reach_km not finite, < 0 or
+ *     > STE_CANDIDATES_MAX_REACH_KM (theta reaches pi at 20 037 km, where every pair is near); flags or reserved non-zero;
+ *     B <= 0 or > STE_CANDIDATES_MAX_TRACKS, Nmax < 0, track_stride non-zero and below B; workspace NULL, not aligned to 8
+ *     bytes or workspace_bytes below the size above; the mask call without track_status; the list call without row_offset or
+ *     pairs, or with npairs < 1 or > STE_ENCOUNTER_MAX_PAIRS.
+ */
+#define STE_CANDIDATES_MAX_WINDOWS 4096
+#define STE_CANDIDATES_MAX_REACH_KM 20000.0
+#define STE_CANDIDATES_MAX_TRACKS (1 << 20)
+#define STE_CAND_BAD_TIME   0x1  /* a non-finite t0 (pairs with nothing), or a dt among the first nsteps that is not finite and
+                                    >= 0 (the track ends there) */
+#define STE_CAND_CLIPPED    0x2  /* a knot of the track lies outside [time0, time0 + NW W): merged into an edge window */
+#define STE_CAND_EMPTY      0x4  /* a finite t0 and no sound step */
+#define STE_CAND_BAD_MARGIN 0x8  /* track_margin_km[t] negative or not finite */
+typedef struct ste_candidates_f64 {
+    const double* states;          /* DEVICE [Nmax+1][4][track_stride]: one state set, as one sample of ste_path_f64 */
+    const double* t0;              /* DEVICE [B] or NULL (= 0): clock time of row 0 of each track, hours */
+    const double* track_margin_km; /* DEVICE [B] or NULL (= 0): added to the reach of every pair the track is in */
+    double reach_km;               /* HOST: finite, 0 <= reach_km <= STE_CANDIDATES_MAX_REACH_KM */
+    double time0;                  /* HOST: start of window 0, hours, finite */
+    double window_h;               /* HOST: W, finite, > 0 */
+    int32_t nwindows;              /* NW, 1 .. STE_CANDIDATES_MAX_WINDOWS */
+    uint32_t flags;                /* must be 0 */
+    uint32_t reserved;             /* must be 0 */
+    int32_t reserved_pad;          /* not read */
+    void* workspace;               /* DEVICE, 8-byte aligned, >= ste_encounter_candidates_workspace(B, nwindows) bytes */
+    uint64_t workspace_bytes;
+    int32_t* track_status;         /* DEVICE [B]: STE_CAND_* bits, written by the mask call */
+    const int64_t* row_offset;     /* DEVICE [B]: exclusive prefix of the workspace's count[] (list call) */
+    int64_t npairs;                /* P = sum of count[], 1 .. STE_ENCOUNTER_MAX_PAIRS (list call) */
+    int32_t* pairs;                /* DEVICE [P][2], written by the list call */
+    int32_t* wfirst;               /* DEVICE [P] or NULL: first near window (list call) */
+    int32_t* nwin;                 /* DEVICE [P] or NULL: number of near windows (list call) */
+} ste_candidates_f64;              /* 128 bytes */
+
+size_t ste_encounter_candidates_workspace(int32_t B, int32_t nwindows);
+int ste_encounter_candidates_mask_f64(const ste_ukf_batch_f64* b, const ste_candidates_f64* c, void* stream);
+int ste_encounter_candidates_list_f64(const ste_ukf_batch_f64* b, const ste_candidates_f64* c, void* stream);
 
 /*
  * POSITIONS: where tracks that stay on the device were AT GIVEN CLOCK TIMES (an unnumbered addition, like ste_encounter_f64):

@@ -261,6 +261,40 @@ class SteEncounterF64(C.Structure):
     ]
 
 
+STE_CANDIDATES_MAX_WINDOWS = 4096
+STE_CANDIDATES_MAX_REACH_KM = 20000.0
+STE_CANDIDATES_MAX_TRACKS = 1 << 20
+STE_CAND_BAD_TIME = 0x1
+STE_CAND_CLIPPED = 0x2
+STE_CAND_EMPTY = 0x4
+STE_CAND_BAD_MARGIN = 0x8
+
+
+class SteCandidatesF64(C.Structure):
+    """Mirror of ``struct ste_candidates_f64`` (include/ste.h): the pair list of the encounter call, found on the device."""
+
+    _fields_ = [
+        ("states", _dp),
+        ("t0", _dp),
+        ("track_margin_km", _dp),
+        ("reach_km", C.c_double),
+        ("time0", C.c_double),
+        ("window_h", C.c_double),
+        ("nwindows", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("reserved_pad", C.c_int32),
+        ("workspace", _dp),
+        ("workspace_bytes", C.c_uint64),
+        ("track_status", _dp),
+        ("row_offset", _dp),
+        ("npairs", C.c_int64),
+        ("pairs", _dp),
+        ("wfirst", _dp),
+        ("nwin", _dp),
+    ]
+
+
 STE_POSITIONS_MAX_QUERIES = 1 << 26
 STE_POS_REUSE_KNOTS = 0x1
 STE_POS_BAD_INDEX = 0x1
@@ -743,6 +777,9 @@ SYMBOLS = {
     "ste_region_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteRegionF64), C.c_void_p]),
     "ste_grid_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteGridF64), C.c_void_p]),
     "ste_encounter_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteEncounterF64), C.c_void_p]),
+    "ste_encounter_candidates_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "ste_encounter_candidates_mask_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteCandidatesF64), C.c_void_p]),
+    "ste_encounter_candidates_list_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteCandidatesF64), C.c_void_p]),
     "ste_track_positions_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(StePositionsF64), C.c_void_p]),
     "ste_site_metrics_f64": (C.c_int, [C.POINTER(SteUkfBatchF64), C.POINTER(SteSiteF64), C.c_void_p]),
     "ste_site_tile": (C.c_int, []),

@@ -690,9 +690,10 @@ class DeviceBatch:
             keep.append(dt)
         return s, states, B, 0
 
-    def _track_clock(self, t0, width, col, keep):
+    def _track_clock(self, t0, width, col, keep, name: str = "t0"):
         """``t0`` of a metric call (None, a scalar or one clock time per track) as the pointer the kernel takes, or None.
-        Inside the stream context."""
+        Inside the stream context.  ``name``: what the value is called in the message (another per-track input of the
+        same form, such as ``track_margin_km``)."""
         if t0 is None:
             return None
         torch, B = self.torch, self.ntracks
@@ -700,7 +701,7 @@ class DeviceBatch:
         if tv.dim() == 0:
             tv = tv.expand(B)
         if tuple(tv.shape) != (B,):
-            raise ValueError(f"t0 must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+            raise ValueError(f"{name} must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
         clock = torch.zeros((width,), dtype=torch.float64, device=self.device)
         clock[col:col + B] = tv
         keep.append(clock)
@@ -1315,6 +1316,117 @@ class DeviceBatch:
             binding.check(self.lib.ste_encounter_metrics_f64(C.byref(s), C.byref(en), self._stream(st)),
                           "ste_encounter_metrics_f64")
             return self._finish(st, keep, out)
+
+    # -- candidate pairs for encounters -----------------------------------------------------------------------------
+    def _clock_range(self, t0):
+        """(earliest start, latest end) in hours over the tracks of this batch whose clock is sound (a finite ``t0``, every
+        ``dt`` of its steps finite and >= 0), as two floats: one host read.  None when no track has one.  Inside the stream
+        context."""
+        torch, B, N = self.torch, self.ntracks, int(self.struct.Nmax)
+        ns = self.t["nsteps"][self.lo:self.lo + B].to(torch.int64).clamp(0, N)
+        dt = self.t["dt"][:, self.lo:self.lo + B]
+        live = torch.arange(N, device=self.device)[:, None] < ns[None, :]
+        d = torch.where(live, dt, torch.zeros_like(dt))
+        if t0 is None:
+            start = torch.zeros((B,), dtype=torch.float64, device=self.device)
+        else:
+            start = torch.as_tensor(t0, dtype=torch.float64).to(self.device).expand(B)
+        end = start + d.sum(dim=0)
+        sound = torch.isfinite(start) & torch.isfinite(end) & (torch.isfinite(d) & (d >= 0.0)).all(dim=0)
+        inf = torch.full_like(start, float("inf"))
+        first, last = (float(v) for v in torch.stack([torch.where(sound, start, inf).min(),
+                                                      torch.where(sound, end, -inf).max()]).cpu())
+        return (first, last) if first <= last else None
+
+    def encounter_candidates(self, reach_km, window_h, states=None, t0=None, time0=None, nwindows=None, track_margin_km=None,
+                             details: bool = False, stream=None):
+        """The pairs of this batch worth giving to ``encounter_metrics``, found on the device (include/ste.h: CANDIDATES,
+        ste_encounter_candidates_mask_f64 / _list_f64; DESIGN.md, "Candidates"): an int32 (P, 2) device tensor of (i, j),
+        i < j, sorted by (i, j), of the tracks that can have been within ``reach_km`` of each other at one instant.  The clock
+        is cut into ``nwindows`` windows of ``window_h`` hours from ``time0``; a track gets a box around its rows per window,
+        and a pair is kept when two boxes of one window are closer than the reach.  Every pair that ``encounter_metrics``
+        on these ``states`` brings within ``reach_km`` (true distance) is in the list, whatever the windows; smaller windows
+        prune more and cost more.  ``states``: ONE state set, (Nmax+1, 4, B) or (1, Nmax+1, 4, B); None = ``sm_mean``, else
+        ``fwd_mean``.  A list for several samples is not built: widen ``reach_km`` or give ``track_margin_km`` (None, a scalar
+        or one value per track, km, added to the reach of every pair the track is in; ``batch.position_spread_km``).  ``t0``
+        as in ``encounter_metrics``.  ``time0`` / ``nwindows`` None: the earliest start and the latest end over the sound
+        clocks, found on the device (one host read); times outside the windows are merged into the edge windows, never
+        lost.  Between the two kernels' calls the number of pairs is read on the host (it sizes the result).  Returns
+        ``pairs``; with ``details`` a dict of ``pairs``, ``wfirst`` and ``nwin`` (P,) int32 -- the first window in which
+        the pair is near and the number of such windows: it can only be within reach inside those -- ``track_status`` (B,)
+        int32 with the STE_CAND_* bits, and the ``time0``, ``window_h`` and ``nwindows`` used."""
+        torch = self.torch
+        if states is None:
+            states = self.sm_mean if self.sm_mean is not None else self.fwd_mean
+            if states is None:
+                raise ValueError("encounter_candidates() needs states, sm_mean or fwd_mean, and this batch was built without histories")
+        states, S = self._metric_states(states)
+        if S != 1:
+            raise ValueError(f"encounter_candidates() takes one state set, got S = {S}: a list for several samples is not built "
+                             "(widen reach_km or give track_margin_km)")
+        reach_km, window_h = float(reach_km), float(window_h)
+        if not (np.isfinite(reach_km) and 0.0 <= reach_km <= binding.STE_CANDIDATES_MAX_REACH_KM):
+            raise ValueError(f"reach_km must be finite and between 0 and {binding.STE_CANDIDATES_MAX_REACH_KM:g}, got {reach_km!r}")
+        if not (np.isfinite(window_h) and window_h > 0.0):
+            raise ValueError(f"window_h must be finite and > 0, got {window_h!r}")
+        B, top = self.ntracks, binding.STE_CANDIDATES_MAX_WINDOWS
+        if B > binding.STE_CANDIDATES_MAX_TRACKS:
+            raise ValueError(f"encounter_candidates() takes at most {binding.STE_CANDIDATES_MAX_TRACKS} tracks, got {B}")
+        if time0 is not None and not np.isfinite(float(time0)):
+            raise ValueError(f"time0 must be finite, got {time0!r}")
+        if nwindows is not None and not 1 <= int(nwindows) <= top:
+            raise ValueError(f"nwindows must be between 1 and {top}, got {nwindows!r}")
+        st = self._ordered_stream(stream)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(st):
+            if time0 is None or nwindows is None:
+                span = self._clock_range(t0)
+                first, last = span if span is not None else (0.0, 0.0)
+                time0 = first if time0 is None else float(time0)
+                if nwindows is None:
+                    count = max(np.floor((last - time0) / window_h), 0.0) + 1.0
+                    if count > top:
+                        raise ValueError(f"{last - time0:g} hours of clock in windows of {window_h:g} h are {count:.0f} windows, "
+                                         f"above STE_CANDIDATES_MAX_WINDOWS = {top}: window_h >= {(last - time0) / (top - 1):.6g} "
+                                         "would fit (or give time0 and nwindows)")
+                    nwindows = int(count)
+            time0, nwindows = float(time0), int(nwindows)
+            keep = []
+            s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
+            cd = binding.SteCandidatesF64()
+            cd.states, cd.reach_km, cd.time0, cd.window_h, cd.nwindows = states.data_ptr(), reach_km, time0, window_h, nwindows
+            cd.flags, cd.reserved = 0, 0
+            cd.t0 = self._track_clock(t0, width, col, keep)
+            cd.track_margin_km = self._track_clock(track_margin_km, width, col, keep, name="track_margin_km")
+            nbytes = int(self.lib.ste_encounter_candidates_workspace(B, nwindows))
+            work = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+            out = {"track_status": torch.empty((B,), **i32)}
+            cd.workspace, cd.workspace_bytes, cd.track_status = work.data_ptr(), 8 * work.numel(), out["track_status"].data_ptr()
+            binding.check(self.lib.ste_encounter_candidates_mask_f64(C.byref(s), C.byref(cd), self._stream(st)),
+                          "ste_encounter_candidates_mask_f64")
+            at = 2 * (7 * nwindows * B + B * ((B + 63) // 64)) + 2 * B  # count[B], after boxes, mask, wlo and whi (include/ste.h)
+            counts = work.view(torch.int32)[at:at + B]
+            ends = torch.cumsum(counts, dim=0, dtype=torch.int64)
+            P = int(ends[-1])  # the one host read: it sizes the result
+            if P > binding.STE_ENCOUNTER_MAX_PAIRS:
+                raise ValueError(f"{P} candidate pairs, above STE_ENCOUNTER_MAX_PAIRS = {binding.STE_ENCOUNTER_MAX_PAIRS}: "
+                                 "use smaller windows, a smaller reach, or a window of the fleet")
+            out["pairs"] = torch.empty((P, 2), **i32)
+            if details:
+                out["wfirst"], out["nwin"] = torch.empty((P,), **i32), torch.empty((P,), **i32)
+            if P > 0:
+                offsets = ends - counts
+                keep.append(offsets)
+                cd.row_offset, cd.npairs, cd.pairs = offsets.data_ptr(), P, out["pairs"].data_ptr()
+                if details:
+                    cd.wfirst, cd.nwin = out["wfirst"].data_ptr(), out["nwin"].data_ptr()
+                binding.check(self.lib.ste_encounter_candidates_list_f64(C.byref(s), C.byref(cd), self._stream(st)),
+                              "ste_encounter_candidates_list_f64")
+            keep.append(work)
+            self._finish(st, keep, out)
+            if not details:
+                return out["pairs"]
+            return dict(out, time0=time0, window_h=window_h, nwindows=nwindows)
 
     # -- positions at query times ---------------------------------------------------------------------------------
     def positions_at(self, states, qtrack, qtime, t0=None, velocity: bool = False, anchor=None, accumulate=None, knots=None,
@@ -3796,7 +3908,8 @@ def candidate_pairs(mean, nsteps, dt, radius_km, margin_km: float = 0.0, t0=None
     return torch.cat(found).to(torch.int32)
 
 
-def encounter_candidates(db: "DeviceBatch", radius_km, margin_km: float = 0.0, t0=None, chunk: int = 2048):
+def encounter_candidates(db: "DeviceBatch", radius_km, margin_km: float = 0.0, t0=None, chunk: int = 2048, window_h=None,
+                         track_margin_km=None):
     """The pairs of a resident batch worth giving to ``DeviceBatch.encounter_metrics``: an int32 (P, 2) device tensor of
     (i, j), i < j, sorted by (i, j), on the batch's device.  Torch plumbing without a kernel, on ``sm_mean`` (``fwd_mean`` when
     the batch has no smoother).  Every track gets a bounding cap on the unit sphere (centre: the normalised sum of its rows'
@@ -3806,7 +3919,19 @@ def encounter_candidates(db: "DeviceBatch", radius_km, margin_km: float = 0.0, t
     times chunk x B doubles.  Tracks with ``nsteps == 0`` or a non-finite row pair with nothing; the test is on unit vectors,
     so the antimeridian is no special case.  ``margin_km`` must cover what the tested track does not show: the posterior spread
     when the pairs are then used on samples of the posterior (a few standard deviations of position), and the 0.2 % by which
-    the kernel's planar distance may differ from the true one."""
+    the kernel's planar distance may differ from the true one.
+
+    ``window_h`` (hours): the pairs come from ``DeviceBatch.encounter_candidates`` instead, the kernels of include/ste.h
+    CANDIDATES, with reach = ``radius_km`` + ``margin_km``, windows of ``window_h`` over the fleet's clock, and
+    ``track_margin_km`` (``position_spread_km``) as a margin per track; ``chunk`` is not used.  Which one: the caps above
+    prune only ships that stay in one place for their whole life (a fleet in separate basins, short tracks); voyages that
+    cross an ocean have caps thousands of kilometres wide and clocks that all overlap, and there the windowed list, which
+    asks where the two ships were in the same few hours, is a small fraction of this one ("Candidates").  Both
+    hold every pair that comes within ``radius_km``; a day is a reasonable ``window_h`` for ships."""
+    if window_h is not None:
+        return db.encounter_candidates(float(radius_km) + float(margin_km), window_h, t0=t0, track_margin_km=track_margin_km)
+    if track_margin_km is not None:
+        raise ValueError("track_margin_km belongs to the windowed list: give window_h as well")
     mean = db.sm_mean if db.sm_mean is not None else db.fwd_mean
     if mean is None:
         raise ValueError("encounter_candidates() needs sm_mean or fwd_mean, and this batch was built without histories")
@@ -3815,6 +3940,28 @@ def encounter_candidates(db: "DeviceBatch", radius_km, margin_km: float = 0.0, t
     dt = db.t["dt"][:, db.lo:db.lo + B]
     with db.torch.cuda.device(db.device):
         return candidate_pairs(mean, nsteps, dt, radius_km, margin_km, t0, chunk)
+
+
+def position_spread_km(db: "DeviceBatch", nsigma: float = 3.0):
+    """How far a posterior sample of each track may lie from its smoothed position, in km: per track, ``nsigma`` times the
+    square root of the largest eigenvalue of the (lon, lat) block of ``sm_cov`` over its rows 0 .. nsteps, longitude scaled
+    by cos(lat) and both by 6378.137 pi / 180 km per degree.  A (B,) float64 device tensor; torch on the device, no kernel.
+    It is the ``track_margin_km`` of ``encounter_candidates`` for a list that is to be used on posterior samples
+    (``encounter_statistics``).  NaN where a covariance of the track is not finite (such a track then pairs with nothing)."""
+    if db.sm_cov is None or db.sm_mean is None:
+        raise ValueError("position_spread_km() needs sm_mean and sm_cov: a batch with histories and a smoother")
+    torch = db.torch
+    with torch.cuda.device(db.device):
+        cov, B = db.sm_cov, db.ntracks
+        c00, c01, c11 = cov[:, 0], cov[:, 1], cov[:, 4 if db.packed_cov else 5]
+        kd = EARTH_RADIUS_KM * np.pi / 180.0
+        kx = kd * torch.cos(torch.deg2rad(db.sm_mean[:, 1]))
+        a, b, d = c00 * kx * kx, c01 * kx * kd, c11 * kd * kd
+        lam = 0.5 * ((a + d) + torch.sqrt((a - d) * (a - d) + 4.0 * b * b))        # (Nmax+1, B)
+        ns = db.t["nsteps"][db.lo:db.lo + B].to(torch.int64).clamp(0, cov.shape[0] - 1)
+        live = torch.arange(cov.shape[0], device=db.device)[:, None] <= ns[None, :]
+        worst = torch.where(live, lam, torch.zeros_like(lam)).max(dim=0).values
+        return float(nsigma) * torch.sqrt(worst.clamp(min=0.0))
 
 
 def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 0, chunk: int = 16, t0=None,
@@ -3826,7 +3973,8 @@ def encounter_statistics(hb_or_db, pairs, radius_km, nsamples: int, seed: int = 
     and with ``chunk >= nsamples`` they are those of ``sample_smoothed(nsamples, seed)``.  The ships' posteriors are taken as
     independent (each is smoothed on its own).  Given a ``HostBatch`` it uploads it and runs the forward pass and the smoother
     first; a ``DeviceBatch`` (or a window of one) is taken to hold a completed ``run()``.  ``pairs``, ``radius_km``, ``t0``
-    and ``model`` as in ``encounter_metrics``.
+    and ``model`` as in ``encounter_metrics``.  A pair list that holds every pair a sample can bring within ``radius_km``
+    comes from ``encounter_candidates`` with ``track_margin_km=position_spread_km(db)``.
 
     Returns a dict of NumPy arrays per pair: ``min_dist_smoothed``, ``min_time_smoothed``, ``time_within_smoothed``,
     ``overlap_smoothed`` (P,) and ``status`` (P,; STE_ENC_* bits), of the smoothed tracks ``sm_mean``; ``min_dist``
