@@ -22,11 +22,10 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include <string>
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
+#include "ste_track.h"  // is_finite, wave_min, wave_max; it switches contraction off, and the pragma below says so here
 
 #pragma clang fp contract(off)  // explicit fma() only (ste_math.h): every expression of the rule as written
 
@@ -62,7 +61,6 @@ struct CandParams {
     int32_t* nwin;          // [P] or nullptr
 };
 
-__device__ __forceinline__ bool finite(double x) { return x * 0.0 == 0.0; }
 __device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
 __device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
 
@@ -97,9 +95,10 @@ __device__ __forceinline__ void box_store(const CandParams& p, int w, int t, con
     o[6 * B] = b.h;
 }
 
-// the unit vector of a row; a row that is not finite belongs to no sound step and gets no trigonometry
-__device__ __forceinline__ void unit_vector(double lon, double lat, double (&u)[3]) {
-    if (finite(lon) && finite(lat)) {
+// The unit vector of a row; a row that is not finite belongs to no sound step and gets no trigonometry.  Not the
+// unit_vector of ste_track.h: the boxes are made with sincos_fast, as tests/candidate_cases.py restates them.
+__device__ __forceinline__ void box_vector(double lon, double lat, double (&u)[3]) {
+    if (is_finite(lon) && is_finite(lat)) {
         double sl, cl, sp, cp;
         sincos_fast(lon * kDeg2Rad, sl, cl);
         sincos_fast(lat * kDeg2Rad, sp, cp);
@@ -115,15 +114,15 @@ __global__ __launch_bounds__(64) void cand_boxes(const CandParams p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
     if (t >= p.B) return;
     const size_t ld = p.ld;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double t0 = p.t0 ? p.t0[t] : 0.0;
     int status = 0;
     if (p.margin) {
         const double m = p.margin[t];
-        if (!(m >= 0.0 && finite(m))) status |= STE_CAND_BAD_MARGIN;
+        if (!(m >= 0.0 && is_finite(m))) status |= STE_CAND_BAD_MARGIN;
     }
     int wlo = 0, whi = -1;
-    const bool bad_t0 = !finite(t0);
+    const bool bad_t0 = !is_finite(t0);
     bool bad_dt = false, clipped = false, any_sound = false;
     if (!bad_t0) {
         const double* st = p.states + (size_t)t;  // row k, component c: st[(k * 4 + c) * ld]
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(64) void cand_boxes(const CandParams p) {
             nlon = st[4 * ld];
             nlat = st[5 * ld];
             dtk = dtp[0];
-            unit_vector(lon, lat, u);
+            box_vector(lon, lat, u);
         }
         for (int k = 0; k < ns; ++k) {
             // what the next step needs, in flight during this step's arithmetic
@@ -152,15 +151,15 @@ __global__ __launch_bounds__(64) void cand_boxes(const CandParams p) {
                 plon = st[(r * 4) * ld];
                 plat = st[(r * 4 + 1) * ld];
             }
-            if (!(dtk >= 0.0 && finite(dtk))) {  // the track ends here: the walk of ENCOUNTERS goes no further either
+            if (!(dtk >= 0.0 && is_finite(dtk))) {  // the track ends here: the walk of ENCOUNTERS goes no further either
                 bad_dt = true;
                 break;
             }
             T = T + dtk;
             const int b = window_of(t0 + T, p.time0, p.window_h, p.NW, clipped);
-            unit_vector(nlon, nlat, v);
+            box_vector(nlon, nlat, v);
             const double delta = wrap180(nlon - lon), dlat = nlat - lat;
-            const bool sound = fabs(delta) < 90.0 && finite(lat) && finite(nlat);
+            const bool sound = fabs(delta) < 90.0 && is_finite(lat) && is_finite(nlat);
             Box sb;
             box_empty(sb);
             if (sound) {
@@ -218,15 +217,6 @@ __device__ __forceinline__ bool near_test(double li0, double li1, double li2, do
     sincos_fast(th / 2.0, s, cs);
     const double c = 2.0 * s;
     return both && gg <= c * c;
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int wave_max(int v) {
-    for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m));
-    return __builtin_amdgcn_readfirstlane(v);
 }
 
 __device__ __forceinline__ void box_load(const CandParams& p, int w, int t, bool in, double (&b)[7]) {
@@ -350,15 +340,12 @@ size_t workspace_bytes(int64_t B, int64_t NW) {
 }
 
 // the refusals the two calls share, and the parameters; returns STE_OK or the recorded failure
-int cand_params(const char* call, const ste_ukf_batch_f64* b, const ste_candidates_f64* c, CandParams& p) {
-    const std::string name(call);
-    auto refuse = [&](const char* why) { return abi_fail(STE_EINVAL, (name + ": " + why).c_str()); };
+int cand_params(const Refusal& refuse, const ste_ukf_batch_f64* b, const ste_candidates_f64* c, CandParams& p) {
     if (!b) return refuse("batch pointer is NULL");
     if (!c) return refuse("the candidate arguments (c) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return refuse("B must be > 0 and Nmax >= 0");
+    if (int rc = refuse.shape(b)) return rc;
     if (b->B > STE_CANDIDATES_MAX_TRACKS) return refuse("B is limited to STE_CANDIDATES_MAX_TRACKS (2^20) per call (the mask is B x B bits)");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return refuse("track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
+    if (int rc = refuse.stride(b)) return rc;
     if (!c->states) return refuse("c->states is required");
     if (!b->dt) return refuse("the batch's dt is required (the clock is made of its sums)");
     if (!(std::isfinite(c->window_h) && c->window_h > 0.0)) return refuse("c->window_h must be finite and > 0");
@@ -376,7 +363,7 @@ int cand_params(const char* call, const ste_ukf_batch_f64* b, const ste_candidat
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.NW = c->nwindows;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nwords = ((size_t)b->B + 63) / 64;
     p.nsteps = b->nsteps;
     p.dt = b->dt;
@@ -411,9 +398,10 @@ extern "C" size_t ste_encounter_candidates_workspace(int32_t B, int32_t nwindows
 
 extern "C" int ste_encounter_candidates_mask_f64(const ste_ukf_batch_f64* b, const ste_candidates_f64* c, void* stream) {
     using namespace ste;
+    const Refusal refuse{"ste_encounter_candidates_mask_f64"};
     CandParams p;
-    if (int rc = cand_params("ste_encounter_candidates_mask_f64", b, c, p)) return rc;
-    if (!c->track_status) return abi_fail(STE_EINVAL, "ste_encounter_candidates_mask_f64: c->track_status is required");
+    if (int rc = cand_params(refuse, b, c, p)) return rc;
+    if (!c->track_status) return refuse("c->track_status is required");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned nt = (unsigned)p.nwords;
     hipLaunchKernelGGL(cand_boxes, dim3(nt), dim3(64), 0, s, p);
@@ -424,12 +412,13 @@ extern "C" int ste_encounter_candidates_mask_f64(const ste_ukf_batch_f64* b, con
 
 extern "C" int ste_encounter_candidates_list_f64(const ste_ukf_batch_f64* b, const ste_candidates_f64* c, void* stream) {
     using namespace ste;
+    const Refusal refuse{"ste_encounter_candidates_list_f64"};
     CandParams p;
-    if (int rc = cand_params("ste_encounter_candidates_list_f64", b, c, p)) return rc;
-    if (!c->row_offset) return abi_fail(STE_EINVAL, "ste_encounter_candidates_list_f64: c->row_offset is required");
-    if (!c->pairs) return abi_fail(STE_EINVAL, "ste_encounter_candidates_list_f64: c->pairs is required");
+    if (int rc = cand_params(refuse, b, c, p)) return rc;
+    if (!c->row_offset) return refuse("c->row_offset is required");
+    if (!c->pairs) return refuse("c->pairs is required");
     if (c->npairs < 1 || c->npairs > STE_ENCOUNTER_MAX_PAIRS)
-        return abi_fail(STE_EINVAL, "ste_encounter_candidates_list_f64: c->npairs must be between 1 and STE_ENCOUNTER_MAX_PAIRS (2^26)");
+        return refuse("c->npairs must be between 1 and STE_ENCOUNTER_MAX_PAIRS (2^26)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (c->wfirst || c->nwin) hipLaunchKernelGGL(cand_list<true>, dim3((unsigned)p.B), dim3(64), 0, s, p);
     else hipLaunchKernelGGL(cand_list<false>, dim3((unsigned)p.B), dim3(64), 0, s, p);

@@ -22,8 +22,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -169,6 +168,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         if (!(t0i * 0.0 == 0.0 && t0j * 0.0 == 0.0)) status = STE_ENC_BAD_TIME;
     }
     if (status == 0) {
+        // track_steps(p, i), written out: through the function the kernel's address arithmetic comes out in another order
         const int nsi = min(max(p.nsteps ? p.nsteps[i] : p.Nmax, 0), p.Nmax);
         const int nsj = min(max(p.nsteps ? p.nsteps[j] : p.Nmax, 0), p.Nmax);
         const double* sti = p.states + (s * rows * 4) * ld + (size_t)i;  // row k, component c: sti[(k * 4 + c) * ld]
@@ -264,33 +264,30 @@ void launch_encounter(const EncParams& p, hipStream_t s) {
 
 extern "C" int ste_encounter_metrics_f64(const ste_ukf_batch_f64* b, const ste_encounter_f64* en, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: batch pointer is NULL");
-    if (!en) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: the encounter arguments (en) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!en->states) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->states is required");
-    if (!en->pairs) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->pairs is required");
-    if (en->nstates < 1) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->nstates must be >= 1");
-    if (en->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->nstates is limited to 65535 per call (one grid row per track of a ship)");
+    const Refusal refuse{"ste_encounter_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!en) return refuse("the encounter arguments (en) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!en->states) return refuse("en->states is required");
+    if (!en->pairs) return refuse("en->pairs is required");
+    if (int rc = refuse.nstates("en->nstates", en->nstates, " (one grid row per track of a ship)")) return rc;
     if (en->npairs < 1 || en->npairs > STE_ENCOUNTER_MAX_PAIRS)
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->npairs must be between 1 and STE_ENCOUNTER_MAX_PAIRS (2^26)");
-    if (en->min_dist && en->model != STE_PREP_SPHERE && en->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->model must be STE_PREP_SPHERE or STE_PREP_WGS84 when min_dist is asked for");
+        return refuse("en->npairs must be between 1 and STE_ENCOUNTER_MAX_PAIRS (2^26)");
+    if (en->min_dist && refuse.model("en->model", en->model, " when min_dist is asked for")) return STE_EINVAL;
     if (!(std::isfinite(en->radius_km) && en->radius_km >= 0.0 && en->radius_km <= STE_ENCOUNTER_MAX_RADIUS_KM))
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->radius_km must be finite and between 0 and STE_ENCOUNTER_MAX_RADIUS_KM (1000)");
-    if (en->flags != 0) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->flags must be 0");
-    if (en->reserved != 0) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: en->reserved must be 0");
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: the batch's dt is required (the common clock is made of its sums)");
+        return refuse("en->radius_km must be finite and between 0 and STE_ENCOUNTER_MAX_RADIUS_KM (1000)");
+    if (en->flags != 0) return refuse("en->flags must be 0");
+    if (en->reserved != 0) return refuse("en->reserved must be 0");
+    if (!b->dt) return refuse("the batch's dt is required (the common clock is made of its sums)");
     if (!en->min_dist && !en->min_time && !en->time_within && !en->first_within && !en->nwithin && !en->overlap &&
         !en->nbroken && !en->status)
-        return abi_fail(STE_EINVAL, "ste_encounter_metrics_f64: no output asked for (min_dist, min_time, time_within, first_within, nwithin, overlap, nbroken and status are all NULL)");
+        return refuse("no output asked for (min_dist, min_time, time_within, first_within, nwithin, overlap, nbroken and status are all NULL)");
     EncParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = en->nstates;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.npairs = (size_t)en->npairs;
     p.nsteps = b->nsteps;
     p.dt = b->dt;

@@ -25,8 +25,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 #ifndef STE_ERROR_TILE
 #define STE_ERROR_TILE 1  // samples per lane; DESIGN.md, "Errors", has the timing of 1 against 4
@@ -51,25 +50,11 @@ struct ErrorParams {
     double nees_limit;
 };
 
-// A position as the leg wants it.  Sphere: radians and cos(lat), converted once per row.  WGS84: degrees.
-struct ErrorPoint {
-    double lon, lat, c;
-};
-template <int kModel>
-__device__ __forceinline__ ErrorPoint error_point(double lon_deg, double lat_deg) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double lat = lat_deg * kDeg2Rad;
-        return {lon_deg * kDeg2Rad, lat, cos(lat)};
-    } else {
-        return {lon_deg, lat_deg, 0.0};
-    }
-}
-
 // The leg from a (the truth) to b (the state): distance and, with kHead, initial heading.  Sphere: sphere_dist_km, and
 // operation for operation the head_deg of sphere_leg on the radians and cosines at hand.  WGS84: wgs84_leg, whose heading
 // arithmetic the compiler drops where the heading is not used.
 template <int kModel, bool kHead>
-__device__ __forceinline__ double error_leg(const ErrorPoint& a, const ErrorPoint& b, double& head_deg) {
+__device__ __forceinline__ double error_leg(const TrackPoint<kModel>& a, const TrackPoint<kModel>& b, double& head_deg) {
     if constexpr (kModel == STE_PREP_SPHERE) {
         if constexpr (kHead) {
             const double dlon = b.lon - a.lon;
@@ -92,6 +77,7 @@ __global__ __launch_bounds__(64) void track_errors(const ErrorParams p) {
     if (t >= (size_t)p.B) return;
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1;
     const double nan = __builtin_nan("");
+    // track_steps(p, t), written out: through the function the kernel's address arithmetic comes out in another order
     const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
     const int s0 = (int)blockIdx.y * kTile;
     // sample j of the tile; the last tile of a call repeats its last sample in the lanes' spare slots and stores it once
@@ -170,15 +156,15 @@ __global__ __launch_bounds__(64) void track_errors(const ErrorParams p) {
         // wave's: no lane with truth in this row, no leg.
         const bool truthed = is_finite(tlon) && is_finite(tlat);
         const bool any = __ballot(truthed) != 0;
-        ErrorPoint tp = {0.0, 0.0, 0.0};
-        if (any) tp = error_point<kModel>(truthed ? tlon : 0.0, truthed ? tlat : 0.0);
+        TrackPoint<kModel> tp = {0.0, 0.0, 0.0};
+        if (any) tp = track_point<kModel>(truthed ? tlon : 0.0, truthed ? tlat : 0.0);
 #pragma unroll
         for (int j = 0; j < kTile; ++j) {
             double e = nan, al = nan, cr = nan, q = nan;
             if (any) {
                 const bool ok = truthed && is_finite(lon[j]) && is_finite(lat[j]);
                 double head = 0.0;
-                const double d = error_leg<kModel, kHead>(tp, error_point<kModel>(ok ? lon[j] : 0.0, ok ? lat[j] : 0.0), head);
+                const double d = error_leg<kModel, kHead>(tp, track_point<kModel>(ok ? lon[j] : 0.0, ok ? lat[j] : 0.0), head);
                 const bool sound = ok && is_finite(d);
                 if (truthed && !sound) ++nbroken[j];
                 if (sound) {
@@ -267,39 +253,35 @@ void launch_errors(const ErrorParams& p, hipStream_t s) {
 
 extern "C" int ste_track_errors_f64(const ste_ukf_batch_f64* b, const ste_errors_f64* er, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_track_errors_f64: batch pointer is NULL");
-    if (!er) return abi_fail(STE_EINVAL, "ste_track_errors_f64: the error arguments (er) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_track_errors_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!er->states) return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->states is required");
-    if (!er->truth) return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->truth is required");
-    if (er->nstates < 1) return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->nstates must be >= 1");
-    if (er->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (er->model != STE_PREP_SPHERE && er->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->model must be STE_PREP_SPHERE or STE_PREP_WGS84");
-    if (er->reserved != 0) return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->reserved must be 0");
+    const Refusal refuse{"ste_track_errors_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!er) return refuse("the error arguments (er) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!er->states) return refuse("er->states is required");
+    if (!er->truth) return refuse("er->truth is required");
+    if (int rc = refuse.nstates("er->nstates", er->nstates, " (one grid row per track of a ship)")) return rc;
+    if (int rc = refuse.model("er->model", er->model)) return rc;
+    if (er->reserved != 0) return refuse("er->reserved must be 0");
     if (er->cov && er->cov_rows != STE_ERRORS_COV_FULL && er->cov_rows != STE_ERRORS_COV_PACKED)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->cov_rows must be 16 (full matrices) or 10 (upper triangles) with er->cov");
+        return refuse("er->cov_rows must be 16 (full matrices) or 10 (upper triangles) with er->cov");
     if (er->cov && er->nstates > 1)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->cov needs nstates == 1 (a covariance belongs to one track, not to its samples)");
+        return refuse("er->cov needs nstates == 1 (a covariance belongs to one track, not to its samples)");
     if (er->cov && !(std::isfinite(er->nees_limit) && er->nees_limit > 0.0))
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: er->nees_limit must be finite and > 0 with er->cov");
+        return refuse("er->nees_limit must be finite and > 0 with er->cov");
     const bool head = er->sum_along || er->sum_along_sq || er->sum_cross || er->sum_cross_sq || er->ncoursed || er->along || er->cross;
     const bool nees = er->sum_nees || er->nscored || er->ninside || er->nees;
     if (head && !er->course)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: an along / cross output (sum_along, sum_along_sq, sum_cross, sum_cross_sq, ncoursed, along, cross) needs er->course");
-    if (nees && !er->cov)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: a NEES output (sum_nees, nscored, ninside, nees) needs er->cov");
+        return refuse("an along / cross output (sum_along, sum_along_sq, sum_cross, sum_cross_sq, ncoursed, along, cross) needs er->course");
+    if (nees && !er->cov) return refuse("a NEES output (sum_nees, nscored, ninside, nees) needs er->cov");
     if (!head && !nees && !er->sum_err && !er->sum_sq && !er->max_err && !er->n && !er->max_row && !er->nbroken && !er->err && !er->cumerr)
-        return abi_fail(STE_EINVAL, "ste_track_errors_f64: no output asked for (every output pointer is NULL)");
+        return refuse("no output asked for (every output pointer is NULL)");
     ErrorParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = er->nstates;
     p.cov_rows = er->cov ? er->cov_rows : 0;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.states = er->states;
     p.truth = er->truth;

@@ -25,8 +25,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(64) void field_query(const FieldParams p) {
         if (!(is_finite(t0) && T0 == T0 && is_finite(tq))) {
             status = STE_POS_BAD_TIME;
         } else {
-            const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+            const int ns = track_steps(p, t);
             const double tau0 = t0 + T0;
             if (tq == tau0) {
                 row = 0;
@@ -320,60 +319,51 @@ __global__ __launch_bounds__(64) void field_query(const FieldParams p) {
 
 extern "C" int ste_field_values_f64(const ste_ukf_batch_f64* b, const ste_field_f64* f, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_field_values_f64: batch pointer is NULL");
-    if (!f) return abi_fail(STE_EINVAL, "ste_field_values_f64: the field arguments (f) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_field_values_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!f->states) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->states is required");
-    if (!f->qtrack) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->qtrack is required");
-    if (!f->qtime) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->qtime is required");
+    const Refusal refuse{"ste_field_values_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!f) return refuse("the field arguments (f) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!f->states) return refuse("f->states is required");
+    if (!f->qtrack) return refuse("f->qtrack is required");
+    if (!f->qtime) return refuse("f->qtime is required");
     if (!f->knots)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->knots is required (the knot times a previous ste_track_positions_f64 "
-                                    "on this batch left, [Nmax+1][track_stride])");
-    if (!f->values) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->values is required");
-    if (f->nstates < 1) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->nstates must be >= 1");
-    if (f->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->nstates is limited to 65535 per call (one grid row per sample)");
+        return refuse("f->knots is required (the knot times a previous ste_track_positions_f64 "
+                      "on this batch left, [Nmax+1][track_stride])");
+    if (!f->values) return refuse("f->values is required");
+    if (int rc = refuse.nstates("f->nstates", f->nstates, " (one grid row per sample)")) return rc;
     if (f->nqueries < 1 || f->nqueries > STE_POSITIONS_MAX_QUERIES)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
-    if (f->flags & ~(STE_GRID_PERIODIC_LON | STE_FLD_NEAREST | STE_FLD_VALUES_F32))
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->flags has unknown bits");
-    if (f->reserved != 0) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->reserved must be 0");
+        return refuse("f->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
+    if (f->flags & ~(STE_GRID_PERIODIC_LON | STE_FLD_NEAREST | STE_FLD_VALUES_F32)) return refuse("f->flags has unknown bits");
+    if (f->reserved != 0) return refuse("f->reserved must be 0");
     if (f->nx < 1 || f->ny < 1 || (int64_t)f->nx * (int64_t)f->ny > (int64_t)STE_GRID_MAX_CELLS)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->nx and f->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
-    if (f->nt < 1 || f->nt > STE_FIELD_MAX_SLABS)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->nt must be between 1 and STE_FIELD_MAX_SLABS (65536)");
+        return refuse("f->nx and f->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
+    if (f->nt < 1 || f->nt > STE_FIELD_MAX_SLABS) return refuse("f->nt must be between 1 and STE_FIELD_MAX_SLABS (65536)");
     if (!std::isfinite(f->lon0) || !std::isfinite(f->lat0) || !std::isfinite(f->lon_ref))
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->lon0, f->lat0 and f->lon_ref must be finite");
+        return refuse("f->lon0, f->lat0 and f->lon_ref must be finite");
     if (!std::isfinite(f->dlon) || !std::isfinite(f->dlat) || !(f->dlon >= 1e-6) || !(f->dlat >= 1e-6))
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->dlon and f->dlat must be finite and >= 1e-6 degrees");
+        return refuse("f->dlon and f->dlat must be finite and >= 1e-6 degrees");
     const bool periodic = (f->flags & STE_GRID_PERIODIC_LON) != 0;
     const double width = (double)f->nx * f->dlon;
     if (periodic) {
-        if (width != 360.0)
-            return abi_fail(STE_EINVAL, "ste_field_values_f64: STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
-        if (!(fabs(f->lon0 - f->lon_ref) <= 360.0))
-            return abi_fail(STE_EINVAL, "ste_field_values_f64: a periodic grid's lon0 must lie within lon_ref +- 360");
+        if (width != 360.0) return refuse("STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
+        if (!(fabs(f->lon0 - f->lon_ref) <= 360.0)) return refuse("a periodic grid's lon0 must lie within lon_ref +- 360");
     } else if (!(f->lon0 - f->lon_ref >= -90.0 && (f->lon0 + width) - f->lon_ref <= 90.0)) {
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
-                                    "(at most 180 degrees wide)");
+        return refuse("a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
+                      "(at most 180 degrees wide)");
     }
-    if (!std::isfinite(f->time0)) return abi_fail(STE_EINVAL, "ste_field_values_f64: f->time0 must be finite");
-    if (f->nt > 1 && !(std::isfinite(f->dtime) && f->dtime > 0.0))
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->dtime must be finite and > 0 when nt > 1");
-    if (!(f->min_cover >= 0.0 && f->min_cover <= 1.0))
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->min_cover must lie in [0, 1]");
+    if (!std::isfinite(f->time0)) return refuse("f->time0 must be finite");
+    if (f->nt > 1 && !(std::isfinite(f->dtime) && f->dtime > 0.0)) return refuse("f->dtime must be finite and > 0 when nt > 1");
+    if (!(f->min_cover >= 0.0 && f->min_cover <= 1.0)) return refuse("f->min_cover must lie in [0, 1]");
     const bool acc = f->count || f->moments || f->vmin || f->vmax;
-    if (acc && !f->vanchor)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: f->vanchor is required when count, moments, vmin or vmax is asked for");
+    if (acc && !f->vanchor) return refuse("f->vanchor is required when count, moments, vmin or vmax is asked for");
     if (!f->value && !f->cover && !f->status && !acc)
-        return abi_fail(STE_EINVAL, "ste_field_values_f64: no output asked for (value, cover, status, count, moments, vmin and vmax are all NULL)");
+        return refuse("no output asked for (value, cover, status, count, moments, vmin and vmax are all NULL)");
     FieldParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = f->nstates;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nq = (size_t)f->nqueries;
     p.nsteps = b->nsteps;
     p.states = f->states;

@@ -22,11 +22,13 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last but the walk: it switches contraction off for the rest of the file
+#include "ste_gridwalk.h"
 
 namespace ste {
 namespace {
+
+using namespace gridwalk;  // kTicksPerHour, Lines, grid_lines, grid_start, unit_clamp, step_ticks
 
 struct GridParams {
     int B, Nmax, nstates, nx, ny;
@@ -43,7 +45,6 @@ struct GridParams {
     int32_t* nbroken;  // [S][ld] or nullptr
 };
 
-constexpr double kTicksPerHour = (double)STE_GRID_TICKS_PER_HOUR;
 constexpr int kRunNone = -2;     // no piece yet
 constexpr int kRunOutside = -1;  // off the grid
 
@@ -100,47 +101,8 @@ __device__ __forceinline__ void run_add(const GridParams& p, Run& r, int ix, int
     r.acc += q;
 }
 
-// the grid lines strictly between gA and gB, in the order met: first, last, direction (none: first past last)
-struct Lines {
-    int i, iend, s;
-};
-
-__device__ __forceinline__ Lines grid_lines(double gA, double gB, int n, bool periodic) {
-    if (gB > gA) {
-        double lo = floor(gA) + 1.0, hi = ceil(gB) - 1.0;
-        if (!periodic) {
-            lo = 0.0 > lo ? 0.0 : lo;
-            hi = (double)n < hi ? (double)n : hi;
-        }
-        if (lo <= hi) return {(int)lo, (int)hi, 1};
-        return {0, -1, 1};
-    }
-    if (gB < gA) {
-        double hi = ceil(gA) - 1.0, lo = floor(gB) + 1.0;
-        if (!periodic) {
-            lo = 0.0 > lo ? 0.0 : lo;
-            hi = (double)n < hi ? (double)n : hi;
-        }
-        if (lo <= hi) return {(int)hi, (int)lo, -1};
-        return {0, 1, -1};
-    }
-    return {0, -1, 1};
-}
-
-// the index of the cell (or of the outside: -1 and n) that floor f of a grid coordinate lies in
-__device__ __forceinline__ int grid_start(double f, int n, bool periodic) {
-    if (periodic) return (int)f;
-    f = -1.0 > f ? -1.0 : f;
-    f = (double)n < f ? (double)n : f;
-    return (int)f;
-}
-
-__device__ __forceinline__ double unit_clamp(double u) {
-    u = 0.0 > u ? 0.0 : u;
-    return 1.0 < u ? 1.0 : u;
-}
-
-// a sound step that crosses grid lines: its dtq ticks split at the lines, x-lines and y-lines merged by u, ties to x
+// A sound step that crosses grid lines: its dtq ticks split at the lines, x-lines and y-lines merged by u, ties to x.  The
+// pieces of gridwalk::walk, from the same leaves, but with two call sites of the adder.
 template <bool kLds>
 __device__ void grid_walk(const GridParams& p, Run& r, double gxA, double gyA, double gxB, double gyB, double fxA, double fyA,
                           int64_t dtq) {
@@ -176,7 +138,7 @@ __device__ void grid_walk(const GridParams& p, Run& r, double gxA, double gyA, d
 template <bool kLds>
 __device__ __forceinline__ void grid_track(const GridParams& p, size_t t, size_t sample, int64_t* tk, int64_t* en) {
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1, s = sample;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     const double ref = p.lon_ref;
     Run r{kRunNone, 0, 0, 0, 0, tk, en};
@@ -199,13 +161,14 @@ __device__ __forceinline__ void grid_track(const GridParams& p, size_t t, size_t
             const double x1 = ref + wrap180(lon1 - ref);
             const double delta = wrap180(lon1 - lon);
             const double gyB = (lat1 - p.lat0) / p.dlat;  // gyA of the next step: the same expression
+            // step_sound(delta, lat, lat1, d), written out: through the function the comparisons come out in another order
             const bool sound = fabs(delta) < 90.0 && lat * 0.0 == 0.0 && lat1 * 0.0 == 0.0 && d >= 0.0 &&
                                d * kTicksPerHour < 4503599627370496.0;
             int64_t dtq = 0;
             double gxA = 0.0, gxB = 0.0, fxA = 0.0, fyA = 0.0;
             bool walk = false;
             if (sound) {
-                dtq = (int64_t)llrint(d * kTicksPerHour);
+                dtq = step_ticks(d);
                 total += dtq;
                 gxA = (ax - p.lon0) / p.dlon;
                 gxB = ((ax + delta) - p.lon0) / p.dlon;
@@ -260,36 +223,32 @@ __global__ __launch_bounds__(64) void grid_metrics(const GridParams p) {
 
 extern "C" int ste_grid_metrics_f64(const ste_ukf_batch_f64* b, const ste_grid_f64* g, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: batch pointer is NULL");
-    if (!g) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: the grid arguments (g) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!g->states) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->states is required");
-    if (g->nstates < 1) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->nstates must be >= 1");
-    if (g->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (g->flags & ~STE_GRID_PERIODIC_LON) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->flags has unknown bits");
+    const Refusal refuse{"ste_grid_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!g) return refuse("the grid arguments (g) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!g->states) return refuse("g->states is required");
+    if (int rc = refuse.nstates("g->nstates", g->nstates, " (one grid row per track of a ship)")) return rc;
+    if (g->flags & ~STE_GRID_PERIODIC_LON) return refuse("g->flags has unknown bits");
     if (g->nx < 1 || g->ny < 1 || (int64_t)g->nx * (int64_t)g->ny > (int64_t)STE_GRID_MAX_CELLS)
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->nx and g->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
+        return refuse("g->nx and g->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
     if (!std::isfinite(g->lon0) || !std::isfinite(g->lat0) || !std::isfinite(g->lon_ref))
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->lon0, g->lat0 and g->lon_ref must be finite");
+        return refuse("g->lon0, g->lat0 and g->lon_ref must be finite");
     if (!std::isfinite(g->dlon) || !std::isfinite(g->dlat) || !(g->dlon >= 1e-6) || !(g->dlat >= 1e-6))
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: g->dlon and g->dlat must be finite and >= 1e-6 degrees");
+        return refuse("g->dlon and g->dlat must be finite and >= 1e-6 degrees");
     const bool periodic = (g->flags & STE_GRID_PERIODIC_LON) != 0;
     const double width = (double)g->nx * g->dlon;
     if (periodic) {
-        if (width != 360.0)
-            return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
-        if (!(fabs(g->lon0 - g->lon_ref) <= 360.0))
-            return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: a periodic grid's lon0 must lie within lon_ref +- 360");
+        if (width != 360.0) return refuse("STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
+        if (!(fabs(g->lon0 - g->lon_ref) <= 360.0)) return refuse("a periodic grid's lon0 must lie within lon_ref +- 360");
     } else if (!(g->lon0 - g->lon_ref >= -90.0 && (g->lon0 + width) - g->lon_ref <= 90.0)) {
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
-                                    "(at most 180 degrees wide)");
+        return refuse("a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
+                      "(at most 180 degrees wide)");
     }
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: the batch's dt is required (every output is a sum of it)");
+    if (!b->dt) return refuse("the batch's dt is required (every output is a sum of it)");
     if (!g->ticks && !g->entries && !g->outside && !g->total && !g->nbroken)
-        return abi_fail(STE_EINVAL, "ste_grid_metrics_f64: no output asked for (ticks, entries, outside, total and nbroken are all NULL)");
+        return refuse("no output asked for (ticks, entries, outside, total and nbroken are all NULL)");
     GridParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
@@ -297,7 +256,7 @@ extern "C" int ste_grid_metrics_f64(const ste_ukf_batch_f64* b, const ste_grid_f
     p.nx = g->nx;
     p.ny = g->ny;
     p.periodic = periodic;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = g->states;

@@ -1,9 +1,10 @@
 // ste_gridwalk.h — the walk of a track's sound step through the cells of a regular lon / lat grid (include/ste.h, GRIDS:
 // Pieces.), for the kernels that lay tracks on such a grid: the grid lines a step crosses, the cell it starts in, the soundness
-// test of a step, and the walk itself, which hands every piece (column, row, ticks) to a sink.  ste_raster.hip is built on it;
-// ste_grid.hip still carries its own copy of these functions ("Rasters": not built), and tests/test_raster_metrics.py
-// holds the two to each other.  Every expression is evaluated as written: include this header after ste_geodesy.h, which
-// switches contraction off for the rest of the including file.
+// test of a step, and the walk itself, which hands every piece (column, row, ticks) to a sink.  ste_raster.hip is built on all
+// of it; ste_grid.hip takes the leaves (Lines, grid_lines, grid_start, unit_clamp, step_ticks) and keeps its own walk, with two
+// call sites of its adder, and the soundness test written out ("What the metric kernels share" and §9);
+// tests/test_raster_metrics.py holds the two walks to each other.  Every expression is evaluated as written: include this
+// header after ste_track.h or ste_geodesy.h, which switch contraction off for the rest of the including file.
 #pragma once
 #include <hip/hip_runtime.h>
 

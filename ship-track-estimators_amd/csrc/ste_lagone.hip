@@ -55,7 +55,7 @@ __global__ __launch_bounds__(64) void urtss_lag_one(const KParams p, const Noise
     if (g >= (size_t)p.B * (size_t)p.Nmax) return;
     const size_t t = g % (size_t)p.B;
     const int k = (int)(g / (size_t)p.B);
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     if (k >= ns) return;  // rows past the track's last step are left as they were
     const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
     double K[4][4];
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(64) void position_cov(const PCovParams p) {
         if (!(is_finite(t0) && T0 == T0 && is_finite(tq))) {
             status = STE_POS_BAD_TIME;
         } else {
-            const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+            const int ns = track_steps(p, t);
             const double tau0 = t0 + T0;
             if (tq == tau0) {
                 row = 0;
@@ -269,34 +269,33 @@ __global__ __launch_bounds__(64) void position_cov(const PCovParams p) {
 
 extern "C" int ste_track_position_cov_f64(const ste_ukf_batch_f64* b, const ste_position_cov_f64* pc, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: batch pointer is NULL");
-    if (!pc) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: the covariance arguments (pc) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!pc->qtrack) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->qtrack is required");
-    if (!pc->qtime) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->qtime is required");
+    const Refusal refuse{"ste_track_position_cov_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!pc) return refuse("the covariance arguments (pc) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!pc->qtrack) return refuse("pc->qtrack is required");
+    if (!pc->qtime) return refuse("pc->qtime is required");
     if (!pc->knots)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->knots is required (what ste_track_positions_f64 left in its workspace, [Nmax+1][track_stride])");
+        return refuse("pc->knots is required (what ste_track_positions_f64 left in its workspace, [Nmax+1][track_stride])");
     if (pc->nqueries < 1 || pc->nqueries > STE_POSITIONS_MAX_QUERIES)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
+        return refuse("pc->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
     if (pc->flags & ~(STE_PCOV_FULL | STE_PCOV_LAG1_POSITION))
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->flags has unknown bits (STE_PCOV_FULL and STE_PCOV_LAG1_POSITION are the two)");
-    if (pc->reserved != 0) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->reserved must be 0");
+        return refuse("pc->flags has unknown bits (STE_PCOV_FULL and STE_PCOV_LAG1_POSITION are the two)");
+    if (pc->reserved != 0) return refuse("pc->reserved must be 0");
     const bool full = (pc->flags & STE_PCOV_FULL) != 0, lag_pos = (pc->flags & STE_PCOV_LAG1_POSITION) != 0;
-    if (full && lag_pos)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: STE_PCOV_FULL needs the 16-entry lag1, not the position form (STE_PCOV_LAG1_POSITION)");
+    if (full && lag_pos) return refuse("STE_PCOV_FULL needs the 16-entry lag1, not the position form (STE_PCOV_LAG1_POSITION)");
     if (!pc->pcov && !pc->step && !pc->frac && !pc->status)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: no output asked for (pcov, step, frac and status are all NULL)");
-    if (pc->pcov && !pc->cov) return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->cov is required with pcov");
+        return refuse("no output asked for (pcov, step, frac and status are all NULL)");
+    if (pc->pcov && !pc->cov) return refuse("pc->cov is required with pcov");
     if (pc->pcov && !pc->lag1 && b->Nmax > 0)
-        return abi_fail(STE_EINVAL, "ste_track_position_cov_f64: pc->lag1 is required with pcov when Nmax > 0 (ste_urtss_lag_one_f64 writes it)");
+        return refuse("pc->lag1 is required with pcov when Nmax > 0 (ste_urtss_lag_one_f64 writes it)");
     PCovParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.packed = (b->flags & STE_FLAG_PACKED_COV) ? 1 : 0;
     p.lag_rows = lag_pos ? 4 : 16;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nq = (size_t)pc->nqueries;
     p.nsteps = b->nsteps;
     p.qtrack = pc->qtrack;

@@ -27,8 +27,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 #ifndef STE_LINE_CHUNK
 #define STE_LINE_CHUNK 64  // segments staged at a time: one vertex per lane and one more ("Lines")
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(64) STE_LINE_OCCUPANCY void line_metrics(const Line
     bool tbad = !is_finite(t0);
     // a bad line is walked by the block of line 0 alone, for the track's own outputs
     const bool walk = live && !tbad && (!lbad || m == 0);
-    const int ns = walk ? min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax) : 0;
+    const int ns = walk ? track_steps(p, t) : 0;
     int nsmax = ns;  // the wave's largest: every lane takes part in the staging of every step
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) nsmax = max(nsmax, __shfl_xor(nsmax, off, 64));
@@ -295,37 +294,33 @@ extern "C" int ste_line_chunk(void) { return ste::kLineChunk; }
 
 extern "C" int ste_line_metrics_f64(const ste_ukf_batch_f64* b, const ste_line_f64* li, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: batch pointer is NULL");
-    if (!li) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: the line arguments (li) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!li->states) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->states is required");
-    if (!li->vert) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->vert is required");
-    if (!li->first) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->first is required (nlines + 1 vertex offsets)");
-    if (!li->lon_ref) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->lon_ref is required (one meridian per line)");
-    if (li->nstates < 1) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->nstates must be >= 1");
-    if (li->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (li->nlines < 1 || li->nlines > STE_LINES_MAX)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->nlines must be between 1 and STE_LINES_MAX (4096)");
+    const Refusal refuse{"ste_line_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!li) return refuse("the line arguments (li) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!li->states) return refuse("li->states is required");
+    if (!li->vert) return refuse("li->vert is required");
+    if (!li->first) return refuse("li->first is required (nlines + 1 vertex offsets)");
+    if (!li->lon_ref) return refuse("li->lon_ref is required (one meridian per line)");
+    if (int rc = refuse.nstates("li->nstates", li->nstates, " (one grid row per track of a ship)")) return rc;
+    if (li->nlines < 1 || li->nlines > STE_LINES_MAX) return refuse("li->nlines must be between 1 and STE_LINES_MAX (4096)");
     if (li->nvert < 2 || li->nvert > STE_LINE_MAX_VERT_TOTAL)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->nvert must be between 2 and STE_LINE_MAX_VERT_TOTAL (1048576)");
-    if (li->min_dist && li->model != STE_PREP_SPHERE && li->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->model must be STE_PREP_SPHERE or STE_PREP_WGS84 when min_dist is asked for");
-    if (li->flags != 0) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->flags must be 0");
-    if (li->reserved != 0) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: li->reserved must be 0");
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_line_metrics_f64: the batch's dt is required (the clock is made of its sums)");
+        return refuse("li->nvert must be between 2 and STE_LINE_MAX_VERT_TOTAL (1048576)");
+    if (li->min_dist && refuse.model("li->model", li->model, " when min_dist is asked for")) return STE_EINVAL;
+    if (li->flags != 0) return refuse("li->flags must be 0");
+    if (li->reserved != 0) return refuse("li->reserved must be 0");
+    if (!b->dt) return refuse("the batch's dt is required (the clock is made of its sums)");
     if (!li->min_dist && !li->min_time && !li->min_seg && !li->min_frac && !li->ncross && !li->net_cross && !li->first_cross &&
         !li->last_cross && !li->sound_time && !li->nbroken && !li->track_status && !li->line_status)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: no output asked for (min_dist, min_time, min_seg, min_frac, ncross, net_cross, first_cross, last_cross, sound_time, nbroken, track_status and line_status are all NULL)");
+        return refuse("no output asked for (min_dist, min_time, min_seg, min_frac, ncross, net_cross, first_cross, last_cross, sound_time, nbroken, track_status and line_status are all NULL)");
     LineParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = li->nstates;
     p.nlines = li->nlines;
     p.nvert = li->nvert;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = li->states;
@@ -347,7 +342,7 @@ extern "C" int ste_line_metrics_f64(const ste_ukf_batch_f64* b, const ste_line_f
     p.line_status = li->line_status;
     const uint64_t nblocks = (uint64_t)li->nlines * (uint64_t)(((int64_t)b->B + 63) / 64);
     if (nblocks > 0x7fffffffull)
-        return abi_fail(STE_EINVAL, "ste_line_metrics_f64: ceil(B / 64) * nlines exceeds 2^31 - 1 blocks: split the lines or the tracks over calls");
+        return refuse("ceil(B / 64) * nlines exceeds 2^31 - 1 blocks: split the lines or the tracks over calls");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool cross = li->ncross || li->net_cross || li->first_cross || li->last_cross;
     const int model = li->min_dist ? li->model : kNoLeg;

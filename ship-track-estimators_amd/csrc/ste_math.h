@@ -19,6 +19,16 @@ constexpr double kRotTol2 = 4.930380657631324e-32;     // (2^-52)^2
 
 #define STE_UNROLL _Pragma("unroll")
 
+// The steps of track t that the kernels downstream of the smoother walk: p.nsteps[t] (absent: p.Nmax) clamped to 0 .. Nmax, so
+// a count that is not the batch's reads no row past the arrays.  p is the kernel's parameter struct, by reference: with nsteps
+// and Nmax passed as values several kernels compile to other code than with the expression written out.  Here and not in
+// ste_track.h with the rest of what those kernels share, because ste_sample.hip needs it and keeps contraction on at file
+// scope, which ste_track.h switches off.
+template <class Params, class Index>
+__device__ __forceinline__ int track_steps(const Params& p, Index t) {
+    return min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+}
+
 // Filter constants shared by every track: kernel arguments, so they sit in SGPRs / the scalar cache.
 struct Mats {
     double fan_scale, w0, wi;

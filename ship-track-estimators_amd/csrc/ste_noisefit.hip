@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void noise_moments(const MomentParams p) {
     const size_t ld = p.ld;
     int tst = 0;
     if (p.status && (p.status[t] & STE_STATUS_NAN)) tst = STE_NOISE_TRACK_NAN;
-    const int ns = tst ? 0 : min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = tst ? 0 : track_steps(p, t);
     constexpr int kCovRows = kPacked ? 10 : 16;
 
     double S[10], vs[4] = {0.0, 0.0, 0.0, 0.0};
@@ -255,29 +255,28 @@ __global__ __launch_bounds__(64) void noise_mstep_tracks(const MstepParams p) {
 
 extern "C" int ste_ukf_noise_moments_f64(const ste_ukf_batch_f64* b, const ste_noise_moments_f64* nm, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: batch pointer is NULL");
-    if (!nm) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: the moment arguments (nm) are NULL");
-    if (b->B <= 0 || b->Nmax < 0 || b->Tmax < 1)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: B must be > 0, Nmax >= 0 and Tmax >= 1");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!nm->moments || !nm->count) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: nm->moments and nm->count are required");
-    if (nm->flags != 0 || nm->reserved != 0) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: nm->flags and nm->reserved must be 0");
-    if (!b->H) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: the batch's H is required");
+    const Refusal refuse{"ste_ukf_noise_moments_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!nm) return refuse("the moment arguments (nm) are NULL");
+    if (b->B <= 0 || b->Nmax < 0 || b->Tmax < 1) return refuse("B must be > 0, Nmax >= 0 and Tmax >= 1");
+    if (int rc = refuse.stride(b)) return rc;
+    if (!nm->moments || !nm->count) return refuse("nm->moments and nm->count are required");
+    if (nm->flags != 0 || nm->reserved != 0) return refuse("nm->flags and nm->reserved must be 0");
+    if (!b->H) return refuse("the batch's H is required");
     if (!b->sm_mean || !b->sm_cov)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: sm_mean and sm_cov are required (the moments are taken about the smoothed track)");
-    if (!b->z || !b->upd_idx) return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: z and upd_idx are required");
+        return refuse("sm_mean and sm_cov are required (the moments are taken about the smoothed track)");
+    if (!b->z || !b->upd_idx) return refuse("z and upd_idx are required");
     if (b->flags & STE_FLAG_ROBUST)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: STE_FLAG_ROBUST is refused (the filter rescales R per update; the M-step is not defined for it)");
+        return refuse("STE_FLAG_ROBUST is refused (the filter rescales R per update; the M-step is not defined for it)");
     if (b->noise_upd)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: recorded noise is refused (noise_upd: the update saw z + noise, the residual is taken from z)");
+        return refuse("recorded noise is refused (noise_upd: the update saw z + noise, the residual is taken from z)");
     if (b->step_begin != 0 || (b->step_end != 0 && b->step_end != b->Nmax))
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_moments_f64: time slices are refused (step_begin / step_end): the moments are those of whole passes");
+        return refuse("time slices are refused (step_begin / step_end): the moments are those of whole passes");
     MomentParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.Tmax = b->Tmax;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     for (int i = 0; i < 16; ++i) p.H[i] = b->H[i];
     p.nsteps = b->nsteps;
     p.upd_idx = b->upd_idx;
@@ -298,20 +297,21 @@ extern "C" int ste_ukf_noise_moments_f64(const ste_ukf_batch_f64* b, const ste_n
 
 extern "C" int ste_ukf_noise_mstep_f64(const ste_noise_mstep_f64* ms, void* stream) {
     using namespace ste;
-    if (!ms) return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: the M-step arguments (ms) are NULL");
+    const Refusal refuse{"ste_ukf_noise_mstep_f64"};
+    if (!ms) return refuse("the M-step arguments (ms) are NULL");
     if (ms->ntracks <= 0 || ms->ngroups <= 0 || ms->nmembers < 0)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ntracks and ngroups must be > 0 and nmembers >= 0");
-    if (ms->ld != 0 && ms->ld < ms->ntracks) return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ld must be 0 or >= ntracks");
-    if (!ms->moments || !ms->count) return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ms->moments and ms->count are required");
+        return refuse("ntracks and ngroups must be > 0 and nmembers >= 0");
+    if (ms->ld != 0 && ms->ld < ms->ntracks) return refuse("ld must be 0 or >= ntracks");
+    if (!ms->moments || !ms->count) return refuse("ms->moments and ms->count are required");
     if (!ms->R_group || !ms->n_group || !ms->group_status || !ms->R_tracks)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ms->R_group, ms->n_group, ms->group_status and ms->R_tracks are required");
+        return refuse("ms->R_group, ms->n_group, ms->group_status and ms->R_tracks are required");
     if (!ms->group_offsets != !ms->group_members)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: group_offsets and group_members come together (both NULL: every track a group of its own)");
+        return refuse("group_offsets and group_members come together (both NULL: every track a group of its own)");
     if (!ms->group_offsets && ms->ngroups != ms->ntracks)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: without groups every track is a group: ngroups must equal ntracks");
+        return refuse("without groups every track is a group: ngroups must equal ntracks");
     if (ms->structure != STE_NOISE_FIT_SCALAR && ms->structure != STE_NOISE_FIT_DIAG2 && ms->structure != STE_NOISE_FIT_BLOCK2)
-        return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ms->structure must be STE_NOISE_FIT_SCALAR, _DIAG2 or _BLOCK2");
-    if (ms->reserved != 0) return abi_fail(STE_EINVAL, "ste_ukf_noise_mstep_f64: ms->reserved must be 0");
+        return refuse("ms->structure must be STE_NOISE_FIT_SCALAR, _DIAG2 or _BLOCK2");
+    if (ms->reserved != 0) return refuse("ms->reserved must be 0");
     MstepParams p;
     p.ntracks = ms->ntracks;
     p.ngroups = ms->ngroups;

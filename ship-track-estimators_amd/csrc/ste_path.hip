@@ -22,8 +22,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -41,31 +40,6 @@ struct PathParams {
     int32_t* ncross;             // [S][ld] or nullptr
 };
 
-// A row as its leg function wants it.  Sphere: radians and cos(lat), converted once per row.  WGS84: degrees.
-template <int kModel>
-struct PathPoint {
-    double lon, lat, c;
-};
-template <int kModel>
-__device__ __forceinline__ PathPoint<kModel> path_point(double lon_deg, double lat_deg) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double lat = lat_deg * kDeg2Rad;
-        return {lon_deg * kDeg2Rad, lat, cos(lat)};
-    } else {
-        return {lon_deg, lat_deg, 0.0};
-    }
-}
-template <int kModel>
-__device__ __forceinline__ double path_leg_km(const PathPoint<kModel>& a, const PathPoint<kModel>& b) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        return sphere_dist_km(a.lon, a.lat, a.c, b.lon, b.lat, b.c);
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (a.lon + a.lat + b.lon + b.lat) * 0.0;
-        return wgs84_leg(a.lon, a.lat, b.lon, b.lat).dist_km + poison;
-    }
-}
-
 // signed offset of a row from the line, degrees: lat - v for a parallel, wrap180(lon - v) for a meridian
 __device__ __forceinline__ double line_offset(int axis, double lon_deg, double lat_deg, double v) {
     return axis == 1 ? lat_deg - v : wrap180(lon_deg - v);
@@ -76,12 +50,12 @@ __global__ __launch_bounds__(64) void path_metrics(const PathParams p) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= (size_t)p.B) return;
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1, s = blockIdx.y;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     double* cum = p.cumdist ? p.cumdist + (s * rows) * ld + t : nullptr;
 
     double lon = st[0], lat = st[ld];
-    PathPoint<kModel> cur = path_point<kModel>(lon, lat);
+    TrackPoint<kModel> cur = track_point<kModel>(lon, lat);
     double dist = 0.0;
     if (cum) cum[0] = 0.0;
 
@@ -109,8 +83,8 @@ __global__ __launch_bounds__(64) void path_metrics(const PathParams p) {
             nlat = st[(r * 4 + 1) * ld];
             if constexpr (kLine) ndt = p.dt[((size_t)k + 1) * ld + t];
         }
-        const PathPoint<kModel> nxt = path_point<kModel>(lon, lat);
-        dist += path_leg_km<kModel>(cur, nxt);
+        const TrackPoint<kModel> nxt = track_point<kModel>(lon, lat);
+        dist += track_leg_km<kModel>(cur, nxt);
         if (cum) cum[((size_t)k + 1) * ld] = dist;
         cur = nxt;
         if constexpr (kLine) {
@@ -145,33 +119,29 @@ void launch_path(const PathParams& p, hipStream_t s) {
 
 extern "C" int ste_path_metrics_f64(const ste_ukf_batch_f64* b, const ste_path_f64* pm, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: batch pointer is NULL");
-    if (!pm) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: the path arguments (pm) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!pm->states) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->states is required");
-    if (pm->nstates < 1) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->nstates must be >= 1");
-    if (pm->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (pm->model != STE_PREP_SPHERE && pm->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->model must be STE_PREP_SPHERE or STE_PREP_WGS84");
+    const Refusal refuse{"ste_path_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!pm) return refuse("the path arguments (pm) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!pm->states) return refuse("pm->states is required");
+    if (int rc = refuse.nstates("pm->nstates", pm->nstates, " (one grid row per track of a ship)")) return rc;
+    if (int rc = refuse.model("pm->model", pm->model)) return rc;
     if (pm->line_axis < -1 || pm->line_axis > 1)
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->line_axis must be -1 (no line), 0 (meridian) or 1 (parallel)");
-    if (pm->reserved != 0) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->reserved must be 0");
+        return refuse("pm->line_axis must be -1 (no line), 0 (meridian) or 1 (parallel)");
+    if (pm->reserved != 0) return refuse("pm->reserved must be 0");
     const bool line = pm->line_axis >= 0;
-    if (line && !pm->line_value) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: a line needs pm->line_value");
-    if (line && !b->dt) return abi_fail(STE_EINVAL, "ste_path_metrics_f64: a line needs the batch's dt (crossing times are sums of it)");
-    if (!line && (pm->cross_time || pm->ncross))
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: pm->cross_time and pm->ncross need a line (line_axis 0 or 1)");
+    if (line && !pm->line_value) return refuse("a line needs pm->line_value");
+    if (line && !b->dt) return refuse("a line needs the batch's dt (crossing times are sums of it)");
+    if (!line && (pm->cross_time || pm->ncross)) return refuse("pm->cross_time and pm->ncross need a line (line_axis 0 or 1)");
     if (!pm->dist && !pm->cumdist && !pm->cross_time && !pm->ncross)
-        return abi_fail(STE_EINVAL, "ste_path_metrics_f64: no output asked for (dist, cumdist, cross_time and ncross are all NULL)");
+        return refuse("no output asked for (dist, cumdist, cross_time and ncross are all NULL)");
     PathParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = pm->nstates;
     p.axis = pm->line_axis;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = pm->states;

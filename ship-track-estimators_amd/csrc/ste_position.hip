@@ -26,8 +26,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -62,7 +61,7 @@ constexpr size_t kLaneLoopQueries = (size_t)1 << 14;  // 256 waves, one for ever
 __global__ __launch_bounds__(64) void position_knots(const PosParams p) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= (size_t)p.B) return;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     double T = 0.0;
     bool bad = false;
     for (int k = 0; k < ns; ++k) {
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(64) void position_query(const PosParams p) {
         if (!(is_finite(t0) && T0 == T0 && is_finite(tq))) {
             status = STE_POS_BAD_TIME;
         } else {
-            const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+            const int ns = track_steps(p, t);
             const double tau0 = t0 + T0;
             if (tq == tau0) {
                 row = 0;
@@ -244,35 +243,31 @@ __global__ __launch_bounds__(64) void position_query(const PosParams p) {
 
 extern "C" int ste_track_positions_f64(const ste_ukf_batch_f64* b, const ste_positions_f64* po, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_track_positions_f64: batch pointer is NULL");
-    if (!po) return abi_fail(STE_EINVAL, "ste_track_positions_f64: the position arguments (po) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_track_positions_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!po->states) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->states is required");
-    if (!po->qtrack) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->qtrack is required");
-    if (!po->qtime) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->qtime is required");
-    if (!po->knots) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->knots is required (the workspace of the knot times, [Nmax+1][track_stride])");
-    if (po->nstates < 1) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->nstates must be >= 1");
-    if (po->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->nstates is limited to 65535 per call (one grid row per sample)");
+    const Refusal refuse{"ste_track_positions_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!po) return refuse("the position arguments (po) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!po->states) return refuse("po->states is required");
+    if (!po->qtrack) return refuse("po->qtrack is required");
+    if (!po->qtime) return refuse("po->qtime is required");
+    if (!po->knots) return refuse("po->knots is required (the workspace of the knot times, [Nmax+1][track_stride])");
+    if (int rc = refuse.nstates("po->nstates", po->nstates, " (one grid row per sample)")) return rc;
     if (po->nqueries < 1 || po->nqueries > STE_POSITIONS_MAX_QUERIES)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
-    if (po->flags & ~STE_POS_REUSE_KNOTS) return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->flags has unknown bits (STE_POS_REUSE_KNOTS is the only one)");
+        return refuse("po->nqueries must be between 1 and STE_POSITIONS_MAX_QUERIES (2^26)");
+    if (po->flags & ~STE_POS_REUSE_KNOTS) return refuse("po->flags has unknown bits (STE_POS_REUSE_KNOTS is the only one)");
     const bool reuse = (po->flags & STE_POS_REUSE_KNOTS) != 0;
-    if (!reuse && !b->dt)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: the batch's dt is required without STE_POS_REUSE_KNOTS (the knots are its sums)");
+    if (!reuse && !b->dt) return refuse("the batch's dt is required without STE_POS_REUSE_KNOTS (the knots are its sums)");
     if ((po->count != nullptr) != (po->moments != nullptr))
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->count and po->moments go together (both or neither)");
-    if (po->count && !po->anchor)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: po->anchor is required when count and moments are asked for");
+        return refuse("po->count and po->moments go together (both or neither)");
+    if (po->count && !po->anchor) return refuse("po->anchor is required when count and moments are asked for");
     if (!po->lon && !po->lat && !po->speed && !po->heading && !po->step && !po->frac && !po->status && !po->count)
-        return abi_fail(STE_EINVAL, "ste_track_positions_f64: no output asked for (lon, lat, speed, heading, step, frac, status, count and moments are all NULL)");
+        return refuse("no output asked for (lon, lat, speed, heading, step, frac, status, count and moments are all NULL)");
     PosParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = po->nstates;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nq = (size_t)po->nqueries;
     p.nsteps = b->nsteps;
     p.dt = b->dt;

@@ -28,8 +28,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last but the walk: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last but the walk: it switches contraction off for the rest of the file
 #include "ste_gridwalk.h"
 
 #ifndef STE_RASTER_EAGER
@@ -195,7 +194,7 @@ __device__ __forceinline__ double row_cell_value(const RasterParams& p, const do
 template <bool kThr, bool kRows>
 __device__ __forceinline__ void raster_track(const RasterParams& p, size_t t, size_t sample, const double* vals) {
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1, s = sample;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     double* rv = kRows ? p.row_value + (s * rows) * ld + t : nullptr;  // row k: rv[k * ld]
     const double ref = p.lon_ref;
@@ -312,56 +311,51 @@ int launch_raster(const RasterParams& p, const RasterOut& out, hipStream_t strea
 
 extern "C" int ste_raster_metrics_f64(const ste_ukf_batch_f64* b, const ste_raster_f64* r, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: batch pointer is NULL");
-    if (!r) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: the raster arguments (r) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!r->states) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->states is required");
-    if (r->nstates < 1) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->nstates must be >= 1");
-    if (r->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->nstates is limited to 65535 per call (one grid row per track of a ship)");
+    const Refusal refuse{"ste_raster_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!r) return refuse("the raster arguments (r) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!r->states) return refuse("r->states is required");
+    if (int rc = refuse.nstates("r->nstates", r->nstates, " (one grid row per track of a ship)")) return rc;
     if (r->flags & ~(STE_GRID_PERIODIC_LON | STE_RASTER_BELOW | STE_RASTER_NO_THRESHOLD))
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->flags has unknown bits");
+        return refuse("r->flags has unknown bits");
     if (r->nx < 1 || r->ny < 1 || (int64_t)r->nx * (int64_t)r->ny > (int64_t)STE_GRID_MAX_CELLS)
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->nx and r->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
+        return refuse("r->nx and r->ny must be >= 1 and nx * ny <= STE_GRID_MAX_CELLS (2^26)");
     if (!std::isfinite(r->lon0) || !std::isfinite(r->lat0) || !std::isfinite(r->lon_ref))
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->lon0, r->lat0 and r->lon_ref must be finite");
+        return refuse("r->lon0, r->lat0 and r->lon_ref must be finite");
     if (!std::isfinite(r->dlon) || !std::isfinite(r->dlat) || !(r->dlon >= 1e-6) || !(r->dlat >= 1e-6))
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->dlon and r->dlat must be finite and >= 1e-6 degrees");
+        return refuse("r->dlon and r->dlat must be finite and >= 1e-6 degrees");
     const bool periodic = (r->flags & STE_GRID_PERIODIC_LON) != 0;
     const double width = (double)r->nx * r->dlon;
     if (periodic) {
-        if (width != 360.0)
-            return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
-        if (!(fabs(r->lon0 - r->lon_ref) <= 360.0))
-            return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: a periodic grid's lon0 must lie within lon_ref +- 360");
+        if (width != 360.0) return refuse("STE_GRID_PERIODIC_LON needs nx * dlon == 360 exactly");
+        if (!(fabs(r->lon0 - r->lon_ref) <= 360.0)) return refuse("a periodic grid's lon0 must lie within lon_ref +- 360");
     } else if (!(r->lon0 - r->lon_ref >= -90.0 && (r->lon0 + width) - r->lon_ref <= 90.0)) {
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
-                                    "(at most 180 degrees wide)");
+        return refuse("a grid without STE_GRID_PERIODIC_LON must lie within lon_ref +- 90 "
+                      "(at most 180 degrees wide)");
     }
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: the batch's dt is required (every output is a sum of it)");
-    if (!r->values) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->values is required");
+    if (!b->dt) return refuse("the batch's dt is required (every output is a sum of it)");
+    if (!r->values) return refuse("r->values is required");
     const bool thr = (r->flags & STE_RASTER_NO_THRESHOLD) == 0;
     const bool hits = r->hit_ticks || r->hit_first || r->nhit || r->nhit_long || r->hit_longest;
     if (thr) {
-        if (r->threshold != r->threshold)
-            return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->threshold is NaN (STE_RASTER_NO_THRESHOLD says there is none)");
-        if (r->min_ticks < 0) return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: r->min_ticks must be >= 0");
+        if (r->threshold != r->threshold) return refuse("r->threshold is NaN (STE_RASTER_NO_THRESHOLD says there is none)");
+        if (r->min_ticks < 0) return refuse("r->min_ticks must be >= 0");
     } else if (hits) {
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: with STE_RASTER_NO_THRESHOLD the hit outputs (hit_ticks, hit_first, "
-                                    "nhit, nhit_long, hit_longest) must be NULL");
+        return refuse("with STE_RASTER_NO_THRESHOLD the hit outputs (hit_ticks, hit_first, "
+                      "nhit, nhit_long, hit_longest) must be NULL");
     }
     if (!r->total && !r->outside && !r->nbroken && !r->valid && !r->nodata && !r->wsum && !r->vmin && !r->vmax && !r->tmin &&
         !r->tmax && !hits && !r->row_value)
-        return abi_fail(STE_EINVAL, "ste_raster_metrics_f64: no output asked for (every output pointer is NULL)");
+        return refuse("no output asked for (every output pointer is NULL)");
     RasterParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = r->nstates;
     p.g = {r->nx, r->ny, periodic};
     p.below = (r->flags & STE_RASTER_BELOW) != 0;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = r->states;

@@ -23,8 +23,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -87,7 +86,7 @@ __device__ bool row_inside(const double* __restrict__ vx, const double* __restri
     return c;
 }
 
-// the leg of path_metrics between two rows given in degrees
+// the leg of path_metrics between two rows given in degrees: leg_km_deg (ste_geodesy.h) without its poison term, on purpose
 template <int kModel>
 __device__ __forceinline__ double region_leg_km(double lon1, double lat1, double lon2, double lat2) {
     if constexpr (kModel == STE_PREP_SPHERE) {
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(64) void region_metrics(const RegionParams p) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= (size_t)p.B) return;
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1, s = blockIdx.y;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     uint8_t* mask = p.inside ? p.inside + (s * rows) * ld + t : nullptr;
     const bool timed = p.dt != nullptr;
@@ -241,32 +240,29 @@ void launch_region(const RegionParams& p, hipStream_t s) {
 
 extern "C" int ste_region_metrics_f64(const ste_ukf_batch_f64* b, const ste_region_f64* rg, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: batch pointer is NULL");
-    if (!rg) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: the region arguments (rg) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!rg->states) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->states is required");
-    if (!rg->vert) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->vert is required");
-    if (rg->nstates < 1) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->nstates must be >= 1");
-    if (rg->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->nstates is limited to 65535 per call (one grid row per track of a ship)");
+    const Refusal refuse{"ste_region_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!rg) return refuse("the region arguments (rg) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!rg->states) return refuse("rg->states is required");
+    if (!rg->vert) return refuse("rg->vert is required");
+    if (int rc = refuse.nstates("rg->nstates", rg->nstates, " (one grid row per track of a ship)")) return rc;
     if (rg->nvert < 3 || rg->nvert > STE_REGION_MAX_VERT)
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->nvert must be between 3 and STE_REGION_MAX_VERT (1024)");
-    if (rg->reserved != 0) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->reserved must be 0");
-    if (!std::isfinite(rg->lon_ref)) return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->lon_ref must be finite");
-    if (rg->dist_inside && rg->model != STE_PREP_SPHERE && rg->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: rg->model must be STE_PREP_SPHERE or STE_PREP_WGS84 when dist_inside is asked for");
+        return refuse("rg->nvert must be between 3 and STE_REGION_MAX_VERT (1024)");
+    if (rg->reserved != 0) return refuse("rg->reserved must be 0");
+    if (!std::isfinite(rg->lon_ref)) return refuse("rg->lon_ref must be finite");
+    if (rg->dist_inside && refuse.model("rg->model", rg->model, " when dist_inside is asked for")) return STE_EINVAL;
     if (!b->dt && (rg->time_inside || rg->first_entry))
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: time_inside and first_entry need the batch's dt (they are sums of it)");
+        return refuse("time_inside and first_entry need the batch's dt (they are sums of it)");
     if (!rg->time_inside && !rg->first_entry && !rg->nenter && !rg->nbroken && !rg->dist_inside && !rg->inside)
-        return abi_fail(STE_EINVAL, "ste_region_metrics_f64: no output asked for (time_inside, first_entry, nenter, nbroken, dist_inside and inside are all NULL)");
+        return refuse("no output asked for (time_inside, first_entry, nenter, nbroken, dist_inside and inside are all NULL)");
     RegionParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = rg->nstates;
     p.nvert = rg->nvert;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = rg->states;

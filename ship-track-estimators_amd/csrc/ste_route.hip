@@ -31,8 +31,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 #ifndef STE_ROUTE_LDS_COLS
 #define STE_ROUTE_LDS_COLS 512  // columns of the boundary row kept in LDS ("Routes")
@@ -65,26 +64,6 @@ struct RouteParams {
     int32_t* status;        // [S][P] or nullptr
 };
 
-// the value of lane l - 1; lane 0 gets something its caller replaces
-__device__ __forceinline__ int lane_up(int x) {
-#ifdef STE_ROUTE_DPP  // a DPP wave shift instead of ds_bpermute, for timing ("Routes")
-    return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false);
-#else
-    return __shfl_up(x, 1, 64);
-#endif
-}
-__device__ __forceinline__ double lane_up(double x) {
-    return __hiloint2double(lane_up(__double2hiint(x)), lane_up(__double2loint(x)));
-}
-
-__device__ __forceinline__ void unit_vector(double lon, double lat, double& x, double& y, double& z) {
-    const double lam = lon * kDeg2Rad, phi = lat * kDeg2Rad;
-    const double c = cos(phi);
-    x = c * cos(lam);
-    y = c * sin(lam);
-    z = sin(phi);
-}
-
 template <int kModel, bool kDtw>
 __global__ __launch_bounds__(64) void route_metrics(const RouteParams p) {
     __shared__ double rx[kRing], ry[kRing], rz[kRing];
@@ -113,8 +92,8 @@ __global__ __launch_bounds__(64) void route_metrics(const RouteParams p) {
         if (i < 0 || i >= p.B || j < 0 || j >= p.B) {
             status = STE_ROUTE_BAD_INDEX;  // nothing of the pair is read
         } else {
-            nsi = min(max(p.nsteps ? p.nsteps[i] : p.Nmax, 0), p.Nmax);
-            nsj = min(max(p.nsteps ? p.nsteps[j] : p.Nmax, 0), p.Nmax);
+            nsi = track_steps(p, i);
+            nsj = track_steps(p, j);
             if (band > 0 && (nsi > nsj ? nsi - nsj : nsj - nsi) > band) status = STE_ROUTE_NO_PATH;
         }
         const double* sti = p.states + (s * rows * 4) * ld + (size_t)(status ? 0 : i);  // row k, component c: sti[(k * 4 + c) * ld]
@@ -287,36 +266,32 @@ extern "C" size_t ste_route_workspace(int32_t Nmax, int32_t nstates, int64_t npa
 
 extern "C" int ste_route_metrics_f64(const ste_ukf_batch_f64* b, const ste_route_f64* ro, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: batch pointer is NULL");
-    if (!ro) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: the route arguments (ro) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->Nmax > kMaxNmax)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: Nmax is limited to 2^31 - 257 (columns and ticks are counted in int32)");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!ro->states) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->states is required");
-    if (!ro->pairs) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->pairs is required");
-    if (ro->nstates < 1) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->nstates must be >= 1");
-    if (ro->nstates > 65535) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->nstates is limited to 65535 per call");
+    const Refusal refuse{"ste_route_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!ro) return refuse("the route arguments (ro) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (b->Nmax > kMaxNmax) return refuse("Nmax is limited to 2^31 - 257 (columns and ticks are counted in int32)");
+    if (int rc = refuse.stride(b)) return rc;
+    if (!ro->states) return refuse("ro->states is required");
+    if (!ro->pairs) return refuse("ro->pairs is required");
+    if (int rc = refuse.nstates("ro->nstates", ro->nstates)) return rc;
     if (ro->npairs < 1 || ro->npairs > STE_ROUTE_MAX_PAIRS)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->npairs must be between 1 and STE_ROUTE_MAX_PAIRS (2^26)");
-    if (ro->frechet && ro->model != STE_PREP_SPHERE && ro->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->model must be STE_PREP_SPHERE or STE_PREP_WGS84 when frechet is asked for");
-    if (ro->band < 0) return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->band must be >= 0 (0 = no band)");
-    if ((ro->flags & ~STE_ROUTE_REVERSE_J) != 0)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->flags must be 0 or STE_ROUTE_REVERSE_J");
+        return refuse("ro->npairs must be between 1 and STE_ROUTE_MAX_PAIRS (2^26)");
+    if (ro->frechet && refuse.model("ro->model", ro->model, " when frechet is asked for")) return STE_EINVAL;
+    if (ro->band < 0) return refuse("ro->band must be >= 0 (0 = no band)");
+    if ((ro->flags & ~STE_ROUTE_REVERSE_J) != 0) return refuse("ro->flags must be 0 or STE_ROUTE_REVERSE_J");
     if (!ro->frechet && !ro->frechet_at && !ro->dtw && !ro->dtw_len && !ro->status)
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: no output asked for (frechet, frechet_at, dtw, dtw_len and status are all NULL)");
+        return refuse("no output asked for (frechet, frechet_at, dtw, dtw_len and status are all NULL)");
     const size_t need = ste_route_workspace(b->Nmax, ro->nstates, ro->npairs);
     if (need > 0 && (!ro->work || ro->work_bytes < 0 || (uint64_t)ro->work_bytes < (uint64_t)need))
-        return abi_fail(STE_EINVAL, "ste_route_metrics_f64: ro->work is required with work_bytes >= ste_route_workspace(Nmax, nstates, npairs) when Nmax + 1 exceeds ste_route_lds_cols()");
+        return refuse("ro->work is required with work_bytes >= ste_route_workspace(Nmax, nstates, npairs) when Nmax + 1 exceeds ste_route_lds_cols()");
     RouteParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = ro->nstates;
     p.band = ro->band > b->Nmax ? 0 : ro->band;  // a band that wide admits every cell
     p.reverse = (ro->flags & STE_ROUTE_REVERSE_J) != 0;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.npairs = (size_t)ro->npairs;
     p.nsteps = b->nsteps;
     p.states = ro->states;

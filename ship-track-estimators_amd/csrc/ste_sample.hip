@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64) void urtss_sample_coef(const KParams p, const N
     if (g >= (size_t)p.B * ((size_t)p.Nmax + 1)) return;
     const size_t t = g % (size_t)p.B;
     const int k = (int)(g / (size_t)p.B);
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     if (k > ns) return;
     const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
     double* cw = sp.coef + ((size_t)k * kCoefElems) * B + t;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64) void urtss_sample_recur(const KParams p, const 
     const size_t B = (size_t)p.ld;
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= (size_t)p.B) return;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const size_t s0 = (size_t)blockIdx.y * kSpl;
     const int nloc = min(kSpl, sp.nsamples - (int)s0);
     const size_t rows = (size_t)p.Nmax + 1;

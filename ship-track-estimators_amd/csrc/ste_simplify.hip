@@ -31,8 +31,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 #ifndef STE_SIMPLIFY_LDS_ROWS
 #define STE_SIMPLIFY_LDS_ROWS 2048  // rows of a track kept in LDS ("Simplification")
@@ -69,14 +68,6 @@ struct SimplifyParams {
     double* out_states;      // [S][cap][4][ld] or nullptr
     double* out_dt;          // [S][cap-1][ld] or nullptr
 };
-
-__device__ __forceinline__ double lane_value(double x, int l) {  // x of lane l (uniform), in every lane
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-__device__ __forceinline__ int first_lane(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ double first_lane(double x) {
-    return __hiloint2double(first_lane(__double2hiint(x)), first_lane(__double2loint(x)));
-}
 
 // One (sample, track) item with ns + 1 rows.  X, Y, T and K hold ns + 1 entries each, in LDS or in the wave's slice of `work`.
 template <bool kShape>
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(64) void track_simplify(const SimplifyParams p) {
 #endif
     for (size_t item = first; item < nitems; item += gridDim.x) {
         const size_t s = item / B, t = item - s * B;
-        const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+        const int ns = track_steps(p, t);
         if constexpr (kWork) {
             if (ns + 1 > R) {  // uniform over the wave
                 const size_t rows = (size_t)p.Nmax + 1;
@@ -326,36 +317,32 @@ extern "C" size_t ste_track_simplify_workspace(int32_t Nmax, int32_t nstates, in
 
 extern "C" int ste_track_simplify_f64(const ste_ukf_batch_f64* b, const ste_simplify_f64* sf, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: batch pointer is NULL");
-    if (!sf) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: the simplification arguments (sf) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: B must be > 0 and Nmax >= 0");
-    if (b->Nmax > kMaxNmax)
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: Nmax is limited to 2^31 - 257 (rows are counted in int32)");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!sf->states) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->states is required");
-    if (sf->nstates < 1) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->nstates must be >= 1");
-    if (sf->nstates > 65535) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->nstates is limited to 65535 per call");
-    if ((sf->flags & ~STE_SIMPLIFY_SHAPE) != 0)
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->flags must be 0 or STE_SIMPLIFY_SHAPE");
-    if (sf->reserved != 0) return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->reserved must be 0");
+    const Refusal refuse{"ste_track_simplify_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!sf) return refuse("the simplification arguments (sf) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (b->Nmax > kMaxNmax) return refuse("Nmax is limited to 2^31 - 257 (rows are counted in int32)");
+    if (int rc = refuse.stride(b)) return rc;
+    if (!sf->states) return refuse("sf->states is required");
+    if (int rc = refuse.nstates("sf->nstates", sf->nstates)) return rc;
+    if ((sf->flags & ~STE_SIMPLIFY_SHAPE) != 0) return refuse("sf->flags must be 0 or STE_SIMPLIFY_SHAPE");
+    if (sf->reserved != 0) return refuse("sf->reserved must be 0");
     if (!sf->tolerance && !(sf->tolerance_all >= 0.0 && sf->tolerance_all * 0.0 == 0.0))
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->tolerance_all must be finite and >= 0 when sf->tolerance is NULL");
+        return refuse("sf->tolerance_all must be finite and >= 0 when sf->tolerance is NULL");
     if (!sf->lon_scale && !(sf->lon_scale_all >= 0.0 && sf->lon_scale_all * 0.0 == 0.0))
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->lon_scale_all must be finite and >= 0 when sf->lon_scale is NULL");
+        return refuse("sf->lon_scale_all must be finite and >= 0 when sf->lon_scale is NULL");
     const bool compact = sf->rows || sf->out_states || sf->out_dt;
-    if (compact && sf->cap == 0)
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: rows, out_states and out_dt need sf->cap, the rows they hold");
+    if (compact && sf->cap == 0) return refuse("rows, out_states and out_dt need sf->cap, the rows they hold");
     if (compact && (sf->cap < 1 || (int64_t)sf->cap > (int64_t)b->Nmax + 1))
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->cap must be between 1 and Nmax + 1");
+        return refuse("sf->cap must be between 1 and Nmax + 1");
     const bool shape = (sf->flags & STE_SIMPLIFY_SHAPE) != 0;
     if (!b->dt && (!shape || sf->out_dt))
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: the batch's dt is required (the clock of the rule, and the terms of out_dt)");
+        return refuse("the batch's dt is required (the clock of the rule, and the terms of out_dt)");
     if (!sf->keep && !sf->nkeep && !sf->worst_sq && !sf->status && !compact)
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: no output asked for (keep, nkeep, worst_sq, status, rows, out_states and out_dt are all NULL)");
+        return refuse("no output asked for (keep, nkeep, worst_sq, status, rows, out_states and out_dt are all NULL)");
     const size_t need = ste_track_simplify_workspace(b->Nmax, sf->nstates, b->B);
     if (need > 0 && (!sf->work || sf->work_bytes < 0 || (uint64_t)sf->work_bytes < (uint64_t)need))
-        return abi_fail(STE_EINVAL, "ste_track_simplify_f64: sf->work is required with work_bytes >= ste_track_simplify_workspace(Nmax, nstates, B) when Nmax + 1 exceeds ste_track_simplify_lds_rows()");
+        return refuse("sf->work is required with work_bytes >= ste_track_simplify_workspace(Nmax, nstates, B) when Nmax + 1 exceeds ste_track_simplify_lds_rows()");
     SimplifyParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
@@ -363,7 +350,7 @@ extern "C" int ste_track_simplify_f64(const ste_ukf_batch_f64* b, const ste_simp
     p.cap = compact ? sf->cap : 0;
     const int64_t nrows = (int64_t)b->Nmax + 1;
     p.lds_rows = (int)((nrows < kLdsRows ? nrows : (int64_t)kLdsRows) + 7) / 8 * 8;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = (!shape || sf->out_dt) ? b->dt : nullptr;
     p.states = sf->states;

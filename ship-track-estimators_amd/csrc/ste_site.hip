@@ -23,8 +23,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 #ifndef STE_SITE_TILE
 #define STE_SITE_TILE 4  // sites per wave: 4, 6 and 8 were timed ("Sites")
@@ -111,6 +110,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STE_SITE_WAV
 
     const double t0 = p.t0 ? p.t0[t] : 0.0;
     bool tbad = !is_finite(t0);
+    // track_steps(p, t), written out: through the function the kernel's address arithmetic comes out in another order
     const int ns = tbad ? 0 : min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     const double* dtp = p.dt + t;
@@ -252,34 +252,30 @@ extern "C" int ste_site_tile(void) { return ste::kSiteTile; }
 
 extern "C" int ste_site_metrics_f64(const ste_ukf_batch_f64* b, const ste_site_f64* si, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: batch pointer is NULL");
-    if (!si) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: the site arguments (si) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!si->states) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->states is required");
-    if (!si->sites) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->sites is required");
-    if (!si->radius_km) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->radius_km is required (one radius per site)");
-    if (si->nstates < 1) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->nstates must be >= 1");
-    if (si->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (si->nsites < 1 || si->nsites > STE_SITES_MAX)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->nsites must be between 1 and STE_SITES_MAX (65536)");
-    if (si->min_dist && si->model != STE_PREP_SPHERE && si->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->model must be STE_PREP_SPHERE or STE_PREP_WGS84 when min_dist is asked for");
-    if (si->flags != 0) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->flags must be 0");
-    if (si->reserved != 0) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: si->reserved must be 0");
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_site_metrics_f64: the batch's dt is required (the clock is made of its sums)");
+    const Refusal refuse{"ste_site_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!si) return refuse("the site arguments (si) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!si->states) return refuse("si->states is required");
+    if (!si->sites) return refuse("si->sites is required");
+    if (!si->radius_km) return refuse("si->radius_km is required (one radius per site)");
+    if (int rc = refuse.nstates("si->nstates", si->nstates, " (one grid row per track of a ship)")) return rc;
+    if (si->nsites < 1 || si->nsites > STE_SITES_MAX) return refuse("si->nsites must be between 1 and STE_SITES_MAX (65536)");
+    if (si->min_dist && refuse.model("si->model", si->model, " when min_dist is asked for")) return STE_EINVAL;
+    if (si->flags != 0) return refuse("si->flags must be 0");
+    if (si->reserved != 0) return refuse("si->reserved must be 0");
+    if (!b->dt) return refuse("the batch's dt is required (the clock is made of its sums)");
     if (!si->min_dist && !si->min_time && !si->time_within && !si->first_within && !si->longest && !si->nwithin &&
         !si->sound_time && !si->nbroken && !si->track_status && !si->site_status)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: no output asked for (min_dist, min_time, time_within, first_within, longest, nwithin, sound_time, nbroken, track_status and site_status are all NULL)");
+        return refuse("no output asked for (min_dist, min_time, time_within, first_within, longest, nwithin, sound_time, nbroken, track_status and site_status are all NULL)");
     SiteParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = si->nstates;
     p.nsites = si->nsites;
     p.ntiles = (unsigned)((si->nsites + kSiteTile - 1) / kSiteTile);
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = si->states;
@@ -298,7 +294,7 @@ extern "C" int ste_site_metrics_f64(const ste_ukf_batch_f64* b, const ste_site_f
     p.site_status = si->site_status;
     const uint64_t nblocks = (uint64_t)p.ntiles * (uint64_t)(((int64_t)b->B + 63) / 64);
     if (nblocks > 0x7fffffffull)
-        return abi_fail(STE_EINVAL, "ste_site_metrics_f64: ceil(B / 64) * ceil(nsites / tile) exceeds 2^31 - 1 blocks: split the sites or the tracks over calls");
+        return refuse("ceil(B / 64) * ceil(nsites / tile) exceeds 2^31 - 1 blocks: split the sites or the tracks over calls");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool within = si->time_within || si->first_within || si->longest || si->nwithin;
     const int model = si->min_dist ? si->model : kNoLeg;

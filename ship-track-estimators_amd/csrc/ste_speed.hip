@@ -26,8 +26,7 @@
 
 #include "../../include/ste.h"
 #include "ste_err.h"
-#include "ste_math.h"
-#include "ste_geodesy.h"  // last: it switches contraction off for the rest of the file
+#include "ste_track.h"  // last: it switches contraction off for the rest of the file
 
 namespace ste {
 namespace {
@@ -58,31 +57,6 @@ struct SpeedParams {
     double edges[STE_SPEED_MAX_BANDS + 1];
 };
 
-// A row as the leg wants it: the operations of leg_km_deg, with the radians and the cosine of row k+1 (sphere) carried into
-// leg k+1 as path_metrics carries them.  WGS84 works on degrees.
-struct SpeedPoint {
-    double lon, lat, c;
-};
-template <int kModel>
-__device__ __forceinline__ SpeedPoint speed_point(double lon_deg, double lat_deg) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        const double lat = lat_deg * kDeg2Rad;
-        return {lon_deg * kDeg2Rad, lat, cos(lat)};
-    } else {
-        return {lon_deg, lat_deg, 0.0};
-    }
-}
-template <int kModel>
-__device__ __forceinline__ double speed_leg_km(const SpeedPoint& a, const SpeedPoint& b) {
-    if constexpr (kModel == STE_PREP_SPHERE) {
-        return sphere_dist_km(a.lon, a.lat, a.c, b.lon, b.lat, b.c);
-    } else {
-        // a non-finite coordinate must come out as NaN whichever branch of the solver it reaches (x * 0 is 0 for finite x)
-        const double poison = (a.lon + a.lat + b.lon + b.lat) * 0.0;
-        return wgs84_leg(a.lon, a.lat, b.lon, b.lat).dist_km + poison;
-    }
-}
-
 template <int kModel, bool kBands, bool kRuns>
 __global__ __launch_bounds__(64) void speed_metrics(const SpeedParams p) {
     extern __shared__ double edge[];  // kBands: [64] edges, then [nbands][64] band sums, a column per lane
@@ -100,7 +74,7 @@ __global__ __launch_bounds__(64) void speed_metrics(const SpeedParams p) {
     const size_t ld = p.ld, rows = (size_t)p.Nmax + 1, s = blockIdx.y;
     const double nan = __builtin_nan(""), inf = __builtin_inf();
     const int nb = p.nbands;
-    const int ns = min(max(p.nsteps ? p.nsteps[t] : p.Nmax, 0), p.Nmax);
+    const int ns = track_steps(p, t);
     const double* st = p.states + (s * rows * 4) * ld + t;  // row k, component c: st[(k * 4 + c) * ld]
     const double* dtp = p.dt + t;
     double* sp = p.speed ? p.speed + (s * (size_t)p.Nmax) * ld + t : nullptr;
@@ -136,10 +110,10 @@ __global__ __launch_bounds__(64) void speed_metrics(const SpeedParams p) {
     };
 
     // row 0 here, row 1 and the dt of step 0 on their way; rows past ns are never read
-    SpeedPoint cur = {0.0, 0.0, 0.0};
+    TrackPoint<kModel> cur = {0.0, 0.0, 0.0};
     double nlon = 0.0, nlat = 0.0, ndt = 0.0;
     if (ns > 0) {
-        cur = speed_point<kModel>(st[0], st[ld]);
+        cur = track_point<kModel>(st[0], st[ld]);
         nlon = st[4 * ld];
         nlat = st[5 * ld];
         ndt = dtp[0];
@@ -153,9 +127,9 @@ __global__ __launch_bounds__(64) void speed_metrics(const SpeedParams p) {
             ndt = dtp[(r - 1) * ld];
         }
         if (!(dtk >= 0.0 && is_finite(dtk))) tbad = true;
-        const SpeedPoint nxt = speed_point<kModel>(lon, lat);
+        const TrackPoint<kModel> nxt = track_point<kModel>(lon, lat);
         // the leg of every step, skipped ones included: they are rare, and the wave stays together
-        const double L = speed_leg_km<kModel>(cur, nxt);
+        const double L = track_leg_km<kModel>(cur, nxt);
         const bool examined = dtk > 0.0;
         const double q = L / dtk;
         const bool sound = examined && is_finite(q);
@@ -236,45 +210,41 @@ void launch_speed(const SpeedParams& p, hipStream_t s) {
 
 extern "C" int ste_speed_metrics_f64(const ste_ukf_batch_f64* b, const ste_speed_f64* sp, void* stream) {
     using namespace ste;
-    if (!b) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: batch pointer is NULL");
-    if (!sp) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: the speed arguments (sp) are NULL");
-    if (b->B <= 0 || b->Nmax < 0) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: B must be > 0 and Nmax >= 0");
-    if (b->track_stride != 0 && b->track_stride < b->B)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: track_stride must be 0 or >= B (a window inside rows of track_stride tracks)");
-    if (!sp->states) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->states is required");
-    if (sp->nstates < 1) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->nstates must be >= 1");
-    if (sp->nstates > 65535)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->nstates is limited to 65535 per call (one grid row per track of a ship)");
-    if (sp->model != STE_PREP_SPHERE && sp->model != STE_PREP_WGS84)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->model must be STE_PREP_SPHERE or STE_PREP_WGS84");
-    if (sp->flags & ~STE_SPEED_ABOVE) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->flags must be 0 or STE_SPEED_ABOVE");
+    const Refusal refuse{"ste_speed_metrics_f64"};
+    if (!b) return refuse("batch pointer is NULL");
+    if (!sp) return refuse("the speed arguments (sp) are NULL");
+    if (int rc = refuse.shape(b)) return rc;
+    if (int rc = refuse.stride(b)) return rc;
+    if (!sp->states) return refuse("sp->states is required");
+    if (int rc = refuse.nstates("sp->nstates", sp->nstates, " (one grid row per track of a ship)")) return rc;
+    if (int rc = refuse.model("sp->model", sp->model)) return rc;
+    if (sp->flags & ~STE_SPEED_ABOVE) return refuse("sp->flags must be 0 or STE_SPEED_ABOVE");
     if (sp->nbands < 0 || sp->nbands > STE_SPEED_MAX_BANDS)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->nbands must be between 0 and STE_SPEED_MAX_BANDS (32)");
+        return refuse("sp->nbands must be between 0 and STE_SPEED_MAX_BANDS (32)");
     if (sp->nbands > 0 && !sp->band_edges)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->band_edges is required with nbands > 0 (nbands + 1 edges on the host)");
-    if (sp->nbands == 0 && sp->band_edges) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->band_edges must be NULL with nbands == 0");
-    if (sp->nbands == 0 && sp->band_time) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->band_time needs bands (nbands > 0)");
+        return refuse("sp->band_edges is required with nbands > 0 (nbands + 1 edges on the host)");
+    if (sp->nbands == 0 && sp->band_edges) return refuse("sp->band_edges must be NULL with nbands == 0");
+    if (sp->nbands == 0 && sp->band_time) return refuse("sp->band_time needs bands (nbands > 0)");
     for (int i = 0; i <= sp->nbands && sp->nbands > 0; ++i) {
         const double e = sp->band_edges[i];
         if (!(std::isfinite(e) && e >= 0.0 && (i == 0 || e > sp->band_edges[i - 1])))
-            return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->band_edges must be finite, >= 0 and strictly ascending");
+            return refuse("sp->band_edges must be finite, >= 0 and strictly ascending");
     }
-    if (!(std::isfinite(sp->min_run_h) && sp->min_run_h >= 0.0))
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: sp->min_run_h must be finite and >= 0");
+    if (!(std::isfinite(sp->min_run_h) && sp->min_run_h >= 0.0)) return refuse("sp->min_run_h must be finite and >= 0");
     const bool runs = sp->cond_time || sp->run_time || sp->first_run || sp->longest || sp->longest_start || sp->nruns;
     if (runs && !sp->threshold && !(std::isfinite(sp->threshold_all) && sp->threshold_all >= 0.0))
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: a run output (cond_time, run_time, first_run, longest, longest_start, nruns) needs sp->threshold, or a threshold_all that is finite and >= 0");
-    if (!b->dt) return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: the batch's dt is required (a speed is a leg over its dt)");
+        return refuse("a run output (cond_time, run_time, first_run, longest, longest_start, nruns) needs sp->threshold, or a threshold_all that is finite and >= 0");
+    if (!b->dt) return refuse("the batch's dt is required (a speed is a leg over its dt)");
     if (!runs && !sp->speed && !sp->dist && !sp->sound_time && !sp->vmax && !sp->vmax_time && !sp->band_time && !sp->nbroken &&
         !sp->track_status)
-        return abi_fail(STE_EINVAL, "ste_speed_metrics_f64: no output asked for (speed, dist, sound_time, vmax, vmax_time, band_time, cond_time, run_time, first_run, longest, longest_start, nruns, nbroken and track_status are all NULL)");
+        return refuse("no output asked for (speed, dist, sound_time, vmax, vmax_time, band_time, cond_time, run_time, first_run, longest, longest_start, nruns, nbroken and track_status are all NULL)");
     SpeedParams p;
     p.B = b->B;
     p.Nmax = b->Nmax;
     p.nstates = sp->nstates;
     p.nbands = sp->nbands;
     p.flags = sp->flags;
-    p.ld = (size_t)(b->track_stride ? b->track_stride : b->B);
+    p.ld = track_ld(b);
     p.nsteps = b->nsteps;
     p.dt = b->dt;
     p.states = sp->states;
