@@ -23,7 +23,7 @@ int launch_forward_q4(const KParams& kp, hipStream_t s);  // the quad launch of 
 // ste_smooth.hip
 bool lean_smoother(const KParams& kp);  // does the batch smooth with the two-kernel form?
 int launch_backward_work(const KParams& kp, const NoiseParams* np, hipStream_t s);  // launch_backward with rts_work
-int launch_recur_sched(bool shift, int nitems, const SmoothSchedParams& sp, hipStream_t s);
+int launch_recur_sched(bool shift, bool plain, int nitems, const SmoothSchedParams& sp, hipStream_t s);  // plain: every window is
 // ste_sample.hip
 int launch_sample_coef(const KParams& kp, const ste_ukf_noise_f64* nz, const ste_ukf_sample_f64& sm, hipStream_t s);
 int launch_sample_recur(const KParams& kp, const ste_ukf_sample_f64& sm, hipStream_t s);

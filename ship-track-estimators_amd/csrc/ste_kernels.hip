@@ -15,6 +15,8 @@
 //     + sched_upload                     working through a host-made schedule of (64-track tile, time slice) items -- the
 //                                        body is ukf_forward_l1's --, the one-wave gate a smoother's stream waits behind,
 //                                        and the upload of the schedule's table from page-locked memory
+//   ukf_forward_l1_plain,                ukf_forward_l1 / ukf_forward_sched <true, true, false> for plain batches (ste_ukf.h:
+//     ukf_forward_sched_plain            plain_batch): packed layout and no recorded noise compiled into the step loop
 //   urtss_backward_l1                    stand-alone smoother that recomputes everything (rts_work == NULL)
 //   ukf_forward_lik, ukf_forward_tn,     the lane-per-track forward pass with the likelihood, and it and the stand-alone
 //     urtss_backward_l1<true>            smoother with per-track Q / R (ste_ukf_noise_f64): instantiations of the same
@@ -479,12 +481,18 @@ __device__ __forceinline__ int ukf_update(const Mats& p, double (&x)[4], double 
 // also leaves the smoother's row of this step (see kWorkD).  x, P are replaced by the predicted mean (+ recorded noise)
 // and covariance.  `flagged` is sticky: set once a square root of this track was clamped or did not converge; from that
 // step on columns 2-3 of D are stored as well.
-template <bool kGains, bool kSched = false>
+// kPlain: inlined into a plain batch's step loop (forward_tile_l1), whose callers pass noise = noise_rts = nullptr.
+// `before_stores` is called once, after the moment arithmetic and in front of the first store: the plain step loop consumes
+// there what it loaded at the top of the step (every other caller passes nothing).
+struct NoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <bool kGains, bool kSched = false, bool kPlain = false, class Hook = NoHook>
 __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], double (&P)[10], double (&V)[4][4], bool warm,
                                             double dt, double sr, double cr, const double* noise,
                                             const double* noise_rts, size_t nrow, size_t B, size_t t, double* work,
                                             bool full_row, bool noise_mode, bool& flagged, double* first_bad,
-                                            const TrigReg& tk, const double (&Qv)[10]) {
+                                            const TrigReg& tk, const double (&Qv)[10], const Hook& before_stores = Hook()) {
 #pragma clang fp contract(off)  // explicit fma() only: the same bits in every kernel this is inlined into
     double T[10];
     const int st = sym_sqrt_p(P, p.fan_scale, T, V, warm);
@@ -531,6 +539,13 @@ __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], doubl
         propagate_fan_branching(xc, Tc, dt, sr, cr, s0c, sc);
         STE_UNROLL
         for (int c = 0; c < 4; ++c) g.c[c] = sc[0][c];
+        if constexpr (kPlain) {
+            // Waited for in this cold branch: without recorded noise nothing reads the centre's speed and heading before
+            // the work-row and history stores do, and a reload left pending where the branch rejoins puts a wait behind the
+            // first of those stores on every step -- for the step's earlier stores too ("Store drain").
+            g.c[2] = in_vgpr(g.c[2]);
+            g.c[3] = in_vgpr(g.c[3]);
+        }
         moments_clear(f);
         moments_add<0, kGains>(f, T, g.c[0], g.c[1], sc[1][0], sc[1][1], sc[5][0], sc[5][1]);
         moments_add<1, kGains>(f, T, g.c[0], g.c[1], sc[2][0], sc[2][1], sc[6][0], sc[6][1]);
@@ -560,6 +575,7 @@ __device__ __forceinline__ int lane_predict(const Mats& p, double (&x)[4], doubl
     Pn[tix(2, 2)] = two_wi * f.S[tix(2, 2)];
     Pn[tix(2, 3)] = two_wi * f.S[tix(2, 3)];
     Pn[tix(3, 3)] = two_wi * f.S[tix(3, 3)];
+    before_stores();
     if (kGains && work) {
         // The smoother's cross-covariance D = wi sum_i T_i (chi'_{i+} - chi'_{i-})^T (the centre's deviation from x_k is
         // zero and x_b cancels in the difference): rows 2-3 of its columns 0-1 are the cross moments S[c][2], S[c][3] just
@@ -682,6 +698,13 @@ __device__ __forceinline__ void store_hist(const KParams& p, size_t row, size_t 
     for (int c = 0; c < 4; ++c) st_stream(&p.fwd_mean[(row * 4 + c) * B + t], x[c]);
     store_cov_p(p.fwd_cov, (p.flags & STE_FLAG_PACKED_COV) != 0, row, B, t, P);
 }
+// ... of a plain batch (ste_ukf.h: plain_batch): the packed layout compiled in
+__device__ __forceinline__ void store_hist_packed(const KParams& p, size_t row, size_t B, size_t t, const double (&x)[4],
+                                                  const double (&P)[10]) {
+    STE_UNROLL
+    for (int c = 0; c < 4; ++c) st_stream(&p.fwd_mean[(row * 4 + c) * B + t], x[c]);
+    store_cov_p<true>(p.fwd_cov, row, B, t, P);
+}
 
 // One wave per SIMD, on purpose: the step loop issues a vector instruction in ~80 % of its cycles, so a second forward
 // wave on the same SIMD gains next to nothing (measured: two per SIMD run 1.55x slower each), while waves of several
@@ -703,10 +726,22 @@ struct LikParams {
     double* nis;     // [Nmax+1][ld] or nullptr
 };
 
-template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff, bool kTrackNoise = false>
+// a recorded-noise array of the batch, or -- kPlain -- the literal nullptr
+template <bool kPlain>
+__device__ __forceinline__ const double* noise_ptr(const double* q) {
+    if constexpr (kPlain)
+        return nullptr;
+    else
+        return q;
+}
+// kPlain: a plain batch (ste_ukf.h: plain_batch) -- packed histories, no recorded noise: `noise_mode` is false, the noise
+// pointers handed to lane_predict / lane_update are literal nullptr and store_hist has the layout compiled in, so the step
+// loop neither tests nor keeps live what cannot change during a launch.  Same arithmetic, same bits.
+template <bool kGains, bool kFastUpd, bool kRobust, bool kSched, int kLik = kLikOff, bool kTrackNoise = false, bool kPlain = false>
 __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t, const LikParams* lk = nullptr,
                                                 const NoiseParams* nz = nullptr) {
     static_assert(kLik != kLikOnly || (!kGains && !kSched), "the likelihood-only pass writes no histories and no work rows");
+    static_assert(!kPlain || (kLik == kLikOff && !kTrackNoise), "plain batches: the default entry points only");
     const size_t B = (size_t)p.ld;  // row pitch of every per-track array (= the batch's own width unless it is a window)
     if (t >= (size_t)p.B) return;
     // A later time slice of a forward pass (slice_params): x0 / P0 name history row k0 -- the state the previous launch
@@ -719,7 +754,7 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
     double x[4], P[10];
     STE_UNROLL
     for (int c = 0; c < 4; ++c) x[c] = p.x0[c * B + t];
-    if (cont && (p.flags & STE_FLAG_PACKED_COV)) {
+    if (cont && (kPlain || (p.flags & STE_FLAG_PACKED_COV))) {
         load_cov_p(p.P0, true, 0, B, t, P);
     } else {
         // the prior enters as (P0 + P0^T) / 2: the host refuses a P0 that is not symmetric (batch._as44)
@@ -739,13 +774,15 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
             for (int c = r; c < 4; ++c) P[tix(r, c)] = 0.5 * (Pf[r][c] + Pf[c][r]);
         }
     }
-    if (kLik != kLikOnly) store_hist(p, 0, B, t, x, P);  // slot 0 = prior (kalman_filter.py:76-77); a later slice rewrites row k0 with its own bits
+    if constexpr (kPlain)
+        store_hist_packed(p, 0, B, t, x, P);
+    else if (kLik != kLikOnly) store_hist(p, 0, B, t, x, P);  // slot 0 = prior (kalman_filter.py:76-77); a later slice rewrites row k0 with its own bits
 
     // (a later slice may run in the same launch, on the same wave, as the one that wrote these two words -- the scheduled
     //  kernel -- without a cache invalidate in between: read them past the CU's L1)
     int st = cont ? (__hip_atomic_load(&p.status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~STE_STATUS_NAN) : 0;  // the NaN bit is taken from the final state, as in a whole pass
     const bool initial_update = !(p.flags & STE_FLAG_NO_INITIAL_UPDATE);
-    const bool noise_mode = p.noise_pred || p.noise_upd || p.noise_rts;
+    const bool noise_mode = kPlain ? false : (p.noise_pred || p.noise_upd || p.noise_rts);
     bool flagged = false;  // sticky: a square root of this track was clamped or did not converge
     double* first_bad = (kGains && p.rts_work) ? p.first_bad + t : nullptr;
     if (first_bad) {
@@ -780,7 +817,7 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
         for (int c = 0; c < 4; ++c) xc[c] = x[c];
         STE_UNROLL
         for (int e = 0; e < 10; ++e) Pc[e] = P[e];
-        st |= lane_predict<true, kSched>(p.m, xc, Pc, V, false, p.dt[t], p.sog_rate[t], p.cog_rate[t], nullptr, p.noise_rts, 0, B, t,
+        st |= lane_predict<true, kSched, kPlain>(p.m, xc, Pc, V, false, p.dt[t], p.sog_rate[t], p.cog_rate[t], nullptr, noise_ptr<kPlain>(p.noise_rts), 0, B, t,
                                          p.rts_work, true, noise_mode, flagged, first_bad, tk, Qv);
     }
     double lik_sum = 0.0;  // kLik: sum of l_u, of the ranks, and the number of updates
@@ -796,7 +833,7 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
             lik_nupd += 1;
             if (lk->nis) st_stream(&lk->nis[t], u.nis);
         } else {
-            st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, z0, p.noise_upd, 0, B, t, nullptr, Rt);  // kalman_filter.py:81
+            st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, z0, noise_ptr<kPlain>(p.noise_upd), 0, B, t, nullptr, Rt);  // kalman_filter.py:81
         }
     } else if (kLik != kLikOff && lk->nis) {
         st_stream(&lk->nis[t], __builtin_nan(""));
@@ -841,8 +878,25 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
             // row 0's smoother rows were taken from the prior above; every later row k is the state this predict starts from
             double* work = (kGains && !(k == 0 && initial_update)) ? p.rts_work : nullptr;
             const bool warm = (k & (kColdEvery - 1)) != 0;
-            st |= lane_predict<kGains, kSched>(p.m, x, P, V, warm, dt, sr, cr, p.noise_pred, p.noise_rts, (size_t)k, B, t, work,
-                                               upd || noise_mode, noise_mode, flagged, first_bad, tk, Qv);
+            if constexpr (kPlain) {
+                // The observation and the inputs of step k + 1, loaded at the top of this step, are consumed in front of the
+                // step's first store (some 2 000 instructions after the loads): a wait for them further down -- the update,
+                // the loop edge -- would cover the work-row and history stores issued in between (DESIGN.md section 5,
+                // "Store drain").  The general loop has such a wait in the same place, where recorded noise would be added.
+                auto consume_loads = [&]() {
+                    STE_UNROLL
+                    for (int c = 0; c < 4; ++c) zk[c] = in_vgpr(zk[c]);
+                    dt_n = in_vgpr(dt_n);
+                    sr_n = in_vgpr(sr_n);
+                    cr_n = in_vgpr(cr_n);
+                    ui_n = in_vgpr(ui_n);
+                };
+                st |= lane_predict<kGains, kSched, true>(p.m, x, P, V, warm, dt, sr, cr, nullptr, nullptr, (size_t)k, B, t, work, upd,
+                                                         false, flagged, first_bad, tk, Qv, consume_loads);
+            } else {
+                st |= lane_predict<kGains, kSched>(p.m, x, P, V, warm, dt, sr, cr, p.noise_pred, p.noise_rts, (size_t)k, B, t, work,
+                                                   upd || noise_mode, noise_mode, flagged, first_bad, tk, Qv);
+            }
             if constexpr (kLik != kLikOff) {
                 UpdLik u;
                 u.nis = __builtin_nan("");
@@ -854,10 +908,12 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
                 }
                 if (lk->nis) st_stream(&lk->nis[((size_t)k + 1) * B + t], u.nis);
             } else {
-                if (upd) st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, zk, p.noise_upd, (size_t)k + 1, B, t, nullptr, Rt);
+                if (upd) st |= lane_update<kFastUpd, kRobust, false, kTrackNoise>(p.m, x, P, zk, noise_ptr<kPlain>(p.noise_upd), (size_t)k + 1, B, t, nullptr, Rt);
             }
             if (!ui_ok) st |= STE_STATUS_BAD_INDEX;
-            if (kLik != kLikOnly) store_hist(p, (size_t)k + 1, B, t, x, P);
+            if constexpr (kPlain)
+                store_hist_packed(p, (size_t)k + 1, B, t, x, P);
+            else if (kLik != kLikOnly) store_hist(p, (size_t)k + 1, B, t, x, P);
         }
     }
     double chk = 0.0;
@@ -877,6 +933,12 @@ __device__ __forceinline__ void forward_tile_l1(const KParams& p, const size_t t
 template <bool kGains, bool kFastUpd, bool kRobust = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_l1(const KParams p) {
     forward_tile_l1<kGains, kFastUpd, kRobust, false>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
+}
+
+// ukf_forward_l1<true, true, false> for a plain batch (forward_tile_l1: kPlain) -- the pass the benchmark, run_fleet and the
+// CLI launch.  A kernel of its own name: the general kernels keep theirs, and their code.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_l1_plain(const KParams p) {
+    forward_tile_l1<true, true, false, false, kLikOff, false, true>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
 }
 
 // ukf_forward_l1 with the innovation log-likelihood (ste_ukf_forward_loglik_f64).  KParams stays the first argument (late_k0
@@ -954,6 +1016,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         const KParams& p = *(const KParams*)(ConstKParams*)(uintptr_t)(sp.kps + kp);
         if (threadIdx.x == 0) *(volatile int*)&g_sched_word[0] = p.k0;
         forward_tile_l1<kGains, kFastUpd, kRobust, true>(p, (size_t)tile * 64 + threadIdx.x);
+        if (meta & 0x40000000) {
+            // publish: this wave's stores have been acknowledged, then made visible at agent scope, before the count moves
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (threadIdx.x == 0) {
+                __hip_atomic_store(sp.progress + prog, publish, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (meta & 0x100)
+                    __hip_atomic_fetch_add(sp.window_done + ((meta >> 9) & 0x1fffff), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+// ukf_forward_sched<true, true, false> when every parameter block of the table is a plain batch's (ukf_forward_l1_plain).  The
+// wave loop is ukf_forward_sched's, line for line, repeated here and not shared through a device function: the general kernels
+// keep their code to the byte that way (as a function of two callers the loop compiled to other scalar registers).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ukf_forward_sched_plain(const SchedParams sp) {
+    typedef const KParams __attribute__((address_space(4))) ConstKParams;  // the table is constant for the launch: scalar loads,
+                                                                           // re-materialised where they are used like kernel arguments
+    if (sp.started && threadIdx.x == 0) __hip_atomic_fetch_add(sp.started, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int r = 0; r < sp.nrounds; ++r) {
+        const SchedItem* ip = sp.items + ((size_t)r * sp.nwaves + blockIdx.x);
+        const int kp = __builtin_amdgcn_readfirstlane(ip->kp);
+        if (kp < 0) continue;
+        const int tile_word = __builtin_amdgcn_readfirstlane(ip->tile), prog = __builtin_amdgcn_readfirstlane(ip->prog);
+        const int tile = tile_word & 0xffffff, publish = (tile_word >> 24) & 0xff;  // publish: slices done once this item has run
+        const int meta = __builtin_amdgcn_readfirstlane(ip->meta);
+        const int slice = meta & 0xff;
+        // (the error word is looked at only where a wave waits: a launch that cannot progress ends through its bounded waits)
+        if (meta < 0 && (__hip_atomic_load(sp.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ||
+                         !sched_wait(sp.progress + prog, slice, sp.timeout_ticks))) {
+            if (threadIdx.x == 0) __hip_atomic_store(sp.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        const KParams& p = *(const KParams*)(ConstKParams*)(uintptr_t)(sp.kps + kp);
+        if (threadIdx.x == 0) *(volatile int*)&g_sched_word[0] = p.k0;
+        forward_tile_l1<true, true, false, true, kLikOff, false, true>(p, (size_t)tile * 64 + threadIdx.x);
         if (meta & 0x40000000) {
             // publish: this wave's stores have been acknowledged, then made visible at agent scope, before the count moves
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1450,6 +1549,8 @@ int launch_forward(const char* fn, const ste::KParams& kp, const ste::LikParams*
                 hipLaunchKernelGGL((ste::ukf_forward_tn<kG, kF, kR, kLik>), grid, block, 0, s, kp, l0, *np);
             else if constexpr (kLik != ste::kLikOff)
                 hipLaunchKernelGGL((ste::ukf_forward_lik<kG, kF, kR, kLik>), grid, block, 0, s, kp, l0);
+            else if (kG && kF && !kR && ste::plain_batch(kp))
+                hipLaunchKernelGGL(ste::ukf_forward_l1_plain, grid, block, 0, s, kp);
             else
                 hipLaunchKernelGGL((ste::ukf_forward_l1<kG, kF, kR>), grid, block, 0, s, kp);
         };
@@ -1673,6 +1774,7 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
     ste::KParams* kps = (ste::KParams*)(hw + lay.kps);
     // parameter block of window w for the run of slices [q0, q1]: built when a (merged) item first needs it
     const ste::KParams* first = nullptr;  // the first block built: every other takes the same kernel
+    bool all_plain = true;                // ... the plain one only if every block of the table is a plain batch's
     std::vector<char> have(nkp, 0);
     auto run_index = [&](int w, int q0, int q1) { return kp0[w] + q0 * nslices[w] - q0 * (q0 - 1) / 2 + (q1 - q0); };
     auto run_params = [&](int w, int q0, int q1, int* index) -> int {
@@ -1691,6 +1793,7 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
         if (first && forward_variant(*kp) != forward_variant(*first))
             return fail(STE_EINVAL, "scheduled forward pass: the windows must agree on H / R structure, robust flag and rts_work (one kernel runs them all)");
         if (!first) first = kp;
+        all_plain = all_plain && ste::plain_batch(*kp);
         have[(size_t)k] = 1;
         return STE_OK;
     };
@@ -1781,8 +1884,11 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
     const dim3 grid((unsigned)sc->nwaves), block(64);
     if (!first) return fail(STE_EINVAL, "scheduled forward pass: no kernel variant");
     with_forward_variant(*first, [&](auto gains, auto fast, auto robust) {
-        hipLaunchKernelGGL((ste::ukf_forward_sched<decltype(gains)::value, decltype(fast)::value, decltype(robust)::value>), grid, block,
-                           0, s, sp);
+        constexpr bool kG = decltype(gains)::value, kF = decltype(fast)::value, kR = decltype(robust)::value;
+        if (kG && kF && !kR && all_plain)
+            hipLaunchKernelGGL(ste::ukf_forward_sched_plain, grid, block, 0, s, sp);
+        else
+            hipLaunchKernelGGL((ste::ukf_forward_sched<kG, kF, kR>), grid, block, 0, s, sp);
     });
     return check_hip(hipGetLastError(), "ukf_forward_sched launch");
 }
@@ -1823,6 +1929,7 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
     std::vector<int> nslices((size_t)sc->nwindows), tile0((size_t)sc->nwindows + 1);
     size_t ntiles = 0;
     int shift = -1;
+    bool all_plain = true;  // the plain kernel only if every window is a plain batch (ste_ukf.h: plain_batch)
     for (int w = 0; w < sc->nwindows; ++w) {
         const ste_ukf_batch_f64& b = sc->windows[w];
         if (b.B <= 0 || b.Nmax <= 0) return fail(STE_EINVAL, "scheduled smoother: a window has B <= 0 or Nmax <= 0");
@@ -1837,6 +1944,7 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
         const int sh = (kp.sog_rate_rts || kp.cog_rate_rts) ? 1 : 0;
         if (shift >= 0 && sh != shift) return fail(STE_EINVAL, "scheduled smoother: the windows must agree on smoother rates (one kernel runs them all)");
         shift = sh;
+        all_plain = all_plain && ste::plain_batch(kp);
         nslices[w] = std::max(1, (b.Nmax + step - 1) / step);
         tile0[w] = (int)ntiles;
         ntiles += ((size_t)b.B + 63) / 64;
@@ -1867,7 +1975,7 @@ int ste_urtss_backward_sched_f64(const ste_bwd_sched_f64* sc, void* stream) {
     sp.progress = sc->progress;
     sp.error = sc->error;
     sp.timeout_ticks = (unsigned long long)((sc->timeout_s > 0 ? sc->timeout_s : 2.0) * 1e8);
-    return ste::launch_recur_sched(shift != 0, sc->nitems, sp, s);
+    return ste::launch_recur_sched(shift != 0, all_plain, sc->nitems, sp, s);
 }
 
 int ste_urtss_backward_f64(const ste_ukf_batch_f64* b, void* stream) {

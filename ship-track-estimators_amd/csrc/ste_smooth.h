@@ -24,7 +24,8 @@ struct RecurRow {
 // (unscented.py:287-292: the smoother indexes the repeated rate arrays by step) sees the same propagated fan moved by
 // (0, 0, d_sog * dt, d_cog * dt): x_b moves by that much, the fan's spread and D not at all, and P_b -- taken about the
 // filtered mean x_k (:324-325) -- becomes C + b' b'^T with the new b' = x_b' - x_k.
-template <bool kShift>
+// kPlain: a plain batch (ste_ukf.h: plain_batch), the packed layout compiled in.
+template <bool kShift, bool kPlain = false>
 __device__ __forceinline__ void load_recur_row(const KParams& p, size_t k, size_t B, size_t t, bool d_rows23, RecurRow& g) {
     g.shift[0] = g.shift[1] = 0.0;
     if (kShift) {
@@ -40,7 +41,10 @@ __device__ __forceinline__ void load_recur_row(const KParams& p, size_t k, size_
         for (int e = 4; e < 8; ++e) g.D2[e] = w[(kWorkD + e) * B];
     }
     load_vec(p.fwd_mean, k, B, t, g.xk);
-    load_cov_p(p.fwd_cov, (p.flags & STE_FLAG_PACKED_COV) != 0, k, B, t, g.Pk);
+    if constexpr (kPlain)
+        load_cov_p<true>(p.fwd_cov, k, B, t, g.Pk);
+    else
+        load_cov_p(p.fwd_cov, (p.flags & STE_FLAG_PACKED_COV) != 0, k, B, t, g.Pk);
 }
 
 // Every value load_recur_row loads, consumed (in_vgpr): in front of a step loop whose rows are loaded a step ahead, so that
@@ -81,7 +85,8 @@ __device__ __forceinline__ void load_stored_xb_pb(const KParams& p, size_t k, si
 // kRowAhead (the step loop of smooth_tile_l1): on a full row `xb` / `Pb` come in holding the stored x_b, P_b, loaded by the
 // caller a row ahead (load_stored_xb_pb) -- in front of the previous row's stores, so that the step waits for neither the
 // loads' latency nor those stores' acknowledgements ("Store drain"); on other rows they are formed here.
-template <bool kShift, bool kTrackNoise = false, bool kRowAhead = false>
+// kPlain: a plain batch (no recorded noise: the caller passes always_full = false, and noise_rts is not looked at).
+template <bool kShift, bool kTrackNoise = false, bool kRowAhead = false, bool kPlain = false>
 __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_t B, size_t t, const RecurRow& cur,
                                                   const double (&xn)[4], const double (&Pn)[10], bool full, bool always_full,
                                                   bool all_eig, double kappa, double first_bad, double (&xb)[4],
@@ -113,9 +118,11 @@ __device__ __forceinline__ int smoother_step_gain(const KParams& p, int k, size_
             double bv[4];
             STE_UNROLL
             for (int c = 0; c < 4; ++c) bv[c] = xb[c] - cur.xk[c];
-            if (p.noise_rts) {
-                STE_UNROLL
-                for (int c = 0; c < 4; ++c) bv[c] -= p.noise_rts[((size_t)k * 4 + c) * B + t];
+            if constexpr (!kPlain) {
+                if (p.noise_rts) {
+                    STE_UNROLL
+                    for (int c = 0; c < 4; ++c) bv[c] -= p.noise_rts[((size_t)k * 4 + c) * B + t];
+                }
             }
             const double s2 = cur.shift[0], s3 = cur.shift[1];
             Pb[tix(0, 2)] = fma(bv[0], s2, Pb[tix(0, 2)]);

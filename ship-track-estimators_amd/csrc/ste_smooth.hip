@@ -7,6 +7,8 @@
 // Kernels:
 //   urtss_recur_l1                       smoother from those rows, one lane per track: gain K = D pinv(P_b), recurrence
 //                                        (batches that fill the chip)
+//   urtss_recur_l1_plain / _sched_plain  urtss_recur_l1 / urtss_recur_sched for plain batches (ste_ukf.h: plain_batch): packed
+//                                        layout, no recorded noise and no position copy compiled in
 //   urtss_recur_tn                       the same with per-track Q (ste_ukf_noise_f64), loaded from NoiseParams
 //   urtss_recur_sched                    the same body for every window of a scheduled forward launch as one launch: a wave
 //                                        per tile, waiting for its own tile's forward pass
@@ -42,14 +44,18 @@ namespace ste {
 // take the issue slots it leaves (batch.SmootherPipeline).  Only reads the work rows: repeatable.
 // ---------------------------------------------------------------------------------------------------------------
 // kShift: the smoother has rates of its own (sog_rate_rts / cog_rate_rts); compiled out for batches that share them.
-template <bool kShift, bool kTrackNoise = false>
+// kPlain: a plain batch (ste_ukf.h: plain_batch) -- always_full is false, the covariance rows are loaded and stored with the
+// packed layout compiled in, and there is no position copy: nothing that is fixed for the launch is tested or kept live
+// in the step loop.  Same arithmetic, same bits.
+template <bool kShift, bool kTrackNoise = false, bool kPlain = false>
 __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t, const NoiseParams* nz = nullptr) {
     const size_t B = (size_t)p.ld;
     if (t >= (size_t)p.B) return;
     double q4[4] = {0.0, 0.0, 0.0, 0.0};
     if constexpr (kTrackNoise) track_q4(p, *nz, B, t, q4);
     const int ns = p.nsteps ? p.nsteps[t] : p.Nmax;
-    const bool always_full = p.noise_pred || p.noise_upd || p.noise_rts;
+    static_assert(!kPlain || !kTrackNoise, "plain batches: the shared-noise entry points only");
+    const bool always_full = kPlain ? false : (p.noise_pred || p.noise_upd || p.noise_rts);
     const bool all_eig = (p.tuning & STE_TUNING_EIG_GAINS) != 0;
     const double kappa = (p.m.wi + p.m.wi) * p.m.fan_scale;  // D[:, 2:4] = kappa P_k[:, 2:4] for an exact square root
     // first step at and after which this track's columns 2-3 of D are stored (kNeverBad: never)
@@ -59,12 +65,19 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
 
     // row ns: smoothed = filtered; it is also "filtered row k + 1" of the first step
     double xs[4], Ps[10], xn[4], Pn[10];
-    const bool packed = (p.flags & STE_FLAG_PACKED_COV) != 0;
+    const bool packed = kPlain ? true : (p.flags & STE_FLAG_PACKED_COV) != 0;
     load_vec(p.fwd_mean, (size_t)ns, B, t, xs);
-    load_cov_p(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
+    if constexpr (kPlain)
+        load_cov_p<true>(p.fwd_cov, (size_t)ns, B, t, Ps);
+    else
+        load_cov_p(p.fwd_cov, packed, (size_t)ns, B, t, Ps);
     store_vec(p.sm_mean, (size_t)ns, B, t, xs);
-    store_cov_p(p.sm_cov, packed, (size_t)ns, B, t, Ps);
-    store_pos(p, (size_t)ns, B, t, xs);
+    if constexpr (kPlain) {
+        store_cov_p<true>(p.sm_cov, (size_t)ns, B, t, Ps);
+    } else {
+        store_cov_p(p.sm_cov, packed, (size_t)ns, B, t, Ps);
+        store_pos(p, (size_t)ns, B, t, xs);
+    }
     STE_UNROLL
     for (int c = 0; c < 4; ++c) xn[c] = xs[c];
     STE_UNROLL
@@ -77,7 +90,7 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
     int ui_n = -1, ui_nn = -1;
     double xb[4] = {0.0, 0.0, 0.0, 0.0}, Pb[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (ns > 0) {
-        load_recur_row<kShift>(p, (size_t)(ns - 1), B, t, always_full, nxt);
+        load_recur_row<kShift, kPlain>(p, (size_t)(ns - 1), B, t, always_full, nxt);
         ui_n = p.upd_idx[(size_t)(ns - 1) * B + t];
         ui_nn = p.upd_idx[(size_t)clampk(ns - 2) * B + t];
         if (work_row_full(p, ns - 1, ui_n, always_full)) load_stored_xb_pb(p, (size_t)(ns - 1), B, t, xb, Pb);
@@ -98,7 +111,7 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
             const RecurRow cur = nxt;
             const bool full = work_row_full(p, k, ui_n, always_full);
             double K[4][4];
-            st |= smoother_step_gain<kShift, kTrackNoise, true>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
+            st |= smoother_step_gain<kShift, kTrackNoise, true, kPlain>(p, k, B, t, cur, xn, Pn, full, always_full, all_eig, kappa, first_bad, xb, Pb, K, q4);
             // y = x^s_{k+1} - x_b and dP = P^s_{k+1} - P_b first: x_b, P_b of this step are done with, and their registers take
             // the stored ones of the next step
             double y[4];
@@ -111,7 +124,7 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
             // the row of the next step, and its stored x_b, P_b if it is full: in front of this row's stores, in flight during
             // the recurrence arithmetic below and across the loop edge (row 0 again on the last step: in bounds, not used)
             const int kn = clampk(k - 1);
-            load_recur_row<kShift>(p, (size_t)kn, B, t, always_full, nxt);
+            load_recur_row<kShift, kPlain>(p, (size_t)kn, B, t, always_full, nxt);
             ui_n = ui_nn;
             if (work_row_full(p, kn, ui_n, always_full)) load_stored_xb_pb(p, (size_t)kn, B, t, xb, Pb);
             ui_nn = p.upd_idx[(size_t)clampk(k - 2) * B + t];
@@ -146,8 +159,12 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
                 }
             }
             store_vec(p.sm_mean, (size_t)k, B, t, xs);
-            store_cov_p(p.sm_cov, packed, (size_t)k, B, t, Ps);
-            store_pos(p, (size_t)k, B, t, xs);
+            if constexpr (kPlain) {
+                store_cov_p<true>(p.sm_cov, (size_t)k, B, t, Ps);
+            } else {
+                store_cov_p(p.sm_cov, packed, (size_t)k, B, t, Ps);
+                store_pos(p, (size_t)k, B, t, xs);
+            }
             // row k becomes "row k + 1" of the next step
             STE_UNROLL
             for (int c = 0; c < 4; ++c) xn[c] = cur.xk[c];
@@ -167,6 +184,11 @@ __device__ __forceinline__ void smooth_tile_l1(const KParams& p, const size_t t,
 template <bool kShift>
 __global__ __launch_bounds__(64) void urtss_recur_l1(const KParams p) {
     smooth_tile_l1<kShift>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
+}
+// urtss_recur_l1 for a plain batch (smooth_tile_l1: kPlain).  A kernel of its own name: the general kernels keep theirs.
+template <bool kShift>
+__global__ __launch_bounds__(64) void urtss_recur_l1_plain(const KParams p) {
+    smooth_tile_l1<kShift, false, true>(p, (size_t)blockIdx.x * 64 + threadIdx.x);
 }
 template <bool kShift>
 __global__ __launch_bounds__(64) void urtss_recur_tn(const KParams p, const NoiseParams nz) {
@@ -191,6 +213,22 @@ __global__ __launch_bounds__(64) void urtss_recur_sched(const SmoothSchedParams 
     }
     const KParams& p = *(const KParams*)(ConstKParams*)(uintptr_t)(sp.kps + kp);
     smooth_tile_l1<kShift>(p, (size_t)tile * 64 + threadIdx.x);
+}
+// urtss_recur_sched when every window of the table is a plain batch (urtss_recur_l1_plain).  The same lines again, not a
+// shared device function: the general kernels keep their code to the byte that way.
+template <bool kShift>
+__global__ __launch_bounds__(64) void urtss_recur_sched_plain(const SmoothSchedParams sp) {
+    typedef const KParams __attribute__((address_space(4))) ConstKParams;
+    const SmoothItem* ip = sp.items + blockIdx.x;
+    const int kp = __builtin_amdgcn_readfirstlane(ip->kp), tile = __builtin_amdgcn_readfirstlane(ip->tile);
+    const int prog = __builtin_amdgcn_readfirstlane(ip->prog), need = __builtin_amdgcn_readfirstlane(ip->need);
+    if (__hip_atomic_load(sp.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ||
+        !sched_wait(sp.progress + prog, need, sp.timeout_ticks)) {
+        if (threadIdx.x == 0) __hip_atomic_store(sp.error, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const KParams& p = *(const KParams*)(ConstKParams*)(uintptr_t)(sp.kps + kp);
+    smooth_tile_l1<kShift, false, true>(p, (size_t)tile * 64 + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -518,6 +556,8 @@ int launch_backward_work(const KParams& kp, const NoiseParams* np, hipStream_t s
     with_shift_tn([&](auto sh, auto t) {
         if constexpr (decltype(t)::value)
             hipLaunchKernelGGL(urtss_recur_tn<decltype(sh)::value>, grid, block, 0, s, kp, nz);
+        else if (!np && plain_batch(kp))
+            hipLaunchKernelGGL(urtss_recur_l1_plain<decltype(sh)::value>, grid, block, 0, s, kp);
         else
             hipLaunchKernelGGL(urtss_recur_l1<decltype(sh)::value>, grid, block, 0, s, kp);
     });
@@ -525,11 +565,14 @@ int launch_backward_work(const KParams& kp, const NoiseParams* np, hipStream_t s
 }
 
 // The launch of ste_urtss_backward_sched_f64: a wave per item of the table that entry point has built and uploaded.
-int launch_recur_sched(bool shift, int nitems, const SmoothSchedParams& sp, hipStream_t s) {
-    if (shift)
-        hipLaunchKernelGGL(urtss_recur_sched<true>, dim3((unsigned)nitems), dim3(64), 0, s, sp);
-    else
-        hipLaunchKernelGGL(urtss_recur_sched<false>, dim3((unsigned)nitems), dim3(64), 0, s, sp);
+// `plain`: every window of the table is a plain batch (ste_ukf.h: plain_batch).
+int launch_recur_sched(bool shift, bool plain, int nitems, const SmoothSchedParams& sp, hipStream_t s) {
+    with_bool(shift, [&](auto sh) {
+        if (plain)
+            hipLaunchKernelGGL(urtss_recur_sched_plain<decltype(sh)::value>, dim3((unsigned)nitems), dim3(64), 0, s, sp);
+        else
+            hipLaunchKernelGGL(urtss_recur_sched<decltype(sh)::value>, dim3((unsigned)nitems), dim3(64), 0, s, sp);
+    });
     return abi_check_hip(hipGetLastError(), "urtss_recur_sched launch");
 }
 

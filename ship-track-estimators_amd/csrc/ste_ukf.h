@@ -152,6 +152,13 @@ __device__ __forceinline__ void store_pos(const KParams& p, size_t row, size_t B
     }
 }
 
+// A "plain batch": packed covariances, no recorded noise, no position copy -- DeviceBatch's default, and what the benchmark,
+// run_fleet and the CLI launch.  All three are facts of the launch that the general step loops test at every step (and keep
+// a pointer live for); the host picks kernels with them compiled in (kPlain of forward_tile_l1 / smooth_tile_l1).
+inline bool plain_batch(const KParams& kp) {
+    return (kp.flags & STE_FLAG_PACKED_COV) && !kp.noise_pred && !kp.noise_upd && !kp.noise_rts && !kp.sm_pos;
+}
+
 // Covariance histories (fwd_cov, sm_cov) come in two layouts: [row][16][B] full 4 x 4 matrices, the reference's return
 // shape, or -- STE_FLAG_PACKED_COV -- [row][10][B] upper triangles (row-major: 00 01 02 03 11 12 13 22 23 33).  The
 // matrices are symmetric by construction, so the packed form loses nothing; it takes 48 of 128 bytes off every history
@@ -179,6 +186,36 @@ __device__ __forceinline__ void load_cov_p(const double* base, bool packed, size
     for (int r = 0; r < 4; ++r) {
         STE_UNROLL
         for (int c = r; c < 4; ++c) P[tix(r, c)] = base[cov_at(packed, row, r, c) * B + t];
+    }
+}
+// The same three with the layout as a template argument, for the "plain batch" step loops (plain_batch below).  With a
+// run-time `packed` the six entries whose packed and full indices differ cost a 64-bit (row_sel + const) * B each, per row;
+// with the layout compiled in every entry is the one before it plus B.
+template <bool kPacked>
+__device__ __forceinline__ size_t cov_at(size_t row, int r, int c) {  // r <= c
+    return kPacked ? row * 10 + (size_t)(r * 4 - (r * (r - 1)) / 2 + (c - r)) : row * 16 + (size_t)(r * 4 + c);
+}
+template <bool kPacked>
+__device__ __forceinline__ void store_cov_p(double* base, size_t row, size_t B, size_t t, const double (&P)[10]) {
+    STE_UNROLL
+    for (int r = 0; r < 4; ++r) {
+        STE_UNROLL
+        for (int c = r; c < 4; ++c) st_stream(&base[cov_at<kPacked>(row, r, c) * B + t], P[tix(r, c)]);
+    }
+    if (!kPacked) {
+        STE_UNROLL
+        for (int r = 1; r < 4; ++r) {
+            STE_UNROLL
+            for (int c = 0; c < r; ++c) st_stream(&base[(row * 16 + r * 4 + c) * B + t], P[tix(r, c)]);
+        }
+    }
+}
+template <bool kPacked>
+__device__ __forceinline__ void load_cov_p(const double* base, size_t row, size_t B, size_t t, double (&P)[10]) {
+    STE_UNROLL
+    for (int r = 0; r < 4; ++r) {
+        STE_UNROLL
+        for (int c = r; c < 4; ++c) P[tix(r, c)] = base[cov_at<kPacked>(row, r, c) * B + t];
     }
 }
 // full 4 x 4 <-> history row (the literal kernels); the packed layout keeps the upper triangle
