@@ -454,6 +454,58 @@ def _index_int32(x):
     return x.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
 
 
+def column_pointer(ten, col: int) -> int:
+    """The address of column ``col`` of a tensor whose last dimension is the track: what a kernel takes as the first track
+    of a window that reads or writes rows as wide as the tensor's."""
+    return ten.data_ptr() + ten.element_size() * col
+
+
+def track_outputs(struct, width: int, col: int, B: int, spec, device) -> dict:
+    """The per-track outputs of a metric call.  ``spec``: (field, leading shape, dtype, fill) per output; ``fill`` None leaves
+    the tensor as allocated (``torch.empty``), 0 zeroes it, anything else (NaN, -1) fills it.  Each is allocated
+    ``leading + (width,)`` on ``device``, ``struct.<field>`` is set to its column ``col``, and the dict returned holds the
+    views ``[..., col:col + B]``: for a window read in place (``_fleet_layout``) the call writes this window's columns of rows
+    as wide as the fleet's and nothing else."""
+    import torch
+
+    out = {}
+    for field, leading, dtype, fill in spec:
+        shape = tuple(leading) + (width,)
+        if fill is None:
+            ten = torch.empty(shape, dtype=dtype, device=device)
+        elif fill == 0:
+            ten = torch.zeros(shape, dtype=dtype, device=device)
+        else:
+            ten = torch.full(shape, fill, dtype=dtype, device=device)
+        setattr(struct, field, column_pointer(ten, col))
+        out[field] = ten[..., col:col + B]
+    return out
+
+
+def track_input(x, B: int, width: int, col: int, keep: list, device, expect: str, scalar: bool = False):
+    """A per-track input of a metric call -- None, a scalar or one value per track, (B,) -- as the pointer the kernel
+    takes: column ``col`` of a zeroed float64 row ``width`` tracks wide that holds the values in this batch's columns (the
+    row is appended to ``keep``); None for None.  ``scalar``: the kernel takes a scalar beside the pointer, and the result is
+    the pair (pointer, value): (None, the float) for a 0-d value, (pointer, None) for (B,).  ``expect``: how the message
+    for any other shape begins, which differs between the callers."""
+    import torch
+
+    if x is None:
+        return (None, None) if scalar else None
+    tv = torch.as_tensor(x, dtype=torch.float64)
+    if tv.dim() == 0:
+        if scalar:
+            return None, float(tv)
+    elif tuple(tv.shape) != (B,):
+        raise ValueError(f"{expect}, got {tuple(tv.shape)}")
+    tv = tv.to(device).expand(B)
+    row = torch.zeros((width,), dtype=torch.float64, device=device)
+    row[col:col + B] = tv
+    keep.append(row)
+    ptr = column_pointer(row, col)
+    return (ptr, None) if scalar else ptr
+
+
 class DeviceBatch:
     """A HostBatch resident in HBM plus its output buffers; ``forward`` / ``backward`` / ``run`` launch the kernels."""
 
@@ -694,18 +746,12 @@ class DeviceBatch:
         """``t0`` of a metric call (None, a scalar or one clock time per track) as the pointer the kernel takes, or None.
         Inside the stream context.  ``name``: what the value is called in the message (another per-track input of the
         same form, such as ``track_margin_km``)."""
-        if t0 is None:
-            return None
-        torch, B = self.torch, self.ntracks
-        tv = torch.as_tensor(t0, dtype=torch.float64).to(self.device)
-        if tv.dim() == 0:
-            tv = tv.expand(B)
-        if tuple(tv.shape) != (B,):
-            raise ValueError(f"{name} must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
-        clock = torch.zeros((width,), dtype=torch.float64, device=self.device)
-        clock[col:col + B] = tv
-        keep.append(clock)
-        return clock.data_ptr() + 8 * col
+        B = self.ntracks
+        return track_input(t0, B, width, col, keep, self.device, f"{name} must be None, a scalar or have shape ({B},)")
+
+    def _track_outputs(self, struct, width, col, spec):
+        """``track_outputs`` for this batch's tracks on its device.  Inside the stream context."""
+        return track_outputs(struct, width, col, self.ntracks, spec, self.device)
 
     def _finish(self, st, keep, out):
         """After the launch: inputs and outputs stay allocated until ``st`` has passed it."""
@@ -789,11 +835,10 @@ class DeviceBatch:
             ll = torch.empty((B,), dtype=torch.float64, **dev)
             dof = torch.empty((B,), dtype=torch.int32, **dev)
             nupd = torch.empty((B,), dtype=torch.int32, **dev)
-            nis_t = torch.full((N + 1, ld), float("nan"), dtype=torch.float64, **dev) if nis else None
+            lk = binding.SteUkfLoglikF64(ll.data_ptr(), dof.data_ptr(), nupd.data_ptr(), None)
+            nis_t = self._track_outputs(lk, ld, col, [("nis", (N + 1,), torch.float64, float("nan"))])["nis"] if nis else None
             s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
             s.flags = (s.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
-            lk = binding.SteUkfLoglikF64(ll.data_ptr(), dof.data_ptr(), nupd.data_ptr(),
-                                         None if nis_t is None else nis_t.data_ptr() + 8 * col)
             if self.noise is not None:
                 binding.check(self.lib.ste_ukf_forward_noise_f64(C.byref(s), C.byref(self.noise), C.byref(lk), self._stream(st)),
                               "ste_ukf_forward_noise_f64")
@@ -803,7 +848,7 @@ class DeviceBatch:
             self._mark_use(st)
             return LogLikelihood(loglik=ll.cpu().numpy(), dof=dof.cpu().numpy(), nupd=nupd.cpu().numpy(),
                                  status=self.status.cpu().numpy(),
-                                 nis=None if nis_t is None else nis_t[:, col:col + B].T.cpu().numpy())
+                                 nis=None if nis_t is None else nis_t.T.cpu().numpy())
 
     # -- measurement noise fitted to the data ("Noise fit") -------------------------------------------
     _NOISE_STRUCTURES = {"scalar": binding.STE_NOISE_FIT_SCALAR, "diag2": binding.STE_NOISE_FIT_DIAG2,
@@ -822,15 +867,13 @@ class DeviceBatch:
         st = self._ordered_stream(stream)
         B, ld, col = self.ntracks, int(self.struct.track_stride or self.struct.B), self.lo
         with torch.cuda.stream(st):
-            mom = torch.zeros((10, ld), dtype=torch.float64, device=self.device)
-            vsum = torch.zeros((4, ld), dtype=torch.float64, device=self.device)
-            count = torch.zeros((ld,), dtype=torch.int32, device=self.device)
-            tstat = torch.zeros((B,), dtype=torch.int32, device=self.device)
-            nm = binding.SteNoiseMomentsF64(mom.data_ptr() + 8 * col, count.data_ptr() + 4 * col, vsum.data_ptr() + 8 * col,
-                                            tstat.data_ptr(), 0, 0)
+            nm = binding.SteNoiseMomentsF64()
+            out = self._track_outputs(nm, ld, col, [("moments", (10,), torch.float64, 0), ("count", (), torch.int32, 0),
+                                                    ("vsum", (4,), torch.float64, 0)])
+            out["track_status"] = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            nm.track_status = out["track_status"].data_ptr()
             binding.check(self.lib.ste_ukf_noise_moments_f64(C.byref(self.struct), C.byref(nm), self._stream(st)),
                           "ste_ukf_noise_moments_f64")
-            out = dict(moments=mom[:, col:col + B], count=count[col:col + B], vsum=vsum[:, col:col + B], track_status=tstat)
             return self._finish(st, [], out)
 
     def update_measurement_noise(self, moments, groups=None, structure: str = "scalar", stream=None):
@@ -893,7 +936,7 @@ class DeviceBatch:
         N, ld = int(self.struct.Nmax), int(self.struct.track_stride or self.struct.B)
         coef = torch.empty((N + 1, binding.STE_SAMPLE_COEF_ROWS, ld), dtype=torch.float64, device=self.device)
         status = torch.zeros((self.ntracks,), dtype=torch.int32, device=self.device)
-        sm = binding.SteUkfSampleF64(int(nsamples), 0, samples.data_ptr() + 8 * self.lo, coef.data_ptr() + 8 * self.lo,
+        sm = binding.SteUkfSampleF64(int(nsamples), 0, column_pointer(samples, self.lo), column_pointer(coef, self.lo),
                                      status.data_ptr())
         return sm, status, (samples, coef)
 
@@ -964,7 +1007,7 @@ class DeviceBatch:
         with torch.cuda.stream(st):
             full = torch.zeros((N, rows, ld), dtype=torch.float64, device=self.device)
             status = torch.zeros((B,), dtype=torch.int32, device=self.device)
-            lg = binding.SteLagOneF64(full.data_ptr() + 8 * self.lo, status.data_ptr(),
+            lg = binding.SteLagOneF64(column_pointer(full, self.lo), status.data_ptr(),
                                       binding.STE_LAG1_POSITION if position_only else 0, 0)
             noise = None if self.noise is None else C.byref(self.noise)
             binding.check(self.lib.ste_urtss_lag_one_f64(C.byref(self.struct), noise, C.byref(lg), self._stream(st)),
@@ -1036,14 +1079,14 @@ class DeviceBatch:
             else:
                 ws = torch.empty((N + 1, ld), **f64)
                 ws[:, self.lo:self.lo + B].copy_(knots)
-                pc.knots = ws.data_ptr() + 8 * self.lo
+                pc.knots = column_pointer(ws, self.lo)
                 keep.append(ws)
             if N == 0 or lag_one.stride() == (rows * ld, ld, 1):
                 pc.lag1 = lag_one.data_ptr() if N > 0 else None
             else:
                 lw = torch.empty((N, rows, ld), **f64)
                 lw[..., self.lo:self.lo + B].copy_(lag_one)
-                pc.lag1 = lw.data_ptr() + 8 * self.lo
+                pc.lag1 = column_pointer(lw, self.lo)
                 keep.append(lw)
             keep += [knots, lag_one]
             pc.cov = self.struct.sm_cov
@@ -1088,38 +1131,23 @@ class DeviceBatch:
         if (line_axis is None) != (line_value is None):
             raise ValueError("line_axis and line_value go together: a line is an axis ('lon' / 'lat') and its value in degrees")
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             keep = []
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=line_axis is not None)
-            dist = torch.empty((S, width), **f64)
-            cum = torch.full((S, N + 1, width), float("nan"), **f64) if cumulative else None
             pm = binding.StePathF64()
             pm.nstates, pm.model, pm.states = S, model_id, states.data_ptr()
-            pm.dist = dist.data_ptr() + 8 * col
-            pm.cumdist = None if cum is None else cum.data_ptr() + 8 * col
             pm.line_axis, pm.reserved = -1, 0
-            ct = nc = None
+            spec = [("dist", (S,), f64, None)] + ([("cumdist", (S, N + 1), f64, float("nan"))] if cumulative else [])
+            out = self._track_outputs(pm, width, col, spec)
             if line_axis is not None:
-                lv = torch.as_tensor(line_value, dtype=torch.float64).to(self.device)
-                if lv.dim() == 0:
-                    lv = lv.expand(B)
-                if tuple(lv.shape) != (B,):
-                    raise ValueError(f"line_value must be a scalar or have shape ({B},), got {tuple(lv.shape)}")
-                line = torch.zeros((width,), **f64)
-                line[col:col + B] = lv
-                ct = torch.empty((S, width), **f64)
-                nc = torch.empty((S, width), dtype=torch.int32, device=self.device)
-                pm.line_axis, pm.line_value = self._PATH_AXES[line_axis], line.data_ptr() + 8 * col
-                pm.cross_time, pm.ncross = ct.data_ptr() + 8 * col, nc.data_ptr() + 4 * col
-                keep.append(line)
+                pm.line_axis = self._PATH_AXES[line_axis]
+                pm.line_value = track_input(line_value, B, width, col, keep, self.device,
+                                            f"line_value must be a scalar or have shape ({B},)")
+                out.update(self._track_outputs(pm, width, col, [("cross_time", (S,), f64, None), ("ncross", (S,), i32, None)]))
             binding.check(self.lib.ste_path_metrics_f64(C.byref(s), C.byref(pm), self._stream(st)), "ste_path_metrics_f64")
-            out = {"distance": dist[:, col:col + B]}
-            if cum is not None:
-                out["cumulative"] = cum[..., col:col + B]
-            if ct is not None:
-                out["cross_time"], out["ncross"] = ct[:, col:col + B], nc[:, col:col + B]
-            return self._finish(st, keep, out)
+            names = {"dist": "distance", "cumdist": "cumulative"}
+            return self._finish(st, keep, {names.get(k, k): ten for k, ten in out.items()})
 
     # -- regions --------------------------------------------------------------------------------------------------
     def region_metrics(self, states, polygon, model: str = "sphere", distance: bool = False, mask: bool = False, stream=None):
@@ -1135,36 +1163,26 @@ class DeviceBatch:
         Windows, in-place views and ``stream`` as in ``path_metrics``; every value depends on its own track's rows and the
         polygon alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
+        N = int(self.struct.Nmax)
         states, S = self._metric_states(states)
         model_id = _metric_model(model)
         poly = polygon if isinstance(polygon, RegionPolygon) else region_polygon(polygon)
         V = int(poly.vert.shape[1])
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             vert = torch.from_numpy(poly.vert).to(self.device)
             keep = [vert]
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
-            tin, first = torch.empty((S, width), **f64), torch.empty((S, width), **f64)
-            nent, nbrk = torch.empty((S, width), **i32), torch.empty((S, width), **i32)
-            din = torch.empty((S, width), **f64) if distance else None
-            flags = torch.zeros((S, N + 1, width), dtype=torch.uint8, device=self.device) if mask else None
             rg = binding.SteRegionF64()
             rg.nstates, rg.model, rg.states = S, model_id, states.data_ptr()
             rg.nvert, rg.reserved, rg.vert, rg.lon_ref = V, 0, vert.data_ptr(), float(poly.lon_ref)
-            rg.time_inside, rg.first_entry = tin.data_ptr() + 8 * col, first.data_ptr() + 8 * col
-            rg.nenter, rg.nbroken = nent.data_ptr() + 4 * col, nbrk.data_ptr() + 4 * col
-            rg.dist_inside = None if din is None else din.data_ptr() + 8 * col
-            rg.inside = None if flags is None else flags.data_ptr() + col
+            spec = [("time_inside", (S,), f64, None), ("first_entry", (S,), f64, None), ("nenter", (S,), i32, None),
+                    ("nbroken", (S,), i32, None)]
+            spec += [("dist_inside", (S,), f64, None)] if distance else []
+            spec += [("inside", (S, N + 1), torch.uint8, 0)] if mask else []
+            out = self._track_outputs(rg, width, col, spec)
             binding.check(self.lib.ste_region_metrics_f64(C.byref(s), C.byref(rg), self._stream(st)), "ste_region_metrics_f64")
-            out = {"time_inside": tin[:, col:col + B], "first_entry": first[:, col:col + B], "nenter": nent[:, col:col + B],
-                   "nbroken": nbrk[:, col:col + B]}
-            if din is not None:
-                out["dist_inside"] = din[:, col:col + B]
-            if flags is not None:
-                out["inside"] = flags[..., col:col + B]
             return self._finish(st, keep, out)
 
     # -- grids ----------------------------------------------------------------------------------------------------
@@ -1180,7 +1198,6 @@ class DeviceBatch:
         the grid's bits do not depend on how the tracks were split into calls.  Windows, in-place views and ``stream`` as in
         ``path_metrics``."""
         torch = self.torch
-        B = self.ntracks
         states, S = self._metric_states(states)
         if not isinstance(grid, TrackGrid):
             raise ValueError("grid must be a TrackGrid (track_estimators.batch.track_grid makes one)")
@@ -1201,16 +1218,14 @@ class DeviceBatch:
                 ent = None
             keep = [ticks] + ([ent] if ent is not None else [])
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
-            outside, total = torch.zeros((S, width), **i64), torch.zeros((S, width), **i64)
-            nbrk = torch.zeros((S, width), dtype=torch.int32, device=self.device)
             g = binding.SteGridF64()
             g.nstates, g.flags, g.states = S, binding.STE_GRID_PERIODIC_LON if grid.periodic else 0, states.data_ptr()
             g.nx, g.ny, g.lon0, g.lat0, g.dlon, g.dlat, g.lon_ref = nx, ny, grid.lon0, grid.lat0, grid.dlon, grid.dlat, grid.lon_ref
             g.ticks, g.entries = ticks.data_ptr(), None if ent is None else ent.data_ptr()
-            g.outside, g.total, g.nbroken = outside.data_ptr() + 8 * col, total.data_ptr() + 8 * col, nbrk.data_ptr() + 4 * col
+            per_track = self._track_outputs(g, width, col, [("outside", (S,), torch.int64, 0), ("total", (S,), torch.int64, 0),
+                                                            ("nbroken", (S,), torch.int32, 0)])
             binding.check(self.lib.ste_grid_metrics_f64(C.byref(s), C.byref(g), self._stream(st)), "ste_grid_metrics_f64")
-            res = {"ticks": ticks, "hours": ticks.to(torch.float64) / float(binding.STE_GRID_TICKS_PER_HOUR),
-                   "outside": outside[:, col:col + B], "total": total[:, col:col + B], "nbroken": nbrk[:, col:col + B]}
+            res = {"ticks": ticks, "hours": ticks.to(torch.float64) / float(binding.STE_GRID_TICKS_PER_HOUR), **per_track}
             if ent is not None:
                 res["entries"] = ent
             return self._finish(st, keep, res)
@@ -1234,7 +1249,7 @@ class DeviceBatch:
         each row lies in, NaN off the grid and past ``nsteps[b]``.  Windows, in-place views and ``stream`` as in
         ``grid_metrics``; every value depends on its own track's rows and the raster alone."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
+        N = int(self.struct.Nmax)
         states, S = self._metric_states(states)
         if not isinstance(raster, TrackRaster):
             raise ValueError("raster must be a TrackRaster (track_estimators.batch.track_raster makes one)")
@@ -1246,20 +1261,17 @@ class DeviceBatch:
         with torch.cuda.stream(st):
             keep = [raster.values]
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
-            names = _RASTER_OUTPUTS + (_RASTER_HIT_OUTPUTS if threshold is not None else ())
-            ten = {k: torch.empty((S, width), dtype=getattr(torch, dt), device=self.device) for k, dt in names}
-            rv = torch.full((S, N + 1, width), float("nan"), dtype=torch.float64, device=self.device) if rows else None
             r = binding.SteRasterF64()
             r.nstates, r.states = S, states.data_ptr()
             r.flags = flags | (binding.STE_GRID_PERIODIC_LON if grid.periodic else 0)
             r.nx, r.ny, r.lon0, r.lat0, r.dlon, r.dlat, r.lon_ref = (grid.nx, grid.ny, grid.lon0, grid.lat0, grid.dlon, grid.dlat,
                                                                      grid.lon_ref)
             r.values, r.threshold, r.min_ticks = raster.values.data_ptr(), thr, min_ticks
-            for k, v in ten.items():
-                setattr(r, k, v.data_ptr() + v.element_size() * col)
-            r.row_value = None if rv is None else rv.data_ptr() + 8 * col
+            names = _RASTER_OUTPUTS + (_RASTER_HIT_OUTPUTS if threshold is not None else ())
+            spec = [(k, (S,), getattr(torch, dt), None) for k, dt in names]
+            spec += [("row_value", (S, N + 1), torch.float64, float("nan"))] if rows else []
+            out = self._track_outputs(r, width, col, spec)
             binding.check(self.lib.ste_raster_metrics_f64(C.byref(s), C.byref(r), self._stream(st)), "ste_raster_metrics_f64")
-            out = {k: v[:, col:col + B] for k, v in ten.items()}
             tph = float(binding.STE_GRID_TICKS_PER_HOUR)
             nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
             hours = {"valid": "valid_hours", "tmin": "tmin_hours", "tmax": "tmax_hours", "hit_ticks": "hit_hours",
@@ -1268,8 +1280,8 @@ class DeviceBatch:
                 if k in out:
                     out[name] = torch.where(out[k] < 0, nan, out[k].to(torch.float64) / tph)
             out["mean"] = torch.where(out["valid"] > 0, out["wsum"] / out["valid"].to(torch.float64), nan)
-            if rv is not None:
-                out["row_value"] = rv[..., col:col + B]
+            if rows:
+                out["row_value"] = out.pop("row_value")  # after the derived values, where it always was
             return self._finish(st, keep, out)
 
     # -- encounters -----------------------------------------------------------------------------------------------
@@ -1492,12 +1504,9 @@ class DeviceBatch:
                 kn = knots  # the view a call of the same kind returned: read where it lies
                 po.knots = kn.data_ptr()
             else:
-                ws = torch.empty((N + 1, width), **f64)
-                kn = ws[:, col:col + B]
+                kn = self._track_outputs(po, width, col, [("knots", (N + 1,), torch.float64, None)])["knots"]
                 if knots is not None:
                     kn.copy_(knots)
-                po.knots = ws.data_ptr() + 8 * col
-                keep.append(ws)
             if knots is not None:
                 po.flags = binding.STE_POS_REUSE_KNOTS
             keep.append(kn)
@@ -1544,21 +1553,20 @@ class DeviceBatch:
         -1) and ``status`` as the only output.  Row 0 holds 0, or NaN for a track with a ``dt`` that is not finite and >= 0;
         rows past ``nsteps[b]`` are NaN.  ``field_at`` and ``positions_at`` take it as ``knots=``."""
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
+        N = int(self.struct.Nmax)
         ld = int(self.struct.track_stride or self.struct.B)
         st = self._ordered_stream(stream)
         with torch.cuda.stream(st):
             s = binding.SteUkfBatchF64.from_buffer_copy(self.struct)
-            ws = torch.full((N + 1, ld), float("nan"), dtype=torch.float64, device=self.device)
+            po = binding.StePositionsF64()
+            out = self._track_outputs(po, ld, self.lo, [("knots", (N + 1,), torch.float64, float("nan"))])
             qt = torch.full((1,), -1, dtype=torch.int32, device=self.device)
             tq = torch.zeros((1,), dtype=torch.float64, device=self.device)  # also stands in for `states`: nothing reads it
             status = torch.empty((1,), dtype=torch.int32, device=self.device)
-            po = binding.StePositionsF64()
             po.nstates, po.flags, po.states = 1, 0, tq.data_ptr()
-            po.nqueries, po.qtrack, po.qtime = 1, qt.data_ptr(), tq.data_ptr()
-            po.knots, po.status = ws.data_ptr() + 8 * self.lo, status.data_ptr()
+            po.nqueries, po.qtrack, po.qtime, po.status = 1, qt.data_ptr(), tq.data_ptr(), status.data_ptr()
             binding.check(self.lib.ste_track_positions_f64(C.byref(s), C.byref(po), self._stream(st)), "ste_track_positions_f64")
-            return self._finish(st, [ws, qt, tq, status], {"knots": ws[:, self.lo:self.lo + B]})["knots"]
+            return self._finish(st, [qt, tq, status], out)["knots"]
 
     def field_at(self, states, field, qtrack, qtime, t0=None, nearest: bool = False, min_cover: float = 0.0, vanchor=None,
                  accumulate=None, knots=None, per_sample: bool = True, stream=None, sort: bool = True):
@@ -1635,11 +1643,8 @@ class DeviceBatch:
                 kn = knots  # the view a call on this layout returned: read where it lies
                 f.knots = kn.data_ptr()
             else:
-                ws = torch.empty((N + 1, width), **f64)
-                kn = ws[:, col:col + B]
+                kn = self._track_outputs(f, width, col, [("knots", (N + 1,), torch.float64, None)])["knots"]
                 kn.copy_(knots)
-                f.knots = ws.data_ptr() + 8 * col
-                keep.append(ws)
             keep.append(kn)
             f.nx, f.ny, f.nt, f.reserved = grid.nx, grid.ny, field.nt, 0
             f.lon0, f.lat0, f.dlon, f.dlat, f.lon_ref = grid.lon0, grid.lat0, grid.dlon, grid.dlat, grid.lon_ref
@@ -1701,7 +1706,6 @@ class DeviceBatch:
         views and ``stream`` as in ``path_metrics``; for a window read in place the per-track outputs are views of rows as
         wide as the fleet's.  Every value depends on the track's rows, ``dt``, ``t0`` and the site's three numbers alone."""
         torch = self.torch
-        B = self.ntracks
         states, S = self._metric_states(states)
         model_id = _metric_model(model)
         sv = torch.as_tensor(sites, dtype=torch.float64)
@@ -1714,8 +1718,7 @@ class DeviceBatch:
         if tuple(rv.shape) != (M,):
             raise ValueError(f"radius_km must be a scalar or have shape ({M},), got {tuple(rv.shape)}")
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             xy = sv.to(self.device).t().contiguous()  # [2][M]: lon then lat
             rad = rv.to(self.device).contiguous()
@@ -1726,15 +1729,11 @@ class DeviceBatch:
             si.nsites, si.sites, si.radius_km, si.flags, si.reserved = M, xy.data_ptr(), rad.data_ptr(), 0, 0
             si.t0 = self._track_clock(t0, width, col, keep)
             # rows as wide as the states': the window's columns are what the call writes and what is returned
-            full = {k: torch.empty((S, M, width), **f64) for k in self._SITE_OUT3}
-            full["nwithin"] = torch.empty((S, M, width), **i32)
-            full["sound_time"] = torch.empty((S, width), **f64)
-            full["nbroken"] = torch.empty((S, width), **i32)
-            full["track_status"] = torch.empty((width,), **i32)
-            for k, ten in full.items():
-                setattr(si, k, ten.data_ptr() + ten.element_size() * col)
-            out = {k: ten[..., col:col + B] for k, ten in full.items()}
-            out["site_status"] = torch.empty((M,), **i32)
+            spec = [(k, (S, M), f64, None) for k in self._SITE_OUT3]
+            spec += [("nwithin", (S, M), i32, None), ("sound_time", (S,), f64, None), ("nbroken", (S,), i32, None),
+                     ("track_status", (), i32, None)]
+            out = self._track_outputs(si, width, col, spec)
+            out["site_status"] = torch.empty((M,), dtype=i32, device=self.device)
             si.site_status = out["site_status"].data_ptr()
             binding.check(self.lib.ste_site_metrics_f64(C.byref(s), C.byref(si), self._stream(st)), "ste_site_metrics_f64")
             return self._finish(st, keep, out)
@@ -1758,14 +1757,12 @@ class DeviceBatch:
         ``line_status`` (M,) int32, STE_LINE_BAD_LINE.  Windows, in-place views and ``stream`` as in ``site_metrics``.  Every
         value depends on the track's rows, ``dt``, ``t0`` and the line's vertices alone."""
         torch = self.torch
-        B = self.ntracks
         states, S = self._metric_states(states)
         model_id = _metric_model(model)
         tl = lines if isinstance(lines, TrackLines) else track_lines(lines)
         M, V = tl.nlines, int(tl.vert.shape[1])
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             vert, first, ref = tl.on(self.device)
             keep = [vert, first, ref]
@@ -1779,14 +1776,10 @@ class DeviceBatch:
             names = dict(self._LINE_OUT3)
             if crossings:
                 names.update(self._LINE_CROSS)
-            full = {k: torch.empty((S, M, width), **(i32 if isint else f64)) for k, isint in names.items()}
-            full["sound_time"] = torch.empty((S, width), **f64)
-            full["nbroken"] = torch.empty((S, width), **i32)
-            full["track_status"] = torch.empty((width,), **i32)
-            for k, ten in full.items():
-                setattr(li, k, ten.data_ptr() + ten.element_size() * col)
-            out = {k: ten[..., col:col + B] for k, ten in full.items()}
-            out["line_status"] = torch.empty((M,), **i32)
+            spec = [(k, (S, M), i32 if isint else f64, None) for k, isint in names.items()]
+            spec += [("sound_time", (S,), f64, None), ("nbroken", (S,), i32, None), ("track_status", (), i32, None)]
+            out = self._track_outputs(li, width, col, spec)
+            out["line_status"] = torch.empty((M,), dtype=i32, device=self.device)
             li.line_status = out["line_status"].data_ptr()
             binding.check(self.lib.ste_line_metrics_f64(C.byref(s), C.byref(li), self._stream(st)), "ste_line_metrics_f64")
             return self._finish(st, keep, out)
@@ -1855,8 +1848,7 @@ class DeviceBatch:
             if edges.ndim != 1 or not 2 <= edges.size <= binding.STE_SPEED_MAX_BANDS + 1:
                 raise ValueError(f"bands must be None or 2 .. {binding.STE_SPEED_MAX_BANDS + 1} band edges, got shape {edges.shape}")
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             keep = []
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=True)
@@ -1866,30 +1858,22 @@ class DeviceBatch:
             sp.nbands, sp.band_edges = (0, None) if edges is None else (edges.size - 1, edges.ctypes.data)
             sp.threshold, sp.threshold_all = None, float("nan")
             if threshold is not None:
-                tv = torch.as_tensor(threshold, dtype=torch.float64)
-                if tv.dim() == 0:
-                    sp.threshold_all = float(tv)
-                elif tuple(tv.shape) == (B,):
-                    limit = torch.zeros((width,), **f64)
-                    limit[col:col + B] = tv.to(self.device)
-                    keep.append(limit)
-                    sp.threshold = limit.data_ptr() + 8 * col
-                else:
-                    raise ValueError(f"threshold must be None, a scalar or have shape ({B},), got {tuple(tv.shape)}")
+                sp.threshold, scalar = track_input(threshold, B, width, col, keep, self.device,
+                                                   f"threshold must be None, a scalar or have shape ({B},)", scalar=True)
+                if scalar is not None:
+                    sp.threshold_all = scalar
             # rows as wide as the states': the window's columns are what the call writes and what is returned
-            full = {k: torch.empty((S, width), **f64) for k in self._SPEED_OUT}
-            full["nbroken"] = torch.empty((S, width), **i32)
-            full["track_status"] = torch.empty((width,), **i32)
+            spec = [(k, (S,), f64, None) for k in self._SPEED_OUT]
+            spec += [("nbroken", (S,), i32, None), ("track_status", (), i32, None)]
             if edges is not None:
-                full["band_time"] = torch.empty((S, edges.size - 1, width), **f64)
+                spec.append(("band_time", (S, edges.size - 1), f64, None))
             if threshold is not None:
-                full.update({k: torch.empty((S, width), **(i32 if int32 else f64)) for k, int32 in self._SPEED_RUNS.items()})
+                spec += [(k, (S,), i32 if int32 else f64, None) for k, int32 in self._SPEED_RUNS.items()]
             if per_step:
-                full["speed"] = torch.full((S, N, width), float("nan"), **f64)
-            for k, ten in full.items():
-                setattr(sp, k, ten.data_ptr() + ten.element_size() * col)
+                spec.append(("speed", (S, N), f64, float("nan")))
+            out = self._track_outputs(sp, width, col, spec)
             binding.check(self.lib.ste_speed_metrics_f64(C.byref(s), C.byref(sp), self._stream(st)), "ste_speed_metrics_f64")
-            return self._finish(st, keep, {k: ten[..., col:col + B] for k, ten in full.items()})
+            return self._finish(st, keep, out)
 
     # -- errors ---------------------------------------------------------------------------------------------------
     _ERROR_OUT = {"sum_err": False, "sum_sq": False, "max_err": False, "n": True, "max_row": True, "nbroken": True}  # name -> int32?
@@ -1917,7 +1901,7 @@ class DeviceBatch:
         wide = torch.full(x.shape[:-1] + (width,), float("nan"), dtype=torch.float64, device=self.device)
         wide[..., col:col + B] = x
         keep.append(wide)
-        return wide.data_ptr() + 8 * col, r
+        return column_pointer(wide, col), r
 
     def track_errors(self, states, truth, course=None, cov=None, coverage: float = 0.95, model: str = "sphere", rows: bool = False,
                      cumulative: bool = False, stream=None):
@@ -1944,7 +1928,7 @@ class DeviceBatch:
         import math
 
         torch = self.torch
-        N, B = int(self.struct.Nmax), self.ntracks
+        N = int(self.struct.Nmax)
         states, S = self._metric_states(states)
         model_id = _metric_model(model)
         if isinstance(cov, str):
@@ -1959,8 +1943,7 @@ class DeviceBatch:
             if not 0.0 < float(coverage) < 1.0:
                 raise ValueError(f"coverage must lie strictly between 0 and 1, got {coverage!r}")
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             keep = []
             s, states, width, col = self._fleet_layout(states, keep, needs_dt=False)
@@ -1981,12 +1964,10 @@ class DeviceBatch:
                 per_row += ["nees"] if rows else []
             per_row += ["cumerr"] if cumulative else []
             # rows as wide as the states': the window's columns are what the call writes and what is returned
-            full = {k: torch.empty((S, width), **(i32 if int32 else f64)) for k, int32 in names.items()}
-            full.update({k: torch.full((S, N + 1, width), float("nan"), **f64) for k in per_row})
-            for k, ten in full.items():
-                setattr(er, k, ten.data_ptr() + ten.element_size() * col)
+            spec = [(k, (S,), i32 if int32 else f64, None) for k, int32 in names.items()]
+            spec += [(k, (S, N + 1), f64, float("nan")) for k in per_row]
+            out = self._track_outputs(er, width, col, spec)
             binding.check(self.lib.ste_track_errors_f64(C.byref(s), C.byref(er), self._stream(st)), "ste_track_errors_f64")
-            out = {k: ten[..., col:col + B] for k, ten in full.items()}
             out["rmse"], out["mean_err"] = torch.sqrt(out["sum_sq"] / out["n"]), out["sum_err"] / out["n"]  # 0 / 0 = NaN
             if course is not None:
                 out["mean_along"] = out["sum_along"] / out["ncoursed"]
@@ -1999,17 +1980,11 @@ class DeviceBatch:
     def _track_limit(self, x, name: str, width, col, keep):
         """A limit of a metric call given as a scalar or one value per track, (B,), as (the pointer the kernel takes or None,
         the scalar it takes beside it).  Inside the stream context."""
-        torch, B = self.torch, self.ntracks
-        tv = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
-        tv = tv.to(torch.float64)
-        if tv.dim() == 0:
-            return None, float(tv)
-        if tuple(tv.shape) != (B,):
-            raise ValueError(f"{name} must be a scalar or have shape ({B},), got {tuple(tv.shape)}")
-        wide = torch.zeros((width,), dtype=torch.float64, device=self.device)
-        wide[col:col + B] = tv.to(self.device)
-        keep.append(wide)
-        return wide.data_ptr() + 8 * col, 0.0
+        B = self.ntracks
+        if not isinstance(x, self.torch.Tensor):
+            x = np.asarray(x, dtype=np.float64)
+        ptr, scalar = track_input(x, B, width, col, keep, self.device, f"{name} must be a scalar or have shape ({B},)", scalar=True)
+        return ptr, 0.0 if scalar is None else scalar
 
     def track_lon_scale(self, states):
         """cos of the smallest |latitude| over the rows <= nsteps of all samples of each track, (B,) on the device: the
@@ -2048,8 +2023,7 @@ class DeviceBatch:
         if compact and not 1 <= cap <= N + 1:
             raise ValueError(f"max_rows must be None or between 1 and Nmax + 1 = {N + 1}, got {max_rows!r}")
         st = self._ordered_stream(stream)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
+        f64, i32 = torch.float64, torch.int32
         with torch.cuda.stream(st):
             keep = []
             scale_t = None
@@ -2067,22 +2041,18 @@ class DeviceBatch:
                 scale_t = keep[-1][col:col + B]
             need = int(self.lib.ste_track_simplify_workspace(N, S, B))
             if need:
-                work = torch.empty(((need + 7) // 8,), **f64)
+                work = torch.empty(((need + 7) // 8,), dtype=f64, device=self.device)
                 keep.append(work)
                 sf.work, sf.work_bytes = work.data_ptr(), need
             # rows as wide as the states': the window's columns are what the call writes and what is returned
-            full = {"keep": torch.zeros((S, N + 1, width), dtype=torch.uint8, device=self.device),
-                    "nkeep": torch.empty((S, width), **i32), "worst_sq": torch.empty((S, width), **f64),
-                    "status": torch.empty((S, width), **i32)}
+            spec = [("keep", (S, N + 1), torch.uint8, 0), ("nkeep", (S,), i32, None), ("worst_sq", (S,), f64, None),
+                    ("status", (S,), i32, None)]
             if compact:
                 sf.cap = cap
-                full["rows"] = torch.full((S, cap, width), -1, **i32)
-                full["out_states"] = torch.full((S, cap, 4, width), float("nan"), **f64)
-                full["out_dt"] = torch.zeros((S, max(cap - 1, 0), width), **f64)
-            for k, ten in full.items():
-                setattr(sf, k, ten.data_ptr() + ten.element_size() * col)
+                spec += [("rows", (S, cap), i32, -1), ("out_states", (S, cap, 4), f64, float("nan")),
+                         ("out_dt", (S, max(cap - 1, 0)), f64, 0)]
+            out = self._track_outputs(sf, width, col, spec)
             binding.check(self.lib.ste_track_simplify_f64(C.byref(s), C.byref(sf), self._stream(st)), "ste_track_simplify_f64")
-            out = {k: ten[..., col:col + B] for k, ten in full.items()}
             out["worst_km"] = torch.sqrt(out.pop("worst_sq")) * KM_PER_DEG
             if scale_t is not None:
                 out["lon_scale"] = scale_t

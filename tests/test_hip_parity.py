@@ -40,6 +40,20 @@ def smoother_form(request):
     batch.default_tuning = prev
 
 
+def test_the_fixtures_reach_the_batch(lanes_per_track, smoother_form):
+    """What the two fixtures set is what a batch that names neither is built with: the lane flags and the tuning word of
+    its struct differ between the fixtures' parameters, so no parity test runs one variant under several names."""
+    from track_estimators import batch, synthetic
+    from track_estimators._hip import binding
+
+    H, Q, R, P0 = synthetic.example_matrices()
+    db = batch.DeviceBatch(batch.pack_uniform(synthetic.make_batch(2, nobs=3, gap_h=1.0, seed0=1), 1, H, Q, R, P0))
+    lane_flags = {1: binding.STE_FLAG_LANES_1, 4: binding.STE_FLAG_LANES_4, 0: 0}
+    assert len(set(lane_flags.values())) == 3
+    assert db.struct.flags & (binding.STE_FLAG_LANES_1 | binding.STE_FLAG_LANES_4) == lane_flags[lanes_per_track]
+    assert db.struct.tuning == smoother_form
+
+
 CASES = [("ukf_synthetic.npz", i) for i in range(10)] + [("ukf_edge.npz", i) for i in range(3)] + [
     ("ukf_ship_01203823.npz", i) for i in range(2)
 ]
