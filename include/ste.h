@@ -1676,7 +1676,11 @@ typedef struct ste_fwd_sched_f64 {
     int32_t* started;                 /* DEVICE [1] or NULL, zero at launch: waves of this launch that have begun */
 } ste_fwd_sched_f64;
 
-/* bytes of host_ws / dev_ws for a schedule of that shape (max_slices = largest ceil(Nmax / slice_steps) over the windows) */
+/* bytes of host_ws / dev_ws for a schedule of that shape (max_slices = largest ceil(Nmax / slice_steps) over the windows, at
+ * least 1).  The launch lays its workspace out by these five numbers alone -- room for max_slices (max_slices + 1) / 2
+ * parameter blocks for EVERY window, the item table, the per-tile counters -- whether or not the windows all have max_slices
+ * slices: a ws_bytes below this size is refused, and the counters sit at ste_ukf_forward_sched_progress_offset (below) of the
+ * same five numbers for any mix of window lengths. */
 size_t ste_ukf_forward_sched_workspace(int32_t nwindows, int32_t max_slices, int64_t ntiles_total, int32_t nrounds,
                                        int32_t nwaves);
 int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream);
@@ -1689,7 +1693,9 @@ int ste_stream_wait_counter(const int32_t* counter, int32_t need, int32_t* error
  * run_rts_smoother (kalman_filter.py:119-137) per track, started as soon as the track's forward pass is complete instead of
  * when its whole window's is.  `items` lists every tile of every window once, in the order the forward schedule finishes
  * them (waves are dispatched in that order).  `progress` is the forward launch's per-tile slice counter array: dev_ws of that
- * launch + ste_ukf_forward_sched_progress_offset(same arguments as ste_ukf_forward_sched_workspace).  Every window must take
+ * launch + ste_ukf_forward_sched_progress_offset(same arguments as ste_ukf_forward_sched_workspace) -- that is where the
+ * forward launch zeroes and counts, for windows of equal and of unequal slice counts alike; int32 [ntiles_total], window by
+ * window, each ending at its window's slice count.  Every window must take
  * the one-kernel smoother (rts_work; more than 4096 tracks, or tuning bit 10) and agree on sog_rate_rts / cog_rate_rts.
  * Waiting waves hold a wave slot each: put ste_stream_wait_counter(started of the forward launch, its nwaves, ...) on `stream`
  * in front of this call, so that every forward wave has its SIMD before a waiting smoother wave could be in its way.  Results
@@ -1708,6 +1714,8 @@ typedef struct ste_bwd_sched_f64 {
     double timeout_s;                 /* bound of a wave's wait; 0 = 2 s */
 } ste_bwd_sched_f64;
 
+/* byte offset of the forward launch's per-tile counters in its dev_ws: ste_ukf_forward_sched_workspace of the same arguments
+ * less the counters themselves (4 bytes per tile, rounded up to 16) */
 size_t ste_ukf_forward_sched_progress_offset(int32_t nwindows, int32_t max_slices, int64_t ntiles_total, int32_t nrounds,
                                              int32_t nwaves);
 size_t ste_urtss_backward_sched_workspace(int32_t nwindows, int64_t ntiles_total);

@@ -1634,6 +1634,14 @@ SchedLayout sched_layout(size_t nkp, size_t nitems, size_t ntiles) {
     l.total = l.progress + align16(ntiles * sizeof(int));
     return l;
 }
+// THE layout of a scheduled forward launch's workspace: the launch, ste_ukf_forward_sched_workspace and
+// ste_ukf_forward_sched_progress_offset all come here, so the per-tile counters sit where a caller is told to look for them
+// whatever the mix of window lengths.  The parameter-block region is sized by the bound a caller can compute without the
+// windows -- max_slices (max_slices + 1) / 2 runs of consecutive slices for each of nwindows -- not by what the windows at hand
+// need (the launch packs theirs at the front of it).
+SchedLayout sched_layout_for(size_t nwindows, size_t max_slices, size_t ntiles, size_t nrounds, size_t nwaves) {
+    return sched_layout(nwindows * (max_slices * (max_slices + 1) / 2), nrounds * nwaves, ntiles);
+}
 
 // `ncopy` bytes of a schedule's table from the caller's host workspace into the device workspace and `nzero` zero bytes behind
 // them (multiples of 16).  Page-locked host memory: a kernel on `s` reads it in place (no copy engine between two launches);
@@ -1734,8 +1742,7 @@ size_t ste_ukf_forward_sched_workspace(int32_t nwindows, int32_t max_slices, int
                                        int32_t nwaves) {
     if (nwindows < 0 || max_slices < 0 || ntiles_total < 0 || nrounds < 0 || nwaves < 0) return 0;
     // a parameter block per (window, run of consecutive slices): max_slices (max_slices + 1) / 2 of them per window
-    return sched_layout((size_t)nwindows * ((size_t)max_slices * ((size_t)max_slices + 1) / 2), (size_t)nrounds * (size_t)nwaves,
-                        (size_t)ntiles_total).total;
+    return sched_layout_for((size_t)nwindows, (size_t)max_slices, (size_t)ntiles_total, (size_t)nrounds, (size_t)nwaves).total;
 }
 
 int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
@@ -1767,8 +1774,9 @@ int ste_ukf_forward_sched_f64(const ste_fwd_sched_f64* sc, void* stream) {
         if (ntiles > 0x7fffffff) return fail(STE_EINVAL, "scheduled forward pass: too many tiles");
     }
     tile0[sc->nwindows] = (int)ntiles;
-    const size_t nitems = (size_t)sc->nrounds * (size_t)sc->nwaves;
-    const SchedLayout lay = sched_layout(nkp, nitems, ntiles);
+    // the windows' blocks (nkp of them, packed by kp0) fill the front of a region sized for nwindows windows of max_slices
+    // slices each: the item table and the counters behind it are where the two size functions say, for any mix of lengths
+    const SchedLayout lay = sched_layout_for((size_t)sc->nwindows, (size_t)max_slices, ntiles, (size_t)sc->nrounds, (size_t)sc->nwaves);
     if (sc->ws_bytes < lay.total) return fail(STE_EINVAL, "scheduled forward pass: workspace too small (ste_ukf_forward_sched_workspace)");
     char* hw = (char*)sc->host_ws;
     ste::KParams* kps = (ste::KParams*)(hw + lay.kps);
@@ -1903,8 +1911,7 @@ int ste_stream_wait_counter(const int32_t* counter, int32_t need, int32_t* error
 size_t ste_ukf_forward_sched_progress_offset(int32_t nwindows, int32_t max_slices, int64_t ntiles_total, int32_t nrounds,
                                              int32_t nwaves) {
     if (nwindows < 0 || max_slices < 0 || ntiles_total < 0 || nrounds < 0 || nwaves < 0) return 0;
-    return sched_layout((size_t)nwindows * ((size_t)max_slices * ((size_t)max_slices + 1) / 2), (size_t)nrounds * (size_t)nwaves,
-                        (size_t)ntiles_total).progress;
+    return sched_layout_for((size_t)nwindows, (size_t)max_slices, (size_t)ntiles_total, (size_t)nrounds, (size_t)nwaves).progress;
 }
 
 size_t ste_urtss_backward_sched_workspace(int32_t nwindows, int64_t ntiles_total) {

@@ -151,6 +151,71 @@ def test_schedule_validation_refuses_tables_that_could_not_progress():
     assert lib.ste_ukf_forward_sched_workspace(2, 2, 4, 2, 4) >= 4 * 64 + 8 * 16 + 16
 
 
+def _align16(v):
+    return (v + 15) & ~15
+
+
+def test_scheduled_workspace_has_one_layout_for_windows_of_unequal_slice_counts():
+    """include/ste.h: the launch lays its workspace out by the five numbers of ste_ukf_forward_sched_workspace -- room for
+    max_slices (max_slices + 1) / 2 parameter blocks for EVERY window -- so that its per-tile counters sit at
+    ste_ukf_forward_sched_progress_offset of the same numbers, where the tile smoothers look, for any mix of window lengths.
+    Windows of 1, 2 and 3 slices need 1 + 3 + 6 = 10 blocks, the documented size holds 3 x 6 = 18: a library that sizes the
+    launch by the 10 takes a workspace 16 bytes short of the documented size and keeps its counters 8 blocks in front of the
+    documented offset.  No GPU needed and none reached: the table is also a slice short, which every build refuses on the host."""
+    import types
+
+    lib, keep = binding.load(), []
+    wins = _minimal_windows(3, keep=keep)  # 3 windows x 2 tiles
+    for w, nmax in zip(wins, (16, 68, 132)):
+        w.Nmax = nmax
+    ws = np.zeros(1 << 16, dtype=np.uint8)
+    ntiles, nslices, nwaves = [2, 2, 2], [1, 2, 3], 4
+    items = batch.forward_schedule(ntiles, nslices, nwaves).copy()
+    _check_schedule(items, ntiles, nslices)
+    last = np.argwhere(items[..., 0] == 2)[-1]
+    items[last[0], last[1]] = (-1, 0)  # a tile of the longest window loses its last slice: never a launch, on any build
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    total = lib.ste_ukf_forward_sched_workspace(3, 3, sum(ntiles), items.shape[0], nwaves)
+    kparams = lib.ste_ukf_forward_sched_workspace(16, 1, 0, 0, 0) // 16  # bytes of a parameter block (16 of them: no rounding)
+    assert lib.ste_ukf_forward_sched_workspace(1, 1, 0, 0, 0) == _align16(kparams)
+    assert total == _align16(18 * kparams) + _align16(16 * items.shape[0] * nwaves) + _align16(4 * sum(ntiles))
+    assert total <= ws.nbytes
+
+    def call(ws_bytes):
+        sc = binding.SteFwdSchedF64()
+        sc.nwindows, sc.windows, sc.slice_steps = 3, C.addressof(wins), 64
+        sc.nwaves, sc.nrounds, sc.items = nwaves, items.shape[0], items.ctypes.data
+        sc.host_ws, sc.dev_ws, sc.ws_bytes = ws.ctypes.data, 0x1000, ws_bytes
+        sc.window_done, sc.error = 0x1000, 0x1000
+        rc = lib.ste_ukf_forward_sched_f64(C.byref(sc), None)
+        return rc, lib.ste_last_error().decode()
+
+    rc, msg = call(total)
+    assert rc == -1 and "missing slices" in msg  # the documented size is enough; the table is what is wrong
+    rc, msg = call(total - 16)
+    assert rc == -1 and "workspace too small" in msg, msg  # ... and anything below it is refused, before the table is read
+
+    # the offset: the workspace less the counters, and behind everything the launch uploads
+    def off(*a):
+        return lib.ste_ukf_forward_sched_progress_offset(*a)
+
+    for nw, ms, nt, nr, nv in [(3, 3, 8, 3, 1024), (3, 3, 6, 3, 4), (2, 3, 130, 3, 1024), (2, 2, 132, 3, 128), (1, 1, 1, 1, 1),
+                               (5, 255, 1000, 40, 64), (20, 8, 3140, 25, 1024)]:
+        o = off(nw, ms, nt, nr, nv)
+        assert o % 16 == 0 and o + _align16(4 * nt) == lib.ste_ukf_forward_sched_workspace(nw, ms, nt, nr, nv)
+        assert o == _align16(nw * (ms * (ms + 1) // 2) * kparams) + _align16(16 * nr * nv)  # blocks by the bound, 16 bytes an item
+        assert off(nw + 1, ms, nt, nr, nv) > o and off(nw, ms + 1, nt, nr, nv) > o
+        assert off(nw, ms, nt, nr + 1, nv) > o and off(nw, ms, nt, nr, nv + 1) > o
+        assert off(nw, ms, nt + 1000, nr, nv) == o  # the counters are last: their number moves nothing in front of them
+    # the Python side hands the library the same five numbers (SmootherPipeline._plan on the windows above)
+    fake = types.SimpleNamespace(forward_cus=1, reserve_cus=0, _schedules={})
+    plan = batch.SmootherPipeline._plan(fake, wins, 64, 0.0)
+    assert (plan.ntiles, plan.nslices, plan.nwaves) == (ntiles, nslices, nwaves)
+    assert plan.table_shape() == (3, 3, 6, plan.items.shape[0], 4) and plan.items.shape[0] == 3
+    plan = batch.SmootherPipeline._plan(fake, wins, 128, 0.0)
+    assert plan.nslices == [1, 1, 2] and plan.table_shape() == (3, 2, 6, plan.items.shape[0], 4)
+
+
 def test_scheduled_smoother_validation():
     """include/ste.h (STE_VERSION 321): ste_urtss_backward_sched_f64 checks windows and tile list before it launches anything
     (no GPU needed): every window must take the one-kernel smoother, every tile appears once."""
@@ -188,8 +253,9 @@ def test_scheduled_smoother_validation():
     small = np.array([(0, t) for t in range(66)] + [(1, t) for t in range(64)], dtype=np.int32)
     assert "one-kernel smoother" in call(small)[1]
     # where the forward launch keeps its per-tile counters: behind its parameter blocks and its item table
+    # (and nothing behind them: the workspace ends with one int32 per tile, rounded up to 16 bytes)
     off = lib.ste_ukf_forward_sched_progress_offset(2, 2, 132, 3, 128)
-    assert 0 < off < lib.ste_ukf_forward_sched_workspace(2, 2, 132, 3, 128) and off % 16 == 0
+    assert off > 0 and off % 16 == 0 and off + _align16(4 * 132) == lib.ste_ukf_forward_sched_workspace(2, 2, 132, 3, 128)
 
 
 def _uniform(B, seed0, nobs=33, substeps=4):
@@ -453,3 +519,209 @@ def test_pipeline_shrinks_to_the_streams_scheduled_launches_need():
         assert all(_same(ref, d) for d in seqs)
         with pytest.raises(ValueError):
             pipe.shrink(0, 1)
+
+
+# ---- windows with UNEQUAL slice counts through the one-launch ("tile") smoothers ----------------------------------------------
+# The forward launch keeps a slice counter per tile in its workspace and the tile smoothers are handed their address:
+# dev_ws + ste_ukf_forward_sched_progress_offset(the five numbers the workspace was sized by).  Windows of 16, 68 and 132 steps
+# are 1, 2 and 3 slices of 64: 1 + 3 + 6 parameter blocks where the documented size holds 3 x 6, so a launch that lays its
+# workspace out by what its windows need keeps its counters 8 blocks in front of the documented offset.  Every test below
+# compares the bits with DeviceBatch.run() on each batch AND reads the counters back at the documented offset: each tile's
+# must hold its window's slice count (what the tile's last run published), whatever stale memory let through or did not.
+_UNEQUAL = ((130, 9, 2), (64, 18, 4), (200, 34, 4))  # (tracks, observations, sub-steps): 3 / 1 / 4 tiles, Nmax 16 / 68 / 132
+_DEFAULT_PATH = ((4160, 18, 4), (4160, 34, 4))  # above the two-kernel smoother's bound: 65 tiles each, Nmax 68 / 132
+_unequal_refs = {}
+
+
+def _unequal_ref(case, ragged, tuning):
+    """(host batch, its DeviceBatch.run()) for one (tracks, observations, sub-steps) case: computed once, never touched again."""
+    import dataclasses
+
+    import torch
+
+    key = (case, ragged, tuning)
+    if key not in _unequal_refs:
+        B, nobs, sub = case
+        _, hb = _uniform(B, 2_300_000 + 7000 * nobs, nobs=nobs, substeps=sub)
+        assert hb.Nmax == (nobs - 1) * sub
+        if ragged:  # tiles end slices early, the window's slice count (from Nmax) stays
+            hb = dataclasses.replace(hb, nsteps=np.maximum(1, hb.Nmax - (np.arange(hb.B) * 7) % 40).astype(np.int32))
+        hb = dataclasses.replace(hb, lanes=1)
+        ref = _clear(batch.DeviceBatch(hb, tuning=tuning))
+        ref.run()
+        torch.cuda.synchronize()
+        assert bool(ref.sm_mean.abs().sum() > 0)  # smoothed (and no NaN in it): zeros on both sides would compare equal
+        _unequal_refs[key] = (hb, ref)
+    return _unequal_refs[key]
+
+
+def _unequal_sequence(order, cases=_UNEQUAL, ragged=False, tuning=binding.STE_TUNING_ONE_KERNEL_SMOOTHER):
+    """References and fresh buffer sets for ``cases`` in ``order``, and the tiles per window."""
+    refs, seqs = [], []
+    for i in order:
+        hb, ref = _unequal_ref(cases[i], ragged, tuning)
+        refs.append(ref)
+        seqs.append(batch.DeviceBatch(hb, tuning=tuning))
+    return refs, seqs, [-(-cases[i][0] // 64) for i in order]
+
+
+def _submit_and_read(pipe, refs, seqs, **kw):
+    """One submit_sequence, synchronised before anything is looked at.  Returns what the assertions need: the launch, the
+    five numbers of its workspace, the int32 words at the documented counter offset, and bit-identity per window."""
+    import torch
+
+    for d in seqs:
+        _clear(d)
+    torch.cuda.synchronize()
+    pipe.submit_sequence(seqs, **kw)
+    launch = pipe._sched_live[-1]
+    pipe.synchronize()
+    shape = pipe._plan(launch.structs, int(kw.get("slice_steps", 0)) or binding.STE_SLICE_ALIGN, kw.get("stagger", 0.0)).table_shape()
+    off = int(pipe.lib.ste_ukf_forward_sched_progress_offset(*shape))
+    assert off % 4 == 0 and off + 4 * shape[2] <= launch.dev_ws.numel()
+    words = launch.dev_ws[off: off + 4 * shape[2]].view(torch.int32).cpu().numpy()
+    return launch, shape, words, [_same(r, d) for r, d in zip(refs, seqs)]
+
+
+def _assert_counters_and_bits(result, ntiles, nslices, what=None):
+    launch, shape, words, same = result
+    assert shape[:3] == (len(ntiles), max(nslices), sum(ntiles)) and shape[3] == launch.items.shape[0], (shape, what)
+    assert launch.smoother is not None, what  # one smoother launch, a wave per tile
+    # every tile's counter, at the documented offset, holds its window's slice count
+    assert np.array_equal(words, np.repeat(nslices, ntiles)), (words.tolist(), what)
+    assert all(same), (same, what)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", [(0, 1, 2), (2, 1, 0), (0, 2, 1)], ids=["ascending", "descending", "longest_in_the_middle"])
+def test_tile_smoothers_of_windows_with_unequal_slice_counts_are_bit_identical(order):
+    """Windows of 1, 2 and 3 slices (tiles that do and do not fill a wave) in three orders -- where a window's parameter blocks
+    start, and how far the packed blocks end in front of the documented region's end, depends on the order -- with and
+    without staggered deadlines."""
+    refs, seqs, ntiles = _unequal_sequence(order)
+    nslices = [(1, 2, 3)[i] for i in order]
+    results = []
+    with batch.SmootherPipeline(ntracks=200, sequence_only=True) as pipe:
+        for stagger in (0.0, 1.0):
+            results.append((stagger, _submit_and_read(pipe, refs, seqs, tile_smoothers=True, stagger=stagger)))
+    for stagger, res in results:
+        _assert_counters_and_bits(res, ntiles, nslices, stagger)
+
+
+@pytest.mark.gpu
+def test_tile_smoothers_of_ragged_tracks_in_windows_with_unequal_slice_counts_are_bit_identical():
+    """The same windows with tracks of their own lengths (up to 39 steps short, at least one step): tracks end inside a slice,
+    many have nothing to do in their window's last one, and every tile still publishes every slice of its window."""
+    refs, seqs, ntiles = _unequal_sequence((0, 1, 2), ragged=True)
+    assert seqs[2].hb.nsteps.min() < 128 < seqs[2].hb.nsteps.max() and seqs[0].hb.nsteps.min() == 1
+    with batch.SmootherPipeline(ntracks=200, sequence_only=True) as pipe:
+        res = _submit_and_read(pipe, refs, seqs, tile_smoothers=True)
+    _assert_counters_and_bits(res, ntiles, [1, 2, 3])
+
+
+@pytest.mark.gpu
+def test_tile_smoothers_with_slices_of_128_steps_are_bit_identical():
+    """slice_steps = 128: the same windows are 1, 1 and 2 slices -- the Python plan, the forward launch and the smoother launch
+    each derive the slice counts from the step they are given, and must agree."""
+    refs, seqs, ntiles = _unequal_sequence((0, 1, 2))
+    with batch.SmootherPipeline(ntracks=200, sequence_only=True) as pipe:
+        res = _submit_and_read(pipe, refs, seqs, tile_smoothers=True, slice_steps=128)
+    _assert_counters_and_bits(res, ntiles, [1, 1, 2])
+
+
+@pytest.mark.gpu
+def test_tile_smoothers_on_a_reused_workspace_full_of_stale_bytes_are_bit_identical():
+    """A pipeline's second sequence takes the first one's workspace from the pool.  The first (three windows of 3 slices) leaves
+    tables and non-zero counters behind; here the pooled workspaces are overwritten with 0x7f on top, so every word a smoother
+    wave may look at is a count no tile will ever reach unless this launch's own upload zeroed it."""
+    import torch
+
+    refs, seqs, ntiles = _unequal_sequence((0, 1, 2))
+    urefs, useqs, untiles = _unequal_sequence((2, 2, 2))
+    with batch.SmootherPipeline(ntracks=200, sequence_only=True) as pipe:
+        first = _submit_and_read(pipe, urefs, useqs, tile_smoothers=True)
+        pooled = list(pipe._sched_free.free)
+        for _host_ws, dev_ws, _counters in pooled:
+            dev_ws.fill_(0x7f)
+        torch.cuda.synchronize()
+        kept = {host_ws.data_ptr() for host_ws, _dev_ws, _counters in pooled}
+        res = _submit_and_read(pipe, refs, seqs, tile_smoothers=True)
+    _assert_counters_and_bits(first, untiles, [3, 3, 3], "uniform")
+    assert len(pooled) == 1 and res[0].host_ws.data_ptr() in kept and res[0].dev_ws.data_ptr() == pooled[0][1].data_ptr()
+    _assert_counters_and_bits(res, ntiles, [1, 2, 3], "reused")
+
+
+@pytest.mark.gpu
+def test_default_path_of_a_final_sequence_with_unequal_slice_counts_is_bit_identical():
+    """What submit_sequence does by itself for a job that is one sequence: batches of more than 4 096 tracks, final, nothing in
+    flight -- tile smoothers, no tuning bit -- at the smallest size that gets there, with windows of 2 and 3 slices."""
+    refs, seqs, ntiles = _unequal_sequence((0, 1), cases=_DEFAULT_PATH, tuning=0)
+    assert ntiles == [65, 65]
+    with batch.SmootherPipeline(ntracks=4160) as pipe:
+        res = _submit_and_read(pipe, refs, seqs)  # tile_smoothers=None, final=True
+    _assert_counters_and_bits(res, ntiles, [2, 3])
+
+
+@pytest.mark.gpu
+def test_c_calls_as_the_header_documents_them_smooth_windows_with_unequal_slice_counts():
+    """include/ste.h followed to the letter, without SmootherPipeline: ste_ukf_forward_sched_workspace, the forward launch with
+    zeroed counters and `started`, ste_stream_wait_counter on the started word in front of ste_urtss_backward_sched_f64 with
+    progress = dev_ws + ste_ukf_forward_sched_progress_offset(the same five numbers).  Two ordinary streams, pageable host
+    workspaces (the staged copy), four forward waves -- so tiles wait for a wave and five rounds go by."""
+    import torch
+
+    lib = binding.require_gpu()
+    refs, seqs, ntiles = _unequal_sequence((0, 1, 2))
+    nslices, n, nwaves, dev = [1, 2, 3], 3, 4, seqs[0].device
+    for d in seqs:
+        _clear(d)
+    structs = (binding.SteUkfBatchF64 * n)()
+    for i, d in enumerate(seqs):
+        st = binding.SteUkfBatchF64.from_buffer_copy(d.struct)
+        st.flags = (st.flags & ~binding.STE_FLAG_LANES_4) | binding.STE_FLAG_LANES_1
+        st.step_begin = st.step_end = 0
+        structs[i] = st
+    items = np.ascontiguousarray(batch.forward_schedule(ntiles, nslices, nwaves), dtype=np.int32)
+    assert items.shape == (5, nwaves, 2)
+    order = batch.smoother_tile_order(items, ntiles)
+    shape = (n, max(nslices), sum(ntiles), items.shape[0], nwaves)
+    nbytes = int(lib.ste_ukf_forward_sched_workspace(*shape))
+    off = int(lib.ste_ukf_forward_sched_progress_offset(*shape))
+    host_ws = np.zeros(nbytes, dtype=np.uint8)  # pageable
+    dev_ws = torch.full((nbytes,), 0x7f, dtype=torch.uint8, device=dev)  # the call fills it; nothing of this may show
+    counters = torch.zeros(n + 2, dtype=torch.int32, device=dev)  # window_done[n], error, started
+    sbytes = int(lib.ste_urtss_backward_sched_workspace(n, int(order.shape[0])))
+    s_host = np.zeros(sbytes, dtype=np.uint8)
+    s_dev = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+    fs, bs = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    torch.cuda.synchronize()  # uploads, clearing and zeroed counters are in memory before either stream starts
+    error, started = counters.data_ptr() + 4 * n, counters.data_ptr() + 4 * (n + 1)
+    sc = binding.SteFwdSchedF64()
+    sc.nwindows, sc.windows, sc.slice_steps = n, C.addressof(structs), 64
+    sc.nwaves, sc.nrounds, sc.items = nwaves, items.shape[0], items.ctypes.data
+    sc.host_ws, sc.dev_ws, sc.ws_bytes = host_ws.ctypes.data, dev_ws.data_ptr(), nbytes
+    sc.window_done, sc.error, sc.started = counters.data_ptr(), error, started
+    bw = binding.SteBwdSchedF64()
+    bw.nwindows, bw.windows, bw.slice_steps = n, C.addressof(structs), 64
+    bw.nitems, bw.items = int(order.shape[0]), order.ctypes.data
+    bw.host_ws, bw.dev_ws, bw.ws_bytes = s_host.ctypes.data, s_dev.data_ptr(), sbytes
+    bw.progress, bw.error = dev_ws.data_ptr() + off, error
+    calls = [lambda: lib.ste_ukf_forward_sched_f64(C.byref(sc), C.c_void_p(fs.cuda_stream)),
+             lambda: lib.ste_stream_wait_counter(started, nwaves, error, 0.0, C.c_void_p(bs.cuda_stream)),
+             lambda: lib.ste_urtss_backward_sched_f64(C.byref(bw), C.c_void_p(bs.cuda_stream))]
+    rcs = []
+    for call in calls:  # (nothing goes behind a call that was refused)
+        rcs.append((call(), lib.ste_last_error().decode()))
+        if rcs[-1][0] != 0:
+            break
+    fs.synchronize()
+    bs.synchronize()
+    assert [rc for rc, _ in rcs] == [0, 0, 0], rcs
+    words = counters.cpu().numpy()
+    assert words[n] == 0  # error word: neither a forward wave nor a smoother wave gave up
+    assert words[:n].tolist() == ntiles and words[n + 1] == nwaves  # window_done, started
+    progress = dev_ws[off: off + 4 * sum(ntiles)].view(torch.int32).cpu().numpy()
+    assert np.array_equal(progress, np.repeat(nslices, ntiles)), progress.tolist()
+    same = [_same(r, d) for r, d in zip(refs, seqs)]
+    assert all(same), same
+    del host_ws, s_host, s_dev, structs, items, order  # (alive until here: the launches read them)
