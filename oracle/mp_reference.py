@@ -13,6 +13,7 @@ reductions and Jacobi sweeps never appear.  Inputs are doubles and enter exactly
   * matrices ............ ``mp.eigsy``; principal square root with negative eigenvalues clamped; pseudo-inverse with NumPy's
                           ``rcond = 1e-15`` rule
   * one UKF step ........ predict / update (unscented.py:144-265) and the two robustification terms (:389-478)
+  * one smoother step ... unscented.py:285-351 for one k, in the two halves ``urts_gain`` and ``urts_combine``
 
 ``ulp_error(got, exact)`` measures a double against such a value in units of the spacing of doubles at the exact value.
 """
@@ -236,22 +237,26 @@ def sigma_weights(n=4):
     return w0, (1 - w0) / (2 * n)
 
 
-def sigma_points(x, P, scale):
-    """unscented.py:95-105: the 2n + 1 points x, x + col_i(T), x - col_i(T), T = sqrtm(scale P) -> list of lists."""
-    x = [mpf(float(v)) for v in np.asarray(x).ravel()]
+def sigma_points(x, P, scale, info=None):
+    """unscented.py:95-105: the 2n + 1 points x, x + col_i(T), x - col_i(T), T = sqrtm(scale P) -> list of lists.
+    ``info`` (a dict), where given, receives the eigenvalues of scale * P as ``eig_P``."""
+    x = [v if isinstance(v, mpf) else mpf(float(v)) for v in (x if isinstance(x, list) else np.asarray(x).ravel())]
     n = len(x)
-    T, _ = sym_sqrt(P, scale)
+    T, w = sym_sqrt(P, scale)
+    if info is not None:
+        info["eig_P"] = w
     pts = [list(x)]
     pts += [[x[r] + T[r, i] for r in range(n)] for i in range(n)]
     pts += [[x[r] - T[r, i] for r in range(n)] for i in range(n)]
     return pts
 
 
-def ukf_predict(x, P, Q, dt, sog_rate, cog_rate, noise=None):
-    """unscented.py:178-207 for n = 4.  Returns (x_pred list of 4 mpf, P_pred 4 x 4 mp.matrix)."""
+def ukf_predict(x, P, Q, dt, sog_rate, cog_rate, noise=None, info=None):
+    """unscented.py:178-207 for n = 4.  Returns (x_pred list of 4 mpf, P_pred 4 x 4 mp.matrix).  ``x`` and ``P`` may be
+    doubles or values of this module's context (the output of another step); ``info``: see ``sigma_points``."""
     n = 4
     w0, wi = sigma_weights(n)
-    sig = [geodetic_step(p, dt, sog_rate, cog_rate) for p in sigma_points(x, P, n / (1 - w0))]
+    sig = [geodetic_step(p, dt, sog_rate, cog_rate) for p in sigma_points(x, P, n / (1 - w0), info)]
     wts = [w0] + [wi] * (2 * n)
     xp = [mp.fsum(w * s[c] for w, s in zip(wts, sig)) for c in range(n)]
     if noise is not None:
@@ -268,23 +273,78 @@ def _mod360(v):
     return v - 360 * mp.floor(v / 360)
 
 
-def ukf_update(x, P, H, R, z, noise=None):
-    """unscented.py:219-265 (linear update, pinv gain, heading wraps, Joseph form).  Returns (x list, P mp.matrix)."""
+def ukf_update(x, P, H, R, z, noise=None, info=None):
+    """unscented.py:219-265 (linear update, pinv gain, heading wraps, Joseph form).  Returns (x list, P mp.matrix).
+    ``x`` and ``P`` may be doubles or values of this module's context (the output of ``ukf_predict``); ``info`` (a dict),
+    where given, receives the eigenvalues of S as ``eig_S`` and the new heading before its reduction mod 360 as
+    ``heading_unwrapped``."""
     n = 4
-    xv, zv = vec(x), vec(z)
+    xv = mp.matrix(list(x)) if isinstance(x, list) else vec(x)
+    zv = vec(z)
     if noise is not None:
         zv = zv + vec(noise)
-    Pm, Hm, Rm = mat(P), mat(H), mat(R)
+    Pm = P if isinstance(P, mp.matrix) else mat(P)
+    Hm, Rm = mat(H), mat(R)
     S = Hm * Pm * Hm.T + Rm
-    Si, _, _ = pinv_sym(S)
+    Si, w, _ = pinv_sym(S)
+    if info is not None:
+        info["eig_S"] = w
     K = Pm * Hm.T * Si
     y = zv - Hm * xv
     y[3] = _mod360(y[3] + 180) - 180
     xn = xv + K * y
+    if info is not None:
+        info["heading_unwrapped"] = xn[3]
     xn[3] = _mod360(xn[3])
     A = mp.eye(n) - K * Hm
     Pn = A * Pm * A.T + K * Rm * K.T
     return [xn[i] for i in range(n)], Pn
+
+
+def urts_gain(xk, Pk, Q, dt, sog_rate, cog_rate, noise=None, info=None):
+    """The half of one smoother step that needs the filtered row alone (unscented.py:300-336): the fan of (x_k, P_k), its
+    propagation, x_b = the weighted mean (plus ``noise``), P_b centred on x_k -- not on x_b -- plus Q, D between the
+    unpropagated deviations about x_k and the propagated deviations about x_b, and K = D pinv(P_b).
+    Returns (x_b list of 4 mpf, P_b, K); ``info`` receives ``eig_P`` (of the scaled P_k) and ``eig_Pb``."""
+    n = 4
+    w0, wi = sigma_weights(n)
+    wts = [w0] + [wi] * (2 * n)
+    sig0 = sigma_points(xk, Pk, n / (1 - w0), info)
+    sig = [geodetic_step(p, dt, sog_rate, cog_rate) for p in sig0]
+    xb = [mp.fsum(w * s[c] for w, s in zip(wts, sig)) for c in range(n)]
+    if noise is not None:
+        xb = [v + mpf(float(e)) for v, e in zip(xb, np.asarray(noise).ravel())]
+    x0 = sig0[0]
+    Qm = Q if isinstance(Q, mp.matrix) else mat(Q)
+    Pb, D = mp.zeros(n, n), mp.zeros(n, n)
+    for r in range(n):
+        for c in range(n):
+            Pb[r, c] = mp.fsum(w * (s[r] - x0[r]) * (s[c] - x0[c]) for w, s in zip(wts, sig)) + Qm[r, c]
+            D[r, c] = mp.fsum(w * (a[r] - x0[r]) * (s[c] - xb[c]) for w, a, s in zip(wts, sig0, sig))
+    Pi, w, _ = pinv_sym(Pb)
+    if info is not None:
+        info["eig_Pb"] = w
+    return xb, Pb, D * Pi
+
+
+def urts_combine(xk, Pk, xs_next, Ps_next, xb, Pb, K, info=None):
+    """The other half (unscented.py:338-349): the innovation against the smoothed row k + 1 with its heading wrapped to
+    +-180, the new heading mod 360, and P_s = P_k + K (P_s,next - P_b) K^T.  ``info`` receives ``heading_unwrapped``."""
+    y = vec(xs_next) - mp.matrix(xb)
+    y[3] = _mod360(y[3] + 180) - 180
+    xs = vec(xk) + K * y
+    if info is not None:
+        info["heading_unwrapped"] = xs[3]
+    xs[3] = _mod360(xs[3])
+    Ps = mat(Pk) + K * (mat(Ps_next) - Pb) * K.T
+    return [xs[i] for i in range(4)], Ps
+
+
+def urts_step(xk, Pk, xs_next, Ps_next, Q, dt, sog_rate, cog_rate, noise=None, info=None):
+    """One step of the unscented RTS smoother (unscented.py:285-351 for one k, as ``ukf_oracle.backward_track`` restates
+    it): from the filtered row k and the smoothed row k + 1 to the smoothed row k.  Returns (x_s list of 4 mpf, P_s)."""
+    xb, Pb, K = urts_gain(xk, Pk, Q, dt, sog_rate, cog_rate, noise, info)
+    return urts_combine(xk, Pk, xs_next, Ps_next, xb, Pb, K, info)
 
 
 def robust_terms(x, P, H, R, z):

@@ -3,6 +3,9 @@
 A reference that is itself wrong would pass wrong kernels, so it is checked here against independent float64 libraries:
 libm-grade functions within 1 ulp, NumPy's floored modulo bit for bit, matrix functions and the UKF step to rounding.  The
 same runs produce the host baselines (``e_host``) that tests/test_math_probe.py holds the device to; they are printed.
+
+The last section does the same for tests/test_step_residuals.py: the smoother step against the oracle, the exclusions' caps
+on the oracle's own histories of every case, and a checker that fails on a 1e-11 slip and names the pair.
 """
 import math
 
@@ -11,6 +14,7 @@ import pytest
 import scipy.linalg
 
 import math_probe_cases as mc
+import step_residual_cases as sr
 from oracle import mp_reference as mpr
 from oracle import ukf_oracle as orc
 
@@ -117,3 +121,101 @@ def test_ukf_step_against_the_float64_oracle():
         print(f"\n[oracle baseline] {route}: {e}")
         assert all(v < 1e-10 for v in e.values()), e
     assert b.count == 130
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the row-by-row residuals of tests/test_step_residuals.py: the smoother step, the exclusions and the checker, on the CPU
+# ----------------------------------------------------------------------------------------------------------------------
+def _history64():
+    """Six full tracks of 64 steps (an update every fourth) and the float64 oracle's histories of them."""
+    from track_estimators import batch, synthetic
+
+    H, Q, R, P0 = synthetic.example_matrices()
+    hb = batch.pack_uniform(synthetic.make_batch(6, nobs=17, gap_h=1.0, seed0=6100), 4, H, Q, R, P0)
+    return (hb,) + sr.oracle_history(hb)
+
+
+def test_urts_step_against_the_float64_oracle():
+    """One turn of ukf_oracle.backward_track's loop (the reference's own calls on a history of two rows) against urts_step on
+    every third row of a 64-step history, at the bound of the predict / update test above: cond(P_b) stays below 1e2 here, so
+    the pseudo-inverse amplifies nothing and 1e-10 separates rounding from a wrong term (P_b centred on x_b instead of x_k
+    shows at 1e-3)."""
+    hb, hist, status = _history64()
+    assert hb.Nmax == 64 and not status.any()
+    m, P, sm, sP = (hist[k] for k in ("means", "covs", "means_smoothed", "covs_smoothed"))
+    em = ec = 0.0
+    for b in range(hb.B):
+        for k in range(0, hb.Nmax, 3):
+            s = sr.step_inputs(hb, (b, k))
+            x, C = mpr.urts_step(m[b, k], P[b, k], sm[b, k + 1], sP[b, k + 1], s.Q, s.dt, s.sog_rate_rts, s.cog_rate_rts)
+            assert isinstance(C, mpr.mp.matrix) and len(x) == 4
+            hx, hC = sr.smoother_host(hb, (m[b, k], P[b, k]), (sm[b, k + 1], sP[b, k + 1]), (b, k))
+            em = max(em, sr.mean_errs(hx, np.array([float(v) for v in x])).max())
+            ec = max(ec, sr.cov_errs(hC, mpr.to_np(C)).max())
+    print(f"\n[oracle baseline] urts_step, 132 pairs: mean {em:.3e}, cov {ec:.3e}")
+    assert em < 1e-10 and ec < 1e-10
+
+
+def test_urts_step_with_noise_and_its_centring():
+    """The recorded noise enters x_b and with it the innovation and D, not P_b, which stays centred on x_k."""
+    hb, hist, _ = _history64()
+    m, P, sm, sP = (hist[k] for k in ("means", "covs", "means_smoothed", "covs_smoothed"))
+    b, k = 2, 30
+    s = sr.step_inputs(hb, (b, k))
+    nz = np.array([1e-3, -2e-3, 5e-4, 1e-2])
+    xb0, Pb0, _ = mpr.urts_gain(m[b, k], P[b, k], s.Q, s.dt, s.sog_rate_rts, s.cog_rate_rts)
+    xb1, Pb1, _ = mpr.urts_gain(m[b, k], P[b, k], s.Q, s.dt, s.sog_rate_rts, s.cog_rate_rts, nz)
+    assert mpr.max_abs(Pb1 - Pb0) == 0 and all(abs(a - c - mpr.mpf(float(e))) < 1e-45 for a, c, e in zip(xb1, xb0, nz))
+    x, C = mpr.urts_step(m[b, k], P[b, k], sm[b, k + 1], sP[b, k + 1], s.Q, s.dt, s.sog_rate_rts, s.cog_rate_rts, nz)
+    hx, hC = orc.backward_track(np.array([m[b, k], sm[b, k + 1]]), np.array([P[b, k], sP[b, k + 1]]), s.Q, [s.dt], 1,
+                                [s.sog_rate_rts], [s.cog_rate_rts], [nz])
+    assert sr.mean_errs(hx[0], np.array([float(v) for v in x])).max() < 1e-10 and sr.cov_errs(hC[0], mpr.to_np(C)).max() < 1e-10
+
+
+@pytest.mark.parametrize("name", sr.CASES)
+def test_exclusion_caps_on_the_oracles_history(name):
+    """The exclusions of tests/test_step_residuals.py, counted on the float64 oracle's history of every case it runs: none on
+    the synthetic cases, at most 5 % on a regime and never a whole row class (steps 0-2, 62-64, a track's last).  The oracle's
+    own rows also pass the comparison, batched (eigh) against per-track (sqrtm) arithmetic."""
+    hb = sr.build_case(name)
+    hist, status = sr.oracle_history(hb)
+    assert len(sr.pairs(hb.nsteps)) <= sr.MAX_PAIRS
+    for which in ("forward", "smoother"):
+        r, all_pairs, left_out, _ = sr.residuals(hb, hist, status, which)
+        sr.report(name + " (oracle)", which, r)
+        sr.check_caps(sr.case_kind(name), all_pairs, left_out, hb.nsteps)
+        assert r.npairs == len(all_pairs) - len(left_out) > 0
+        sr.check(name + " (oracle)", which, r)
+
+
+def test_pairs_cover_the_rows_they_name():
+    import step_loop_cases as slc
+    n = slc.ragged_lengths()
+    ps = sr.pairs(n)
+    assert len(ps) == len(set(ps)) <= sr.MAX_PAIRS and all(0 <= k < n[b] for b, k in ps)
+    assert {b for b, _ in ps} == {1, 2, 3, 4, 5, 6, 7, 20, 31, 42, 53, 62, 63, 64}  # slot 0 has no step
+    for b in (6, 64):  # the 65-step tracks: both sides of the restart, the last step, every 7th between
+        assert [k for t, k in ps if t == b] == [0, 1, 2, 7, 14, 21, 28, 35, 42, 49, 56, 62, 63, 64]
+    assert [k for t, k in ps if t == 4] == [0, 1, 2, 7, 14, 21, 28, 35, 42, 49, 56, 62]  # 63 steps: ends before the restart
+    assert sr.row_classes((5, 63), n) == ["restart", "last"] and sr.row_classes((3, 2), n) == ["first", "last"]
+
+
+PERTURB_MEAN, PERTURB_COV = 1e-11, 1e-10
+
+
+def test_the_checker_has_teeth():
+    """The oracle's rows as 'got', one element of one mean multiplied by 1 + 1e-11, one covariance entry moved by 1e-10 of
+    max |P|: the comparison of tests/test_step_residuals.py fails and names the pair.  Unperturbed it passes."""
+    hb, hist, status = _history64()
+    for which, mkey, ckey, row in (("forward", "means", "covs", 1), ("smoother", "means_smoothed", "covs_smoothed", 0)):
+        r, all_pairs, left_out, (got, ref, host, kept) = sr.residuals(hb, hist, status, which)
+        sr.check("teeth", which, r)
+        assert not left_out
+        b, k = 4, 21
+        assert (b, k) in kept
+        for key, el, factor in ((mkey, (1,), 1 + PERTURB_MEAN), (ckey, (0, 1), None)):
+            bent = {p: (v[0].copy(), v[1].copy()) for p, v in got.items()}
+            a = bent[(b, k)][0 if key == mkey else 1]
+            a[el] = a[el] * factor if factor is not None else a[el] + PERTURB_COV * np.max(np.abs(a))
+            with pytest.raises(AssertionError, match=rf"track {b}, step {k}, entry \({el[0]},"):
+                sr.check("teeth", which, sr.measure(kept, bent, ref, host))
